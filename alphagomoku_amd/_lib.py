@@ -126,6 +126,11 @@ class AgxEdgeView(ctypes.Structure):
                 ("reserved", ctypes.c_uint16)]
 
 
+class AgxNodeView(ctypes.Structure):
+    _fields_ = [("found", ctypes.c_int), ("visits", ctypes.c_int), ("win", ctypes.c_float), ("draw", ctypes.c_float), ("moves_left", ctypes.c_float)] + \
+               [(n, ctypes.c_int) for n in ["score", "flags", "sign_to_move", "depth", "virtual_loss", "n_edges"]]
+
+
 class AgxGameInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ["active", "sign_to_move", "n_moves", "outcome", "error", "opening_id", "games_done",
                                             "n_nodes", "n_edges", "root_visits"]] + \
@@ -190,6 +195,9 @@ def _declare(c):  # noqa: F811
     c.agx_stream_destroy.argtypes = [vp]
     c.agx_stream_synchronize.argtypes = [vp]
     c.agx_engine_set_board.argtypes = [vp, ci, vp, ci, vp]
+    c.agx_engine_set_board_ex.argtypes = [vp, ci, vp, ci, ci, vp]
+    c.agx_engine_node_info.argtypes = [vp, ci, vp, vp, ci, vp, vp, ci, vp]
+    c.agx_engine_principal_variation.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, ctypes.POINTER(ci), vp]
     c.agx_engine_set_max_simulations.argtypes = [vp, ci]
     c.agx_engine_set_batch_size.argtypes = [vp, ci]
     c.agx_engine_solve_timed_group.argtypes = [vp, ci, ci, ci, ctypes.c_double, vp]

@@ -806,8 +806,6 @@ namespace ag
 		GamePool &p = bound();
 		if (!standalone)
 			throw std::logic_error("Tree::setBoard() : the trees of a pool slice take their positions from the pool's own games");
-		if (forceRemoveRootNode)
-			throw std::logic_error("Tree::setBoard() : forceRemoveRootNode is not provided by the device tree");
 		if (newBoard.rows() != p.getGameConfig().rows || newBoard.cols() != p.getGameConfig().cols)
 			throw std::logic_error("Tree::setBoard() : the board is " + std::to_string(newBoard.rows()) + "x" + std::to_string(newBoard.cols()) + ", the search was created for "
 					+ std::to_string(p.getGameConfig().rows) + "x" + std::to_string(p.getGameConfig().cols));
@@ -816,7 +814,10 @@ namespace ag
 		std::vector<uint8_t> cells(static_cast<size_t>(newBoard.size()));
 		for (int i = 0; i < newBoard.size(); i++)
 			cells[i] = static_cast<uint8_t>(newBoard[i]);
-		check(agx_engine_set_board(p.handle(), 0, cells.data(), static_cast<int>(signToMove), stream));
+		if (forceRemoveRootNode) // Tree.cpp:145-147: the node of the new position is dropped, its children stay
+			check(agx_engine_set_board_ex(p.handle(), 0, cells.data(), static_cast<int>(signToMove), 1, stream));
+		else
+			check(agx_engine_set_board(p.handle(), 0, cells.data(), static_cast<int>(signToMove), stream));
 		summary_valid = false;
 		edge_selector.reset();  // a fresh selector / generator per position, as Player::setBoard installs them
 		edge_generator.reset();
@@ -986,7 +987,22 @@ namespace ag
 	Node Tree::getInfo(int game, const std::vector<Move> &moves) const
 	{
 		if (!moves.empty())
-			throw std::logic_error("Tree::getInfo() : only the root (an empty move list) can be read from the device");
+		{ // Tree.cpp:403-424: the moves on a copy of the base board with alternating colours, the position sought in the node cache
+			std::vector<uint16_t> path;
+			for (const Move &m : moves)
+				path.push_back(m.toShort());
+			const int offsets[2] = { 0, static_cast<int>(path.size()) };
+			AgxNodeView view;
+			std::vector<AgxEdgeView> views(static_cast<size_t>(bound().getGameConfig().rows) * bound().getGameConfig().cols);
+			check(agx_engine_node_info(bound().handle(), first_game + game, path.data(), offsets, 1, &view, views.data(), static_cast<int>(views.size()), stream));
+			if (!view.found)
+				return Node();
+			std::vector<Edge> edges;
+			for (int i = 0; i < view.n_edges; i++)
+				edges.emplace_back(views[i]);
+			return Node(std::move(edges), Value(view.win, view.draw), Score::from_short(static_cast<uint16_t>(view.score)), view.visits,
+					static_cast<Sign>(view.sign_to_move));
+		}
 		std::vector<AgxEdgeView> views;
 		const AgxGameInfo info = game_info(bound(), first_game + game, &views);
 		std::vector<Edge> edges;
@@ -994,6 +1010,21 @@ namespace ag
 			edges.emplace_back(v);
 		return Node(std::move(edges), Value(info.root_win, info.root_draw), Score::from_short(static_cast<uint16_t>(info.root_score)), info.root_visits,
 				static_cast<Sign>(info.sign_to_move));
+	}
+	std::vector<Move> Tree::getPrincipalVariation(const std::vector<Move> &moves, int game) const
+	{
+		std::vector<uint16_t> path;
+		for (const Move &m : moves)
+			path.push_back(m.toShort());
+		const int cells = bound().getGameConfig().rows * bound().getGameConfig().cols;
+		std::vector<uint16_t> pv(static_cast<size_t>(cells));
+		int length = 0;
+		check(agx_engine_principal_variation(bound().handle(), first_game + game, path.data(), static_cast<int>(path.size()), cells, pv.data(), nullptr, nullptr,
+				&length, stream));
+		std::vector<Move> result;
+		for (int i = 0; i < length; i++)
+			result.push_back(Move(pv[i]));
+		return result;
 	}
 	NodeCacheStats Tree::getNodeCacheStats() const noexcept
 	{

@@ -33,6 +33,7 @@
 #include <chrono>
 #include <mutex>
 #include <cstring>
+#include <algorithm>
 
 using namespace agx;
 using namespace agx::dev;
@@ -1895,8 +1896,10 @@ namespace
 	 * prepare_search / Player::setBoard for tree t on the position in its GameState (GameGenerator.cpp:174-185, Player.cpp:98-110):
 	 * NodeCache::cleanup (NodeCache.cpp:221-249) as keep-test + prefix sum + copy to the other arena, Search::setBoard
 	 * (increaseGeneration), Tree::setBoard (root = seek(new board), Tree.cpp:146-149).  Whole workgroup of TPB threads.
+	 * DropRoot (set-board with forceRemoveRootNode, Tree.cpp:145-147): the keep test also drops the node of the new position itself, so the
+	 * root is absent afterwards; nothing points at it (children are found by hash) and the table is rebuilt from the kept nodes.
 	 */
-	template<int TPB>
+	template<int TPB, bool DropRoot = false>
 	__device__ void rebase_tree(const EngineDev &E0, int t, int tid, u64 *scratch, int *scan_nodes, int *scan_edges)
 	{
 		EngineDev E = E0;
@@ -1912,6 +1915,14 @@ namespace
 			ht[i] = 0;
 		const int total = gs.n_nodes;
 		int node_base = 0, edge_base = 0;
+		u64 drop_hash = 0;
+		if constexpr (DropRoot)
+		{ // the new root's key, before the scan
+			for (int i = tid; i < E.hw; i += TPB)
+				drop_hash ^= E.nc_keys[3 + 3 * i + gs.board[i]];
+			block_reduce_xor<TPB>(drop_hash, scratch, tid);
+			drop_hash ^= E.nc_keys[gs.sign_to_move];
+		}
 		__syncthreads();
 		for (int base = 0; base < total; base += TPB)
 		{
@@ -1920,10 +1931,17 @@ namespace
 			if (i < total)
 			{
 				keep = 1;
+				u64 differs = 0;
 				for (int w = 0; w < BWORDS; w++)
 				{ // isTransitionPossibleFrom (NodeCache.cpp:95-115): every stone of the new position must be present
 					const u64 from = gs.cboard[w], to = nodes[i].cboard[w];
 					if (((from ^ to) & from) != 0)
+						keep = 0;
+					differs |= from ^ to;
+				}
+				if constexpr (DropRoot)
+				{ // NodeCache::remove(newBoard, signToMove): same key, same side to move, same board
+					if (differs == 0 && nodes[i].hash == drop_hash && nodes[i].sign_to_move == gs.sign_to_move)
 						keep = 0;
 				}
 				ne = keep ? nodes[i].n_edges : 0;
@@ -2888,7 +2906,7 @@ namespace
 			}
 		}
 	}
-	__global__ __launch_bounds__(256) void k_set_board(EngineDev E, int g, const uint8_t *board, int sign_to_move)
+	__global__ __launch_bounds__(256) void k_set_board(EngineDev E, int g, const uint8_t *board, int sign_to_move, int force_remove_root)
 	{
 		__shared__ u64 scratch[4];
 		__shared__ int scan_nodes[256], scan_edges[256];
@@ -2922,7 +2940,10 @@ namespace
 			gs.active = 1;
 		}
 		__syncthreads();
-		rebase_tree<256>(E, g, tid, scratch, scan_nodes, scan_edges);
+		if (force_remove_root)
+			rebase_tree<256, true>(E, g, tid, scratch, scan_nodes, scan_edges);
+		else
+			rebase_tree<256>(E, g, tid, scratch, scan_nodes, scan_edges);
 		if (E.shared_tree)
 		{ // every task buffer of the tree follows (its solver table ages with the tree's, Search::setBoard -> increaseGeneration)
 			__syncthreads();
@@ -2968,6 +2989,166 @@ namespace
 		out[1] = proven;
 		out[2] = gs.n_nodes;
 		out[3] = gs.error;
+	}
+
+	/* Tree::getInfo(moves) / the principal variation (agx_engine_node_info / agx_engine_principal_variation): read-only walks over one tree's
+	 * node cache, one wave per walk.  The position is the compressed board in LDS plus the node-cache key, updated per ply like the descent
+	 * updates them (k_select); the colours alternate from the base board's side to move (Tree.cpp:403-424). */
+	struct QueryWalk
+	{
+			u64 hash;
+			int sign;
+			bool valid; // false once a move hit an occupied cell: the reference's empty Node()
+	};
+	__device__ inline void query_begin(const EngineDev &E, const GameState &gs, u64 *sh_cboard, QueryWalk &q, int lane)
+	{
+		if (lane < BWORDS)
+			sh_cboard[lane] = gs.cboard[lane];
+		q.sign = gs.sign_to_move;
+		q.hash = full_hash(E, gs.board, q.sign, lane);
+		q.valid = true;
+		__syncthreads();
+	}
+	__device__ inline void query_place(const EngineDev &E, u64 *sh_cboard, QueryWalk &q, uint32_t move, int lane)
+	{ // (row, col) < n: checked by the host for caller paths, edge moves are cells of the board
+		if (!q.valid)
+			return;
+		const int cell = ((move >> 2) & 127) * E.n + ((move >> 9) & 127), w = cell >> 5, shift = 2 * (cell & 31);
+		const bool empty = ((sh_cboard[w] >> shift) & 3ull) == 0;
+		__syncthreads();
+		if (!empty)
+		{
+			q.valid = false;
+			return;
+		}
+		if (lane == 0)
+			sh_cboard[w] |= static_cast<u64>(q.sign) << shift;
+		q.hash ^= E.nc_keys[3 + 3 * cell] ^ E.nc_keys[3 + 3 * cell + q.sign] ^ E.nc_keys[q.sign] ^ E.nc_keys[3 - q.sign];
+		q.sign = 3 - q.sign;
+		__syncthreads();
+	}
+	__device__ inline void query_write_node(AgxNodeView *out, const DNode *nd, int lane)
+	{ // nd == nullptr: not found
+		if (lane != 0)
+			return;
+		AgxNodeView v;
+		v.found = (nd != nullptr) ? 1 : 0;
+		v.visits = nd ? nd->visits : 0;
+		v.win = nd ? nd->win : 0.0f;
+		v.draw = nd ? nd->draw : 0.0f;
+		v.moves_left = nd ? nd->moves_left : 0.0f;
+		v.score = nd ? nd->score : 0;
+		v.flags = nd ? nd->flags : 0;
+		v.sign_to_move = nd ? nd->sign_to_move : 0;
+		v.depth = nd ? nd->depth : 0;
+		v.virtual_loss = nd ? nd->vl : 0;
+		v.n_edges = nd ? nd->n_edges : 0;
+		*out = v;
+	}
+	__device__ __forceinline__ void query_write_edge(AgxEdgeView *out, const DEdge &d)
+	{
+		AgxEdgeView v;
+		v.prior = d.prior;
+		v.win = d.win;
+		v.draw = d.draw;
+		v.visits = d.visits;
+		v.move = d.move;
+		v.score = d.score;
+		v.flag_and_virtual_loss = d.flag_vl;
+		v.reserved = 0;
+		*out = v;
+	}
+	/* BestEdgeSelector (EdgeSelector.cpp:515-536): the rating of k_advance's default final selector, the same arithmetic */
+	__device__ __forceinline__ float best_edge_rating(const DEdge &e, const DNode &parent)
+	{
+		switch (s_pv(e.score))
+		{
+			case 0:
+				return -1.0e8f + s_distance(e.score);
+			case 3:
+				return +1.0e8f - s_distance(e.score);
+			default:
+				return e.visits + (e.win + 0.5f * e.draw) * parent.visits + 0.001f * e.prior;
+		}
+	}
+
+	/* One wave per path (agx_engine_node_info): path p is moves[offsets[p] .. offsets[p + 1]) */
+	__global__ __launch_bounds__(64) void k_node_info(EngineDev E, int t, const uint16_t *moves, const int *offsets, AgxNodeView *out_nodes,
+			AgxEdgeView *out_edges, int edges_per_path)
+	{
+		__shared__ u64 sh_cboard[BWORDS];
+		const int p = blockIdx.x, lane = threadIdx.x;
+		use_game_arenas(E, t);
+		const GameState &gs = E.games[t];
+		const DNode *nodes = nodes_of(E, t, gs.arena);
+		const DEdge *edges = edges_of(E, t, gs.arena);
+		QueryWalk q;
+		query_begin(E, gs, sh_cboard, q, lane);
+		for (int k = offsets[p]; k < offsets[p + 1] && q.valid; k++)
+			query_place(E, sh_cboard, q, moves[k], lane);
+		const int found = q.valid ? cache_seek(E, nodes, ht_of(E, t), q.hash, sh_cboard, q.sign, lane) : -1;
+		query_write_node(out_nodes + p, (found >= 0) ? nodes + found : nullptr, lane);
+		if (found >= 0)
+		{
+			const DNode &nd = nodes[found];
+			const int count = min(static_cast<int>(nd.n_edges), edges_per_path);
+			for (int i = lane; i < count; i += 64)
+				query_write_edge(out_edges + static_cast<size_t>(p) * edges_per_path + i, edges[nd.edge_begin + i]);
+		}
+	}
+
+	/* The principal variation (agx_engine_principal_variation, one wave): the path, then BestEdgeSelector's edge and its child while the node
+	 * is cached and has edges, at most max_length plies.  out_nodes[k] is the node after k plies (max_length + 1 records). */
+	__global__ __launch_bounds__(64) void k_principal_variation(EngineDev E, int t, const uint16_t *moves, int n_moves, int max_length, int *out_length,
+			uint16_t *out_pv, AgxEdgeView *out_edges, AgxNodeView *out_nodes)
+	{
+		__shared__ u64 sh_cboard[BWORDS];
+		const int lane = threadIdx.x;
+		use_game_arenas(E, t);
+		const GameState &gs = E.games[t];
+		const DNode *nodes = nodes_of(E, t, gs.arena);
+		const DEdge *edges = edges_of(E, t, gs.arena);
+		const int *ht = ht_of(E, t);
+		QueryWalk q;
+		query_begin(E, gs, sh_cboard, q, lane);
+		for (int k = 0; k < n_moves && q.valid; k++)
+			query_place(E, sh_cboard, q, moves[k], lane);
+		int length = 0;
+		while (true)
+		{
+			const int found = q.valid ? cache_seek(E, nodes, ht, q.hash, sh_cboard, q.sign, lane) : -1;
+			query_write_node(out_nodes + length, (found >= 0) ? nodes + found : nullptr, lane);
+			if (found < 0 || length >= max_length)
+				break;
+			DNode nd;
+			node_head(nd, nodes[found]);
+			if (nd.n_edges <= 0)
+				break;
+			float best_value = -3.402823466e+38f;
+			int best = 0x7FFFFFFF;
+			for (int i = lane; i < nd.n_edges; i += 64)
+			{ // first strict maximum per lane, then the lowest index among the lanes' maxima (k_advance's tie rule)
+				const float value = best_edge_rating(edges[nd.edge_begin + i], nd);
+				if (value > best_value)
+				{
+					best_value = value;
+					best = i;
+				}
+			}
+			wave_argmax(best_value, best);
+			if (best >= nd.n_edges)
+				break; // (no edge rated above the floor: only NaN ratings)
+			const DEdge chosen = edges[nd.edge_begin + best];
+			if (lane == 0)
+			{
+				out_pv[length] = chosen.move;
+				query_write_edge(out_edges + length, chosen);
+			}
+			query_place(E, sh_cboard, q, chosen.move, lane);
+			length++;
+		}
+		if (lane == 0)
+			*out_length = length;
 	}
 	__global__ void k_reset_counter(int *counter, int *second)
 	{
@@ -3101,6 +3282,10 @@ struct AgxEngine
 		bool sizing_only = false; // agx_engine_estimate_device_bytes: dev_alloc only adds up, nothing touches a device
 		int sizing_cus = 0;
 		int *summary_dev = nullptr, *summary_host = nullptr; // agx_engine_root_summary: four words on their way back (device, pinned host)
+		// agx_engine_node_info / agx_engine_principal_variation: the paths on their way to the device and the answers on their way back, one
+		// staging buffer each side (grown on demand)
+		uint8_t *query_dev = nullptr, *query_host = nullptr;
+		size_t query_bytes = 0;
 		bool speculative = false;
 		bool external_moves = false; // agx_engine_set_board has been called: the caller makes the moves, no advance stage services the arenas
 		int spec_waves = 0; // waves of that launch over the whole pool
@@ -3556,6 +3741,8 @@ int agx_engine_destroy(AgxEngine *e)
 		(void) hipEventDestroy(ev);
 	if (e->summary_host != nullptr)
 		(void) hipHostFree(e->summary_host);
+	if (e->query_host != nullptr)
+		(void) hipHostFree(e->query_host);
 	delete e;
 	return AGX_OK;
 }
@@ -4034,6 +4221,10 @@ int agx_engine_match_results(AgxEngine *e, int *h_results, int pair_capacity)
 
 int agx_engine_set_board(AgxEngine *e, int game, const uint8_t *h_board, int sign_to_move, void *stream)
 {
+	return agx_engine_set_board_ex(e, game, h_board, sign_to_move, 0, stream);
+}
+int agx_engine_set_board_ex(AgxEngine *e, int game, const uint8_t *h_board, int sign_to_move, int force_remove_root, void *stream)
+{
 	AGX_REQUIRE(e != nullptr && h_board != nullptr, AGX_ERR_INVALID, "agx_engine_set_board: null argument");
 	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_set_board: agx_engine_begin has not been called");
 	AGX_REQUIRE(game >= 0 && game < e->dev.n_games, AGX_ERR_INVALID, "agx_engine_set_board: game %d of %d", game, e->dev.n_games);
@@ -4055,7 +4246,7 @@ int agx_engine_set_board(AgxEngine *e, int game, const uint8_t *h_board, int sig
 		one.g0 = game;
 		hipLaunchKernelGGL(k_cancel_pending, dim3(1), dim3(64), 0, s, one);
 	}
-	hipLaunchKernelGGL(k_set_board, dim3(1), dim3(256), 0, s, e->dev, game, e->board_staging, sign_to_move);
+	hipLaunchKernelGGL(k_set_board, dim3(1), dim3(256), 0, s, e->dev, game, e->board_staging, sign_to_move, force_remove_root ? 1 : 0);
 	e->external_moves = true;
 	AGX_HIP_CHECK(hipGetLastError());
 	return AGX_OK;
@@ -4148,6 +4339,136 @@ int agx_engine_root_summary(AgxEngine *e, int game, void *stream, int *out4)
 	AGX_HIP_CHECK(hipMemcpyAsync(e->summary_host, e->summary_dev, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
 	AGX_HIP_CHECK(hipStreamSynchronize(s)); // THIS stream only: a network launch on another stream keeps running
 	std::memcpy(out4, e->summary_host, 4 * sizeof(int));
+	return AGX_OK;
+}
+namespace
+{
+	size_t align16(size_t bytes)
+	{
+		return (bytes + 15) & ~static_cast<size_t>(15);
+	}
+	/* the query staging buffers hold at least `bytes` (device and pinned host, same size); their previous contents are not kept */
+	int query_reserve(AgxEngine *e, size_t bytes)
+	{
+		if (bytes <= e->query_bytes)
+			return AGX_OK;
+		const size_t want = std::max(bytes, 2 * e->query_bytes);
+		if (e->query_dev != nullptr)
+		{
+			e->allocations.erase(std::find(e->allocations.begin(), e->allocations.end(), static_cast<void*>(e->query_dev)));
+			AGX_HIP_CHECK(hipFree(e->query_dev));
+			AGX_HIP_CHECK(hipHostFree(e->query_host));
+			e->query_dev = e->query_host = nullptr;
+			e->query_bytes = 0;
+		}
+		AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->query_dev), want));
+		e->allocations.push_back(e->query_dev);
+		AGX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e->query_host), want, hipHostMallocDefault));
+		e->query_bytes = want;
+		return AGX_OK;
+	}
+	/* the tree a query reads: the pool slot (match mode: that player's tree), game 0 of a tournament-search engine */
+	int query_tree(AgxEngine *e, int game, const char *who)
+	{
+		AGX_REQUIRE(e->begun, AGX_ERR_STATE, "%s: agx_engine_begin has not been called", who);
+		AGX_REQUIRE(game >= 0 && game < e->dev.n_games, AGX_ERR_INVALID, "%s: game %d of %d", who, game, e->dev.n_games);
+		AGX_REQUIRE(!e->dev.shared_tree || game == 0, AGX_ERR_INVALID, "%s: a tournament-search engine has one tree, game 0 (records 1.. are its task buffers)", who);
+		return AGX_OK;
+	}
+	int query_moves_on_board(const AgxEngine *e, const uint16_t *moves, int count, const char *who)
+	{
+		for (int i = 0; i < count; i++)
+		{
+			const int r = (moves[i] >> 2) & 127, c = (moves[i] >> 9) & 127;
+			AGX_REQUIRE(r < e->dev.n && c < e->dev.n, AGX_ERR_INVALID, "%s: move %d (0x%x) is at row %d, column %d of a %dx%d board", who, i, moves[i], r, c, e->dev.n,
+					e->dev.n);
+		}
+		return AGX_OK;
+	}
+}
+int agx_engine_node_info(AgxEngine *e, int game, const uint16_t *h_moves, const int *h_path_offsets, int n_paths, AgxNodeView *h_nodes, AgxEdgeView *h_edges,
+		int edges_per_path, void *stream)
+{
+	AGX_REQUIRE(e != nullptr && h_path_offsets != nullptr && h_nodes != nullptr, AGX_ERR_INVALID, "agx_engine_node_info: null argument");
+	AGX_REQUIRE(n_paths >= 0 && edges_per_path >= 0, AGX_ERR_INVALID, "agx_engine_node_info: %d paths, %d edges per path", n_paths, edges_per_path);
+	AGX_REQUIRE(edges_per_path == 0 || h_edges != nullptr, AGX_ERR_INVALID, "agx_engine_node_info: h_edges is null but edges_per_path is %d", edges_per_path);
+	int status = query_tree(e, game, "agx_engine_node_info");
+	if (status != AGX_OK)
+		return status;
+	AGX_REQUIRE(h_path_offsets[0] == 0, AGX_ERR_INVALID, "agx_engine_node_info: the first path offset is %d, not 0", h_path_offsets[0]);
+	for (int i = 0; i < n_paths; i++)
+		AGX_REQUIRE(h_path_offsets[i + 1] >= h_path_offsets[i], AGX_ERR_INVALID, "agx_engine_node_info: path %d ends (%d) before it starts (%d)", i,
+				h_path_offsets[i + 1], h_path_offsets[i]);
+	const int n_moves = h_path_offsets[n_paths];
+	AGX_REQUIRE(n_moves == 0 || h_moves != nullptr, AGX_ERR_INVALID, "agx_engine_node_info: h_moves is null");
+	if ((status = query_moves_on_board(e, h_moves, n_moves, "agx_engine_node_info")) != AGX_OK)
+		return status;
+	if (n_paths == 0)
+		return AGX_OK;
+	// staging: [offsets | moves] in, [nodes | edges] out
+	const size_t off_bytes = align16(sizeof(int) * (n_paths + 1)), move_bytes = align16(sizeof(uint16_t) * std::max(1, n_moves));
+	const size_t node_bytes = align16(sizeof(AgxNodeView) * n_paths), edge_bytes = sizeof(AgxEdgeView) * static_cast<size_t>(n_paths) * edges_per_path;
+	const size_t in_bytes = off_bytes + move_bytes;
+	hipStream_t s = static_cast<hipStream_t>(stream); // (the staging buffers are free: every query waits for its own copy back before it returns)
+	if ((status = query_reserve(e, in_bytes + node_bytes + edge_bytes)) != AGX_OK)
+		return status;
+	std::memcpy(e->query_host, h_path_offsets, sizeof(int) * (n_paths + 1));
+	if (n_moves > 0)
+		std::memcpy(e->query_host + off_bytes, h_moves, sizeof(uint16_t) * n_moves);
+	AGX_HIP_CHECK(hipMemcpyAsync(e->query_dev, e->query_host, in_bytes, hipMemcpyHostToDevice, s));
+	const int *d_offsets = reinterpret_cast<const int*>(e->query_dev);
+	const uint16_t *d_moves = reinterpret_cast<const uint16_t*>(e->query_dev + off_bytes);
+	AgxNodeView *d_nodes = reinterpret_cast<AgxNodeView*>(e->query_dev + in_bytes);
+	AgxEdgeView *d_edges = reinterpret_cast<AgxEdgeView*>(e->query_dev + in_bytes + node_bytes);
+	const int tree = e->dev.shared_tree ? 0 : game;
+	hipLaunchKernelGGL(k_node_info, dim3(n_paths), dim3(64), 0, s, e->dev, tree, d_moves, d_offsets, d_nodes, d_edges, edges_per_path);
+	AGX_HIP_CHECK(hipGetLastError());
+	AGX_HIP_CHECK(hipMemcpyAsync(e->query_host + in_bytes, e->query_dev + in_bytes, node_bytes + edge_bytes, hipMemcpyDeviceToHost, s));
+	AGX_HIP_CHECK(hipStreamSynchronize(s)); // THIS stream only
+	std::memcpy(h_nodes, e->query_host + in_bytes, sizeof(AgxNodeView) * n_paths);
+	if (edge_bytes > 0)
+		std::memcpy(h_edges, e->query_host + in_bytes + node_bytes, edge_bytes);
+	return AGX_OK;
+}
+int agx_engine_principal_variation(AgxEngine *e, int game, const uint16_t *h_moves, int n_moves, int max_length, uint16_t *h_pv, AgxEdgeView *h_pv_edges,
+		AgxNodeView *h_pv_nodes, int *length, void *stream)
+{
+	AGX_REQUIRE(e != nullptr && length != nullptr && (h_pv != nullptr || max_length == 0), AGX_ERR_INVALID, "agx_engine_principal_variation: null argument");
+	AGX_REQUIRE(n_moves >= 0 && (n_moves == 0 || h_moves != nullptr), AGX_ERR_INVALID, "agx_engine_principal_variation: %d moves", n_moves);
+	AGX_REQUIRE(max_length >= 0, AGX_ERR_INVALID, "agx_engine_principal_variation: max_length %d", max_length);
+	int status = query_tree(e, game, "agx_engine_principal_variation");
+	if (status != AGX_OK)
+		return status;
+	if ((status = query_moves_on_board(e, h_moves, n_moves, "agx_engine_principal_variation")) != AGX_OK)
+		return status;
+	const int cap = std::min(max_length, e->dev.hw); // (a variation cannot be longer than the board has cells)
+	// staging: [moves] in, [length | nodes | edges | pv] out
+	const size_t in_bytes = align16(sizeof(uint16_t) * std::max(1, n_moves)), len_bytes = 16;
+	const size_t node_bytes = align16(sizeof(AgxNodeView) * (cap + 1)), edge_bytes = align16(sizeof(AgxEdgeView) * std::max(1, cap));
+	const size_t pv_bytes = sizeof(uint16_t) * std::max(1, cap), out_bytes = len_bytes + node_bytes + edge_bytes + pv_bytes;
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	if ((status = query_reserve(e, in_bytes + out_bytes)) != AGX_OK)
+		return status;
+	if (n_moves > 0)
+		std::memcpy(e->query_host, h_moves, sizeof(uint16_t) * n_moves);
+	AGX_HIP_CHECK(hipMemcpyAsync(e->query_dev, e->query_host, in_bytes, hipMemcpyHostToDevice, s));
+	uint8_t *out_dev = e->query_dev + in_bytes, *out_host = e->query_host + in_bytes;
+	const int tree = e->dev.shared_tree ? 0 : game;
+	hipLaunchKernelGGL(k_principal_variation, dim3(1), dim3(64), 0, s, e->dev, tree, reinterpret_cast<const uint16_t*>(e->query_dev), n_moves, cap,
+			reinterpret_cast<int*>(out_dev), reinterpret_cast<uint16_t*>(out_dev + len_bytes + node_bytes + edge_bytes),
+			reinterpret_cast<AgxEdgeView*>(out_dev + len_bytes + node_bytes), reinterpret_cast<AgxNodeView*>(out_dev + len_bytes));
+	AGX_HIP_CHECK(hipGetLastError());
+	AGX_HIP_CHECK(hipMemcpyAsync(out_host, out_dev, out_bytes, hipMemcpyDeviceToHost, s));
+	AGX_HIP_CHECK(hipStreamSynchronize(s)); // THIS stream only
+	int n = 0;
+	std::memcpy(&n, out_host, sizeof(int));
+	*length = n;
+	if (n > 0)
+		std::memcpy(h_pv, out_host + len_bytes + node_bytes + edge_bytes, sizeof(uint16_t) * n);
+	if (h_pv_edges != nullptr && n > 0)
+		std::memcpy(h_pv_edges, out_host + len_bytes + node_bytes, sizeof(AgxEdgeView) * n);
+	if (h_pv_nodes != nullptr)
+		std::memcpy(h_pv_nodes, out_host + len_bytes, sizeof(AgxNodeView) * (n + 1));
 	return AGX_OK;
 }
 int agx_engine_cancel_pending(AgxEngine *e, void *stream)

@@ -8,7 +8,7 @@ import ctypes
 import numpy as np
 
 from ._lib import (lib, check, AgxEngineConfig, AgxEngineBuffers, AgxEngineStats, AgxGameInfo, AgxEdgeView, AgxMoveRecord, AgxGameEnd, AgxSavedGame,
-                   AgxRecordCounts, AgxGameBufferStats)
+                   AgxRecordCounts, AgxGameBufferStats, AgxNodeView)
 
 OPENING_CAP = 32
 
@@ -157,10 +157,14 @@ class GeneratorPool:
         """Search::generateEdges + expand + backup without the engine's own move rule (a game driven from outside: set_board)"""
         check(lib.agx_engine_expand_group(self._h, 0, 1, stream))
 
-    def set_board(self, game, board, sign_to_move, stream=None):
-        """Search::cleanup + Tree::setBoard(board, signToMove) + Search::setBoard for one game (evaluation/Player.cpp:100-110)"""
+    def set_board(self, game, board, sign_to_move, stream=None, *, force_remove_root=False):
+        """Search::cleanup + Tree::setBoard(board, signToMove, forceRemoveRootNode) + Search::setBoard for one game (evaluation/Player.cpp:100-110);
+        force_remove_root=True also drops the cached node of the position itself (the analysis engine's setPosition, SearchEngine.cpp:97-104)"""
         b = np.ascontiguousarray(board, dtype=np.uint8).reshape(-1)
-        check(lib.agx_engine_set_board(self._h, game, b.ctypes.data_as(ctypes.c_void_p), int(sign_to_move), stream))
+        if force_remove_root:
+            check(lib.agx_engine_set_board_ex(self._h, game, b.ctypes.data_as(ctypes.c_void_p), int(sign_to_move), 1, stream))
+        else:
+            check(lib.agx_engine_set_board(self._h, game, b.ctypes.data_as(ctypes.c_void_p), int(sign_to_move), stream))
 
     def cancel_pending(self, stream=None):
         """Search::cleanup: leaves selected but not expanded give their virtual losses back, every task buffer is emptied"""
@@ -300,6 +304,41 @@ class GeneratorPool:
                                  flag_vl=e.flag_and_virtual_loss) for e in edges[:info.root_edges]]
         return out
 
+    def node_info(self, game, paths, edges_per_path=None, stream=None):
+        """Tree::getInfo(moves) for every move path in `paths` (Move::toShort words from the tree's base board, colours alternating from its side
+        to move), one launch: a list of node dicts (found, visits, win, draw, moves_left, score, flags, sign_to_move, depth, virtual_loss,
+        n_edges, edges).  A path over an occupied cell or to an uncached position gives found = 0."""
+        paths = [[int(m) for m in p] for p in paths]
+        per = self.cells if edges_per_path is None else int(edges_per_path)
+        offsets = np.zeros(len(paths) + 1, np.int32)
+        offsets[1:] = np.cumsum([len(p) for p in paths])
+        moves = np.array([m for p in paths for m in p] or [0], np.uint16)
+        nodes = (AgxNodeView * max(len(paths), 1))()
+        edges = (AgxEdgeView * max(len(paths) * per, 1))()
+        check(lib.agx_engine_node_info(self._h, game, moves.ctypes.data_as(ctypes.c_void_p), offsets.ctypes.data_as(ctypes.c_void_p), len(paths),
+                                       ctypes.cast(nodes, ctypes.c_void_p), ctypes.cast(edges, ctypes.c_void_p) if per > 0 else None, per, stream))
+        out = []
+        for i in range(len(paths)):
+            d = _node_dict(nodes[i])
+            d["edges"] = [_edge_dict(e) for e in edges[i * per:i * per + min(nodes[i].n_edges, per)]]
+            out.append(d)
+        return out
+
+    def principal_variation(self, game, moves=(), max_length=None, stream=None):
+        """SearchEngine's principal variation (BestEdgeSelector from the node at the end of `moves` while it is cached and has edges), one
+        launch: dict(moves = the variation's Move::toShort words, edges = the edge chosen at each ply, nodes = the node after each ply, the
+        first one the node `moves` lead to, the last one where the walk stopped)"""
+        path = np.array([int(m) for m in moves] or [0], np.uint16)
+        cap = self.cells if max_length is None else int(max_length)
+        pv = np.zeros(max(cap, 1), np.uint16)
+        edges = (AgxEdgeView * max(cap, 1))()
+        nodes = (AgxNodeView * (cap + 1))()
+        length = ctypes.c_int()
+        check(lib.agx_engine_principal_variation(self._h, game, path.ctypes.data_as(ctypes.c_void_p), len(moves), cap, pv.ctypes.data_as(ctypes.c_void_p),
+                                                 ctypes.cast(edges, ctypes.c_void_p), ctypes.cast(nodes, ctypes.c_void_p), ctypes.byref(length), stream))
+        n = length.value
+        return dict(moves=[int(m) for m in pv[:n]], edges=[_edge_dict(e) for e in edges[:n]], nodes=[_node_dict(x) for x in nodes[:n + 1]])
+
     def records(self, drain=False):
         """(move records, their root-edge snapshots) produced so far; drain=True also empties the device-side pools"""
         nr, ne = ctypes.c_int(), ctypes.c_int()
@@ -390,6 +429,14 @@ class GeneratorPool:
         if self._h:
             lib.agx_engine_destroy(self._h)
             self._h = ctypes.c_void_p()
+
+
+def _edge_dict(e):
+    return dict(move=e.move, visits=e.visits, prior=e.prior, win=e.win, draw=e.draw, score=e.score, flag_vl=e.flag_and_virtual_loss)
+
+
+def _node_dict(v):
+    return {name: getattr(v, name) for name, _ in v._fields_}
 
 
 class GameBuffer:

@@ -394,9 +394,15 @@ int agx_stream_synchronize(void* stream);
  * Search::cleanup + Tree::setBoard(board, signToMove) + Search::setBoard (Tree.cpp:128-151: the cached states still reachable from the new
  * position are kept, the root is the cached node of the position if there is one; the solver table ages by a generation); the caller then
  * steps select_solve / evaluate / expand (agx_engine_expand_group: no move is played by the engine) until ITS stopping rule says so, reads the
- * root (agx_engine_game_info) and decides the move.  h_board: one byte per cell, 0 empty / 1 cross / 2 circle.  forceRemoveRootNode is not
- * provided.  agx_engine_set_max_simulations: the budget Search::select(tree, maxSimulations) takes per call. */
+ * root (agx_engine_game_info) and decides the move.  h_board: one byte per cell, 0 empty / 1 cross / 2 circle.  This is
+ * Tree::setBoard(board, sign, forceRemoveRootNode = false); agx_engine_set_board_ex takes the flag.  agx_engine_set_max_simulations: the
+ * budget Search::select(tree, maxSimulations) takes per call. */
 int agx_engine_set_board(AgxEngine* engine, int game, const uint8_t* h_board, int sign_to_move, void* stream);
+/* Tree::setBoard(board, sign, forceRemoveRootNode) (Tree.cpp:145-147): with force_remove_root != 0 the cached node of the new position itself
+ * is dropped while the tree is rebased (its former children stay cached), so the root is absent and the next select stage hands the position
+ * to the network afresh — what the analysis engine does on every new position (player/SearchEngine.cpp:97-104).  force_remove_root = 0 is
+ * agx_engine_set_board. */
+int agx_engine_set_board_ex(AgxEngine* engine, int game, const uint8_t* h_board, int sign_to_move, int force_remove_root, void* stream);
 int agx_engine_set_max_simulations(AgxEngine* engine, int max_simulations);
 /* Search::setBatchSize (search/monte_carlo/Search.cpp:252-255; SearchThread.cpp:125-126 grows it with sqrt(simulations)): the number of leaves the
  * select stage takes per game from the next launch on, 1 .. max_batch_size (the capacity the engine was created with) */
@@ -442,6 +448,35 @@ int agx_engine_speculative_waves(AgxEngine* engine, int* waves);
 int agx_engine_kernel_timing(AgxEngine* engine, int enable, double* ms_out, long long* launches_out);
 /* Tree::getInfo({}) of one game (Tree.cpp:403-424): root snapshot + board. */
 int agx_engine_game_info(AgxEngine* engine, int game, AgxGameInfo* info, uint8_t* h_board, AgxEdgeView* h_root_edges, int edge_capacity);
+/* Tree::getInfo(moves) for any move path (Tree.cpp:403-424) and the principal variation built on it (player/SearchEngine.cpp:219-230,243-266),
+ * read from the device tree without changing it.  A path starts at the tree's base board (the position of the last set-board or played move)
+ * and puts its moves on with alternating colours, the first one of the side to move; only the row and column of a Move::toShort are read.
+ * The position reached is sought in the tree's node cache.  An occupied cell or a position that is not cached gives found = 0 (the
+ * reference's empty Node()), not an error; a row or column outside the board is AGX_ERR_INVALID.  `game` is the pool slot (match mode: that
+ * player's tree); a tournament-search engine has one tree, game 0.  Both calls run one launch behind the work `stream` holds and wait for THAT
+ * stream only; call them between two steps of the tree. */
+typedef struct AgxNodeView
+{ /* ag::Node (Node.hpp:24-42) of the position a path leads to */
+	int found;          /* 0: occupied cell on the path, or the position is not cached (every other field 0) */
+	int visits;
+	float win, draw, moves_left;
+	int score;          /* Score raw bits */
+	int flags;          /* root 2, fully expanded 4, statically solved 8, recursively solved 16, must defend 32 */
+	int sign_to_move, depth, virtual_loss;
+	int n_edges;        /* the node's full edge count, also when fewer edges were copied */
+} AgxNodeView;
+/* n_paths paths in one launch, one wave per path: path i is h_moves[h_path_offsets[i] .. h_path_offsets[i + 1]) (n_paths + 1 offsets).
+ * h_nodes[i] receives its node, h_edges[i * edges_per_path ..] the first min(n_edges, edges_per_path) of its edges (h_edges may be NULL
+ * with edges_per_path 0). */
+int agx_engine_node_info(AgxEngine* engine, int game, const uint16_t* h_moves, const int* h_path_offsets, int n_paths,
+		AgxNodeView* h_nodes, AgxEdgeView* h_edges, int edges_per_path, void* stream);
+/* The principal variation from the end of the path h_moves[0 .. n_moves) in one launch: while the node is cached and has edges, the edge of
+ * BestEdgeSelector (EdgeSelector.cpp:515-536, the "best" final selector: first strict maximum) is taken and its child sought, for at most
+ * max_length plies.  *length receives the number of plies; h_pv[k] the move (Move::toShort) and h_pv_edges[k] the edge chosen at ply k;
+ * h_pv_nodes[k] (max_length + 1 entries) the node of the position after k plies, the last one the node the walk stopped at.  h_pv_edges and
+ * h_pv_nodes may be NULL. */
+int agx_engine_principal_variation(AgxEngine* engine, int game, const uint16_t* h_moves, int n_moves, int max_length,
+		uint16_t* h_pv, AgxEdgeView* h_pv_edges, AgxNodeView* h_pv_nodes, int* length, void* stream);
 int agx_engine_records(AgxEngine* engine, AgxMoveRecord* h_records, int record_capacity, AgxEdgeView* h_edges, int edge_capacity, int* n_records, int* n_edges);
 /* Same, then empties the device-side record pools (what GeneratorManager::addToBuffer's hand-over does, GeneratorManager.cpp:
  * 160-164): a long-running loop calls this every few hundred steps so that record_capacity is never exhausted. */

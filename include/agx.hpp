@@ -431,6 +431,39 @@ namespace agx
 					*board = b;
 				return info;
 			}
+			/* Tree::setBoard(board, signToMove, forceRemoveRootNode) for one game driven from outside (board: one byte per cell, 0 / 1 / 2) */
+			void setBoard(int game, const std::vector<uint8_t> &board, int signToMove, bool forceRemoveRootNode = false, void *stream = nullptr)
+			{
+				check(agx_engine_set_board_ex(m_engine, game, board.data(), signToMove, forceRemoveRootNode ? 1 : 0, stream));
+			}
+			/* Tree::getInfo(moves) of one game for a move path from its base board (Move::toShort words); edges (optional) receives the node's edges */
+			AgxNodeView getInfo(int game, const std::vector<uint16_t> &moves, std::vector<AgxEdgeView> *edges, void *stream = nullptr) const
+			{
+				const int offsets[2] = { 0, static_cast<int>(moves.size()) };
+				AgxNodeView view;
+				std::vector<AgxEdgeView> e(edges != nullptr ? m_buffers.cells : 0);
+				check(agx_engine_node_info(m_engine, game, moves.data(), offsets, 1, &view, edges != nullptr ? e.data() : nullptr, static_cast<int>(e.size()), stream));
+				if (edges != nullptr)
+					edges->assign(e.begin(), e.begin() + (view.found ? view.n_edges : 0));
+				return view;
+			}
+			/* the principal variation from the node the path leads to (BestEdgeSelector at every ply, SearchEngine::getSummary): its moves */
+			std::vector<uint16_t> getPrincipalVariation(int game, const std::vector<uint16_t> &moves = { }, std::vector<AgxEdgeView> *edges = nullptr,
+					std::vector<AgxNodeView> *nodes = nullptr, void *stream = nullptr) const
+			{
+				const int cap = m_buffers.cells;
+				std::vector<uint16_t> pv(cap);
+				std::vector<AgxEdgeView> e(cap);
+				std::vector<AgxNodeView> n(cap + 1);
+				int length = 0;
+				check(agx_engine_principal_variation(m_engine, game, moves.data(), static_cast<int>(moves.size()), cap, pv.data(), e.data(), n.data(), &length, stream));
+				pv.resize(length);
+				if (edges != nullptr)
+					edges->assign(e.begin(), e.begin() + length);
+				if (nodes != nullptr)
+					nodes->assign(n.begin(), n.begin() + length + 1);
+				return pv;
+			}
 			/* samples produced so far (one per played move): what GameGenerator::make_move hands to GameDataStorage */
 			void getRecords(std::vector<AgxMoveRecord> &records, std::vector<AgxEdgeView> &edges) const
 			{

@@ -556,8 +556,13 @@ namespace ag
 			bool hasAllMovesProven(int game = 0) const;
 			bool hasSingleMove(int game = 0) const;
 			bool hasSingleNonLosingMove(int game = 0) const;
-			Node getInfo(const std::vector<Move> &moves) const; // Tree::getInfo({}) (Tree.cpp:403-424): an owning copy of the root
+			/* Tree::getInfo(moves) (Tree.cpp:403-424): an owning copy of the node the moves lead to from the base board (colours alternating from
+			 * the side to move), the root for an empty list; an occupied cell or an uncached position gives an empty Node() */
+			Node getInfo(const std::vector<Move> &moves) const;
 			Node getInfo(int game, const std::vector<Move> &moves = { }) const;
+			/* SearchEngine's principal variation (SearchEngine.cpp:243-266: getInfo + BestEdgeSelector until a leaf) from the node the moves lead
+			 * to, as one device launch: the variation's moves */
+			std::vector<Move> getPrincipalVariation(const std::vector<Move> &moves = { }, int game = 0) const;
 			void clearNodeCacheStats() noexcept; // Tree.cpp:425-428: the device keeps peaks per game since agx_engine_begin; this forgets what was reported so far
 			NodeCacheStats getNodeCacheStats() const noexcept;
 			/* Tree.hpp:102-103: guards for HOST threads sharing the Tree object (player/SearchThread.cpp:94,107,126,137,155) */
