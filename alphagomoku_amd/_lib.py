@@ -16,6 +16,42 @@ class AgxNetDesc(ctypes.Structure):
                 ("action_values", ctypes.c_int)]
 
 
+_shared_torch_runtime = None   # path of torch's own HIP runtime once share_torch_hip_runtime() has put it in front of the system's
+
+
+def share_torch_hip_runtime():
+    """PyTorch-ROCm wheels bundle a HIP runtime of their own (torch/lib/libamdhip64.so, no soname), libagx.so is linked against the
+    system's; two HIP runtimes in one process do not both get the GPU.  Called BEFORE libagx.so is first used, this loads torch's runtime
+    with global symbol scope, so that the library's HIP calls and its kernels' registration bind to the runtime torch uses: torch tensors,
+    torch streams and the library's launches then share one runtime.  Returns the runtime's path, or None when torch carries none (a
+    torch built against the system ROCm shares the runtime anyway).  Raises when the library is already loaded."""
+    global _shared_torch_runtime
+    if _shared_torch_runtime is not None:
+        return _shared_torch_runtime
+    import importlib.util
+    spec = importlib.util.find_spec("torch")
+    if spec is None or not spec.submodule_search_locations:
+        return None
+    path = os.path.join(list(spec.submodule_search_locations)[0], "lib", "libamdhip64.so")
+    if not os.path.exists(path):
+        return None
+    if _Lazy._cdll is not None:
+        raise AgxError("share_torch_hip_runtime() must be called before libagx.so is first used in this process")
+    ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
+    _shared_torch_runtime = path
+    return path
+
+
+def torch_shares_hip_runtime():
+    """True when torch tensors and the library's launches live in one HIP runtime in this process"""
+    import importlib.util
+    spec = importlib.util.find_spec("torch")
+    if spec is None or not spec.submodule_search_locations:
+        return False
+    bundled = os.path.join(list(spec.submodule_search_locations)[0], "lib", "libamdhip64.so")
+    return _shared_torch_runtime is not None or not os.path.exists(bundled)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise AgxError(
@@ -243,3 +279,35 @@ def _declare(c):  # noqa: F811
     c.agx_host_tables.argtypes = [ci, vp, vp, vp, vp]
     c.agx_make_opening.argtypes = [ci, ci, ctypes.c_uint32, vp]
     c.agx_get_outcome.argtypes = [ci, ci, vp, ci, ci, ci, ci, vp]
+
+
+class AgxDatasetSample(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ["fragment", "game", "sample", "augmentation"]]
+
+
+class AgxTensorShape(ctypes.Structure):
+    _fields_ = [("rank", ctypes.c_int), ("dim", ctypes.c_int * 4)]
+
+
+BATCH_INPUT_FP16, BATCH_POLICY_VISITS = 1, 2
+
+_declare_engine = _declare
+
+
+def _declare(c):  # noqa: F811
+    _declare_engine(c)
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    shape = ctypes.POINTER(AgxTensorShape)
+    c.agx_game_buffer_config.argtypes = [vp] + [ctypes.POINTER(ci)] * 4
+    c.agx_game_buffer_file_config.argtypes = [ctypes.c_char_p] + [ctypes.POINTER(ci)] * 3
+    c.agx_dataset_create.argtypes = [ci, ci, ci, ctypes.POINTER(vp)]
+    c.agx_dataset_destroy.argtypes = [vp]
+    c.agx_dataset_add_fragment_file.argtypes = [vp, ci, ctypes.c_char_p]
+    c.agx_dataset_add_fragment_buffer.argtypes = [vp, ci, vp]
+    c.agx_dataset_unload_fragment.argtypes = [vp, ci]
+    c.agx_dataset_games.argtypes = [vp, ctypes.POINTER(ci)]
+    c.agx_dataset_sizes.argtypes = [vp, vp, ci]
+    c.agx_dataset_stats.argtypes = [vp, ctypes.POINTER(AgxGameBufferStats)]
+    c.agx_dataset_tensor_shapes.argtypes = [vp, ci] + [shape] * 6
+    c.agx_dataset_load_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+    c.agx_dataset_load_batch_host.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, ci]

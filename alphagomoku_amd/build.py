@@ -12,13 +12,15 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libagx.so")
 
 INCLUDE = os.path.join(HERE, "..", "include")
-SOURCES = ["agx_api.hip", "nn_forward.hip", "engine.hip", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
+SOURCES = ["agx_api.hip", "nn_forward.hip", "engine.hip", "training_batch.hip", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
 DRIVER = os.path.join(HERE, "agx_selfplay")
 AG_LIB = os.path.join(HERE, "libagx_ag.so")               # the reference-named C++ classes (include/alphagomoku_agx/) over the C ABI
 BOUNDARY_TEST = os.path.join(HERE, "agx_boundary_test")  # tests/cpp/boundary_main.cpp: the reference's call chain on those classes
 
 
 BOUNDARY_SRC = os.path.join(HERE, "..", "tests", "cpp", "boundary_main.cpp")
+TRAINING_TEST = os.path.join(HERE, "agx_training_batch_test")  # tests/cpp/training_batch_main.cpp: the reference's dataset entry points (dataset.hpp)
+TRAINING_SRC = os.path.join(HERE, "..", "tests", "cpp", "training_batch_main.cpp")
 HOST_ONLY = ("ag_classes.cpp", "selfplay_main.cpp")  # plain g++ sources in csrc/ (not part of libagx.so)
 
 
@@ -80,6 +82,8 @@ def _stale_host_targets():
         out.append(AG_LIB)
     if _mtime(BOUNDARY_TEST) < max(_mtime(BOUNDARY_SRC), headers, _mtime(AG_LIB)) or AG_LIB in out:
         out.append(BOUNDARY_TEST)
+    if _mtime(TRAINING_TEST) < max(_mtime(TRAINING_SRC), headers, _mtime(AG_LIB)) or AG_LIB in out:
+        out.append(TRAINING_TEST)
     return out
 
 
@@ -144,7 +148,7 @@ def build(force=False, verbose=True):
         relink = True
     if relink:
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + [BUILD_ID_OBJ, "-lz"])
-    stale = [DRIVER, AG_LIB, BOUNDARY_TEST] if force else _stale_host_targets()
+    stale = [DRIVER, AG_LIB, BOUNDARY_TEST, TRAINING_TEST] if force else _stale_host_targets()
     if DRIVER in stale:  # native C++ host driver over the C ABI (include/agx.hpp)
         run([cxx, "-std=c++17", "-O2", "-o", DRIVER, os.path.join(CSRC, "selfplay_main.cpp"), "-L" + HERE, "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     if AG_LIB in stale:  # the C++ boundary: plain host code (g++), no HIP types — a maintainer of the reference links it like any other library
@@ -152,6 +156,8 @@ def build(force=False, verbose=True):
              "-Wl,-rpath," + HERE, "-lpthread"])
     if BOUNDARY_TEST in stale:
         run([cxx, "-std=c++17", "-O2", "-Wall", "-o", BOUNDARY_TEST, BOUNDARY_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
+    if TRAINING_TEST in stale:
+        run([cxx, "-std=c++17", "-O2", "-Wall", "-o", TRAINING_TEST, TRAINING_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     return LIB
 
 

@@ -5,6 +5,7 @@
  * (invalid argument / state) or std::runtime_error (device failure), the exceptions the reference throws (NNEvaluator.cpp:149,185-187).
  */
 #include "../../include/alphagomoku_agx/selfplay.hpp"
+#include "../../include/alphagomoku_agx/dataset.hpp"
 #include "symmetry.hpp"
 
 #include <algorithm>
@@ -2178,6 +2179,127 @@ namespace ag
 				generators[i]->loadGames(file);
 				std::cout << "Loaded " << file << std::endl;
 			}
+		}
+	}
+	/* ---------------- dataset/torch_api.h on the device reader (agx.h: agx_dataset_*) ---------------- */
+	namespace
+	{
+		struct ProcessDataset
+		{ // torch_api.cpp:26-30: one Dataset per process
+				std::mutex mutex;
+				AgxDataset *handle = nullptr;
+				int fragments = 0;
+				~ProcessDataset()
+				{
+					agx_dataset_destroy(handle);
+				}
+		};
+		ProcessDataset& process_dataset()
+		{
+			static ProcessDataset d;
+			return d;
+		}
+		void dataset_check(int status)
+		{
+			if (status == AGX_OK)
+				return;
+			const std::string msg = agx_last_error();
+			if (status == AGX_ERR_INVALID || status == AGX_ERR_STATE)
+				throw std::logic_error(msg);
+			throw std::runtime_error(msg);
+		}
+		AgxDataset* loaded_dataset()
+		{
+			AgxDataset *h = process_dataset().handle;
+			if (h == nullptr)
+				throw std::logic_error("no dataset fragment is loaded");
+			return h;
+		}
+		void to_tensor_size(TensorSize_t *dst, const AgxTensorShape &src)
+		{
+			if (dst == nullptr)
+				return;
+			dst->rank = src.rank;
+			for (int i = 0; i < 4; i++)
+				dst->dim[i] = src.dim[i];
+		}
+		static_assert(sizeof(Sample_t) == sizeof(AgxDatasetSample), "Sample_t and AgxDatasetSample are the same four ints");
+	}
+	extern "C"
+	{
+		void load_dataset_fragment(int i, const char *path)
+		{
+			ProcessDataset &d = process_dataset();
+			std::lock_guard<std::mutex> lock(d.mutex);
+			if (d.fragments == 0)
+			{ // the dataset takes the game configuration of its first fragment
+				int rules = 0, rows = 0, cols = 0;
+				dataset_check(agx_game_buffer_file_config(path, &rules, &rows, &cols));
+				agx_dataset_destroy(d.handle);
+				d.handle = nullptr;
+				dataset_check(agx_dataset_create(rules, rows, cols, &d.handle));
+			}
+			dataset_check(agx_dataset_add_fragment_file(d.handle, i, path));
+			d.fragments++;
+		}
+		void unload_dataset_fragment(int i)
+		{
+			ProcessDataset &d = process_dataset();
+			std::lock_guard<std::mutex> lock(d.mutex);
+			dataset_check(agx_dataset_unload_fragment(loaded_dataset(), i));
+			d.fragments--;
+		}
+		void print_dataset_info()
+		{
+			AgxGameBufferStats s;
+			dataset_check(agx_dataset_stats(loaded_dataset(), &s));
+			GameDataBufferStats out;
+			out.games = s.games;
+			out.samples = s.samples;
+			out.cross_win = s.cross_win;
+			out.draws = s.draws;
+			out.circle_win = s.circle_win;
+			out.game_length = s.game_length;
+			std::cout << out.toString() << '\n';
+		}
+		void get_dataset_size(TensorSize_t *shape, int *size)
+		{
+			int games = 0;
+			dataset_check(agx_dataset_games(loaded_dataset(), &games));
+			if (shape != nullptr)
+			{
+				shape->rank = 2;
+				shape->dim[0] = games;
+				shape->dim[1] = 4;
+				shape->dim[2] = shape->dim[3] = 0;
+				return;
+			}
+			if (size != nullptr && games > 0)
+				dataset_check(agx_dataset_sizes(loaded_dataset(), size, games));
+		}
+		void get_tensor_shapes(int batch_size, const Sample_t *samples, TensorSize_t *input, TensorSize_t *policy_target, TensorSize_t *value_target,
+				TensorSize_t *moves_left_target, TensorSize_t *action_values_target)
+		{
+			(void) samples; // one game configuration per dataset: nothing to compare
+			if (batch_size <= 0)
+				return;
+			AgxTensorShape in, pol, val, ml, av;
+			dataset_check(agx_dataset_tensor_shapes(loaded_dataset(), batch_size, &in, nullptr, &pol, &val, &ml, &av));
+			pol.rank = 4; // the reference's policy target is [batch, rows, cols, 1]: the same memory
+			pol.dim[3] = 1;
+			to_tensor_size(input, in);
+			to_tensor_size(policy_target, pol);
+			to_tensor_size(value_target, val);
+			to_tensor_size(moves_left_target, ml);
+			to_tensor_size(action_values_target, av);
+		}
+		void load_batch(int batch_size, const Sample_t *samples, float *input, float *policy_target, float *value_target, float *moves_left_target,
+				float *action_values_target)
+		{
+			if (batch_size <= 0)
+				return;
+			dataset_check(agx_dataset_load_batch_host(loaded_dataset(), batch_size, reinterpret_cast<const AgxDatasetSample*>(samples), input, nullptr, policy_target,
+					value_target, moves_left_target, action_values_target, 0));
 		}
 	}
 } /* namespace ag */

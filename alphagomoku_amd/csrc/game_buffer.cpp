@@ -66,6 +66,64 @@ struct AgxGameBuffer
 		std::map<const void*, std::map<std::pair<int, int>, PendingGame>> pending;
 };
 
+namespace
+{
+	/* the content of a file written by agx_game_buffer_save, inflated when it is a zlib stream */
+	int read_buffer_file(const char *who, const char *path, std::vector<char> &raw)
+	{
+		std::ifstream stream(path, std::ifstream::in | std::ifstream::binary);
+		AGX_REQUIRE(stream.good(), AGX_ERR_STATE, "%s: cannot open '%s'", who, path);
+		raw.assign((std::istreambuf_iterator<char>(stream)), std::istreambuf_iterator<char>());
+		AGX_REQUIRE(!raw.empty(), AGX_ERR_INVALID, "%s: '%s' is empty", who, path);
+		if (raw[0] != '{')
+		{ // a zlib stream: inflate into a growing buffer
+			std::vector<char> plain(std::max<size_t>(raw.size() * 4, 1 << 16));
+			while (true)
+			{
+				uLongf size = static_cast<uLongf>(plain.size());
+				const int z = uncompress(reinterpret_cast<Bytef*>(plain.data()), &size, reinterpret_cast<const Bytef*>(raw.data()), static_cast<uLong>(raw.size()));
+				if (z == Z_BUF_ERROR)
+				{
+					plain.resize(plain.size() * 2);
+					continue;
+				}
+				AGX_REQUIRE(z == Z_OK, AGX_ERR_INVALID, "%s: '%s' is neither a JSON header nor a zlib stream (zlib %d)", who, path, z);
+				plain.resize(size);
+				break;
+			}
+			raw.swap(plain);
+		}
+		return AGX_OK;
+	}
+	/* the header line of such a file: {"format": 201, "config": {"rules": "...", "rows": R, "cols": C, ...}, "offsets": [...]} */
+	struct FileHeader
+	{
+			std::string line;
+			int rules = -1; // index of the rules' name, -1: none of the five
+			long long rows = 0, cols = 0;
+			size_t blob_begin = 0; // first byte behind the header's newline
+	};
+	int read_buffer_header(const char *who, const char *path, std::vector<char> &raw, FileHeader &h)
+	{
+		const int read_status = read_buffer_file(who, path, raw);
+		if (read_status != AGX_OK)
+			return read_status;
+		const auto newline = std::find(raw.begin(), raw.end(), '\n');
+		AGX_REQUIRE(newline != raw.end(), AGX_ERR_INVALID, "%s: '%s' has no header line", who, path);
+		h.line.assign(raw.begin(), newline);
+		h.blob_begin = static_cast<size_t>(newline - raw.begin()) + 1;
+		AGX_REQUIRE(h.line.find("\"format\": 201") != std::string::npos, AGX_ERR_UNSUPPORTED, "%s: only dataset format 201 is read", who);
+		for (int r = 0; r <= AGX_CARO6; r++)
+			if (h.line.find(std::string("\"rules\": \"") + rules_name(r) + "\"") != std::string::npos)
+				h.rules = r;
+		const size_t at_rows = h.line.find("\"rows\": "), at_cols = h.line.find("\"cols\": ");
+		AGX_REQUIRE(at_rows != std::string::npos && at_cols != std::string::npos, AGX_ERR_INVALID, "%s: '%s' names no board size in its header", who, path);
+		h.rows = std::atoll(h.line.c_str() + at_rows + 8);
+		h.cols = std::atoll(h.line.c_str() + at_cols + 8);
+		return AGX_OK;
+	}
+}
+
 extern "C" {
 
 int agx_game_buffer_create(int rules, int rows, int cols, int draw_after, AgxGameBuffer **out)
@@ -196,6 +254,20 @@ int agx_game_buffer_stats(const AgxGameBuffer *b, AgxGameBufferStats *out)
 	return AGX_OK;
 }
 
+int agx_game_buffer_config(const AgxGameBuffer *b, int *rules, int *rows, int *cols, int *draw_after)
+{
+	AGX_REQUIRE(b != nullptr, AGX_ERR_INVALID, "agx_game_buffer_config: null buffer");
+	if (rules != nullptr)
+		*rules = b->rules;
+	if (rows != nullptr)
+		*rows = b->rows;
+	if (cols != nullptr)
+		*cols = b->cols;
+	if (draw_after != nullptr)
+		*draw_after = b->draw_after;
+	return AGX_OK;
+}
+
 int agx_game_buffer_game(const AgxGameBuffer *b, int index, uint8_t *h_bytes, size_t capacity, size_t *size)
 {
 	AGX_REQUIRE(b != nullptr && size != nullptr, AGX_ERR_INVALID, "agx_game_buffer_game: null argument");
@@ -249,45 +321,15 @@ int agx_game_buffer_save(const AgxGameBuffer *b, const char *path, int compress)
 int agx_game_buffer_load(AgxGameBuffer *b, const char *path)
 {
 	AGX_REQUIRE(b != nullptr && path != nullptr, AGX_ERR_INVALID, "agx_game_buffer_load: null argument");
-	std::ifstream stream(path, std::ifstream::in | std::ifstream::binary);
-	AGX_REQUIRE(stream.good(), AGX_ERR_STATE, "agx_game_buffer_load: cannot open '%s'", path);
-	std::vector<char> raw((std::istreambuf_iterator<char>(stream)), std::istreambuf_iterator<char>());
-	AGX_REQUIRE(!raw.empty(), AGX_ERR_INVALID, "agx_game_buffer_load: '%s' is empty", path);
-	if (raw[0] != '{')
-	{ // a zlib stream: inflate into a growing buffer
-		std::vector<char> plain(std::max<size_t>(raw.size() * 4, 1 << 16));
-		while (true)
-		{
-			uLongf size = static_cast<uLongf>(plain.size());
-			const int z = uncompress(reinterpret_cast<Bytef*>(plain.data()), &size, reinterpret_cast<const Bytef*>(raw.data()), static_cast<uLong>(raw.size()));
-			if (z == Z_BUF_ERROR)
-			{
-				plain.resize(plain.size() * 2);
-				continue;
-			}
-			AGX_REQUIRE(z == Z_OK, AGX_ERR_INVALID, "agx_game_buffer_load: '%s' is neither a JSON header nor a zlib stream (zlib %d)", path, z);
-			plain.resize(size);
-			break;
-		}
-		raw.swap(plain);
-	}
-	const auto newline = std::find(raw.begin(), raw.end(), '\n');
-	AGX_REQUIRE(newline != raw.end(), AGX_ERR_INVALID, "agx_game_buffer_load: '%s' has no header line", path);
-	const std::string header(raw.begin(), newline);
-	AGX_REQUIRE(header.find("\"format\": 201") != std::string::npos, AGX_ERR_UNSUPPORTED, "agx_game_buffer_load: only dataset format 201 is read");
-	auto number_after = [&](const std::string &key, long long &out)
-	{
-		const size_t at = header.find(key);
-		if (at == std::string::npos)
-			return false;
-		out = std::atoll(header.c_str() + at + key.size());
-		return true;
-	};
-	long long rows = 0, cols = 0;
-	AGX_REQUIRE(number_after("\"rows\": ", rows) && number_after("\"cols\": ", cols) && rows == b->rows && cols == b->cols, AGX_ERR_INVALID,
-			"agx_game_buffer_load: '%s' holds %lldx%lld games, the buffer %dx%d", path, rows, cols, b->rows, b->cols);
-	AGX_REQUIRE(header.find(std::string("\"rules\": \"") + rules_name(b->rules) + "\"") != std::string::npos, AGX_ERR_INVALID,
-			"agx_game_buffer_load: '%s' was saved for other rules than %s", path, rules_name(b->rules));
+	std::vector<char> raw;
+	FileHeader fh;
+	const int read_status = read_buffer_header("agx_game_buffer_load", path, raw, fh);
+	if (read_status != AGX_OK)
+		return read_status;
+	const std::string &header = fh.line;
+	AGX_REQUIRE(fh.rows == b->rows && fh.cols == b->cols, AGX_ERR_INVALID, "agx_game_buffer_load: '%s' holds %lldx%lld games, the buffer %dx%d", path, fh.rows, fh.cols,
+			b->rows, b->cols);
+	AGX_REQUIRE(fh.rules == b->rules, AGX_ERR_INVALID, "agx_game_buffer_load: '%s' was saved for other rules than %s", path, rules_name(b->rules));
 	std::vector<size_t> offsets;
 	{
 		const size_t at = header.find("\"offsets\": [");
@@ -305,8 +347,8 @@ int agx_game_buffer_load(AgxGameBuffer *b, const char *path)
 				p++;
 		}
 	}
-	const uint8_t *blob = reinterpret_cast<const uint8_t*>(&*newline) + 1;
-	const size_t blob_size = static_cast<size_t>(raw.end() - newline) - 1;
+	const uint8_t *blob = reinterpret_cast<const uint8_t*>(raw.data()) + fh.blob_begin;
+	const size_t blob_size = raw.size() - fh.blob_begin;
 	std::vector<std::vector<uint8_t>> games;
 	std::vector<int> outcomes, lengths, samples;
 	for (size_t i = 0; i < offsets.size(); i++)
@@ -347,6 +389,22 @@ int agx_game_buffer_load(AgxGameBuffer *b, const char *path)
 		b->lengths.push_back(lengths[i]);
 		b->samples.push_back(samples[i]);
 	}
+	return AGX_OK;
+}
+
+/* GameConfig of a file written by agx_game_buffer_save (its header line): what a reader needs before it can create a buffer for the file */
+int agx_game_buffer_file_config(const char *path, int *rules, int *rows, int *cols)
+{
+	AGX_REQUIRE(path != nullptr && rules != nullptr && rows != nullptr && cols != nullptr, AGX_ERR_INVALID, "agx_game_buffer_file_config: null argument");
+	std::vector<char> raw;
+	FileHeader fh;
+	const int read_status = read_buffer_header("agx_game_buffer_file_config", path, raw, fh);
+	if (read_status != AGX_OK)
+		return read_status;
+	AGX_REQUIRE(fh.rules >= 0, AGX_ERR_INVALID, "agx_game_buffer_file_config: '%s' names none of the five rule sets in its header", path);
+	*rules = fh.rules;
+	*rows = static_cast<int>(fh.rows);
+	*cols = static_cast<int>(fh.cols);
 	return AGX_OK;
 }
 

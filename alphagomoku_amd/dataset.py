@@ -1,0 +1,181 @@
+"""Training batches from self-play games: format-201 fragments -> torch tensors on the ROCm device.
+
+TrainingDataset binds the agx_dataset_* calls of include/agx.h (csrc/training_batch.hip: one wavefront per sample, a batch per launch).
+It is what the reference's dataset reader for PyTorch (include/alphagomoku/dataset/torch_api.h, src/dataset/torch_api.cpp) does on one
+host thread: load_dataset_fragment / get_dataset_size / load_batch, plus BaseSampler::pick_sample's sampling scheme.  torch only
+allocates the tensors and names the stream; the kernel writes through data_ptr().  A PyTorch-ROCm wheel that bundles its own HIP runtime
+has to share it with the library first: see _lib.share_torch_hip_runtime().
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from ._lib import lib, check, AgxError, AgxDatasetSample, AgxGameBufferStats, AgxTensorShape, BATCH_INPUT_FP16, BATCH_POLICY_VISITS
+
+SYMMETRIES = 8   # number_of_available_symmetries of a square board
+
+
+class TrainingDataset:
+    """Numbered fragments of self-play games of one game configuration (Dataset, src/dataset/Dataset.cpp).  Loading and indexing are
+    host work; a fragment's bytes go to the device at the first load_batch that uses it."""
+
+    def __init__(self, rules, rows, cols):
+        self.rules, self.rows, self.cols = rules, rows, cols
+        self._h = ctypes.c_void_p()
+        check(lib.agx_dataset_create(rules, rows, cols, ctypes.byref(self._h)))
+        self._next_fragment = 0
+        self._order, self._cursor = None, 0   # the sampler's shuffled list of games
+
+    def add_fragment(self, source, index=None):
+        """source: the path of a file written by GameBuffer.save (compressed or not), or a live GameBuffer (its finished games are
+        copied).  Returns the fragment's number."""
+        index = self._next_fragment if index is None else index
+        if hasattr(source, "_h"):
+            check(lib.agx_dataset_add_fragment_buffer(self._h, index, source._h))
+        else:
+            check(lib.agx_dataset_add_fragment_file(self._h, index, str(source).encode()))
+        self._next_fragment = max(self._next_fragment, index + 1)
+        self._order = None
+        return index
+
+    def unload_fragment(self, index):
+        check(lib.agx_dataset_unload_fragment(self._h, index))
+        self._order = None
+
+    def number_of_games(self):
+        n = ctypes.c_int()
+        check(lib.agx_dataset_games(self._h, ctypes.byref(n)))
+        return n.value
+
+    def games(self):
+        """get_dataset_size: int32 [games, 4] = (fragment, game, samples, symmetries)"""
+        out = np.zeros((self.number_of_games(), 4), np.int32)
+        if out.size:
+            check(lib.agx_dataset_sizes(self._h, out.ctypes.data_as(ctypes.c_void_p), out.shape[0]))
+        return out
+
+    def stats(self):
+        s = AgxGameBufferStats()
+        check(lib.agx_dataset_stats(self._h, ctypes.byref(s)))
+        return {name: getattr(s, name) for name, _ in s._fields_}
+
+    def tensor_shapes(self, batch_size):
+        """get_tensor_shapes, plus the packed feature words"""
+        shapes = [AgxTensorShape() for _ in range(6)]
+        check(lib.agx_dataset_tensor_shapes(self._h, batch_size, *[ctypes.byref(s) for s in shapes]))
+        names = ["input", "features", "policy_target", "value_target", "moves_left_target", "action_values_target"]
+        return {k: tuple(s.dim[:s.rank]) for k, s in zip(names, shapes)}
+
+    @staticmethod
+    def _records(samples):
+        a = np.ascontiguousarray(np.asarray(samples, dtype=np.int32).reshape(-1, 4))
+        assert ctypes.sizeof(AgxDatasetSample) == 16
+        return a
+
+    def load_batch(self, samples, *, dtype=None, out=None, features=True, policy="torch_api"):
+        """samples: [n, 4] (fragment, game, sample, augmentation).  Returns a dict of torch tensors on the current ROCm device:
+        input [n, rows, cols, 32] (dtype torch.float32 or torch.float16), features [n, rows * cols] (the uint32 feature words agx_nn_forward
+        takes, as int32), policy_target [n, rows, cols], value_target [n, 3], moves_left_target [n, 1], action_values_target
+        [n, rows, cols, 3].  The launch is enqueued on torch.cuda.current_stream(); nothing is synchronised.  features=False leaves the
+        feature words out.  out: a dict of tensors to write into, e.g. from an earlier call of the same batch size: it must hold the four
+        targets, and exactly what it holds of "input" and "features" is written (dtype and features are then taken from it).
+        policy: "torch_api" (proven draw: max(1, visits)) or "visits" (SamplerVisits).  The dataset lives on the device of its first
+        batch; a call with another device current is refused."""
+        if not _lib.torch_shares_hip_runtime():
+            raise AgxError("this torch carries a HIP runtime of its own: call alphagomoku_amd._lib.share_torch_hip_runtime() before the library is first "
+                           "used in this process, or use load_batch_pointers / load_batch_host")
+        import torch
+        rec = self._records(samples)
+        n = rec.shape[0]
+        if out is not None and "input" in out:
+            if dtype is not None and dtype != out["input"].dtype:
+                raise ValueError("dtype %s does not match out['input'] (%s)" % (dtype, out["input"].dtype))
+            dtype = out["input"].dtype
+        dtype = dtype or torch.float32
+        if dtype not in (torch.float32, torch.float16):
+            raise ValueError("input dtype must be torch.float32 or torch.float16")
+        if policy not in ("torch_api", "visits"):
+            raise ValueError("policy must be 'torch_api' or 'visits'")
+        shapes = self.tensor_shapes(n)
+        if out is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in shapes if k not in ("input", "features")}
+            out["input"] = torch.empty(shapes["input"], dtype=dtype, device=dev)
+            if features:
+                out["features"] = torch.empty(shapes["features"], dtype=torch.int32, device=dev)
+        else:
+            missing = [k for k in ("policy_target", "value_target", "moves_left_target", "action_values_target") if k not in out]
+            if missing or any(k not in shapes for k in out):
+                raise ValueError("out must hold the four targets and at most 'input' and 'features' besides (missing %s)" % missing)
+            for k, t in out.items():
+                want = dtype if k == "input" else (torch.int32 if k == "features" else torch.float32)
+                if tuple(t.shape) != shapes[k] or t.dtype != want or not t.is_contiguous() or not t.is_cuda:
+                    raise ValueError("out[%r] must be a contiguous %s device tensor of shape %s" % (k, want, shapes[k]))
+        flags = (BATCH_INPUT_FP16 if dtype == torch.float16 else 0) | (BATCH_POLICY_VISITS if policy == "visits" else 0)
+        ptr = lambda k: ctypes.c_void_p(out[k].data_ptr()) if k in out else None  # noqa: E731
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(lib.agx_dataset_load_batch(self._h, n, rec.ctypes.data_as(ctypes.c_void_p), ptr("input"), ptr("features"), ptr("policy_target"),
+                                         ptr("value_target"), ptr("moves_left_target"), ptr("action_values_target"), flags, stream))
+        return out
+
+    def load_batch_pointers(self, samples, pointers, *, half=False, policy="torch_api", stream=None):
+        """agx_dataset_load_batch on raw device addresses: pointers maps the output names of tensor_shapes() to integers ("input" and
+        "features" may be missing), stream is a hipStream_t as an integer / c_void_p or None"""
+        rec = self._records(samples)
+        flags = (BATCH_INPUT_FP16 if half else 0) | (BATCH_POLICY_VISITS if policy == "visits" else 0)
+        ptr = lambda k: ctypes.c_void_p(pointers[k]) if pointers.get(k) else None  # noqa: E731
+        check(lib.agx_dataset_load_batch(self._h, rec.shape[0], rec.ctypes.data_as(ctypes.c_void_p), ptr("input"), ptr("features"), ptr("policy_target"),
+                                         ptr("value_target"), ptr("moves_left_target"), ptr("action_values_target"), flags, stream))
+
+    def load_batch_host(self, samples, *, half=False, features=True, policy="torch_api"):
+        """the same through the C ABI's host-pointer form (what ag::load_batch forwards to): numpy arrays, no torch"""
+        rec = self._records(samples)
+        n = rec.shape[0]
+        shapes = self.tensor_shapes(n)
+        out = {k: np.zeros(shapes[k], np.float32) for k in shapes if k not in ("input", "features")}
+        out["input"] = np.zeros(shapes["input"], np.float16 if half else np.float32)
+        if features:
+            out["features"] = np.zeros(shapes["features"], np.uint32)
+        flags = (BATCH_INPUT_FP16 if half else 0) | (BATCH_POLICY_VISITS if policy == "visits" else 0)
+        ptr = lambda k: out[k].ctypes.data_as(ctypes.c_void_p) if k in out else None  # noqa: E731
+        check(lib.agx_dataset_load_batch_host(self._h, n, rec.ctypes.data_as(ctypes.c_void_p), ptr("input"), ptr("features"), ptr("policy_target"),
+                                              ptr("value_target"), ptr("moves_left_target"), ptr("action_values_target"), flags))
+        return out
+
+    def sample(self, batch_size, generator):
+        """BaseSampler::pick_sample (torch_api.cpp:46-77) batch_size times: the games in a shuffled order, of every game one random
+        sample under one random symmetry; when every game has been visited the order is shuffled again.  generator: a
+        numpy.random.Generator — the same seed gives the same sequence.  The reference draws from std::random_shuffle and its own
+        randInt, whose sequences are not reproduced: only the scheme is.  Returns int32 [batch_size, 4]."""
+        games = self.games()
+        games = games[games[:, 2] > 0]   # (a fragment with a game without samples is refused when it is loaded)
+        if games.shape[0] == 0:
+            raise ValueError("the dataset holds no games")
+        out = np.zeros((batch_size, 4), np.int32)
+        for b in range(batch_size):
+            if self._order is None or self._order.shape[0] != games.shape[0]:
+                self._order, self._cursor = generator.permutation(games.shape[0]), 0
+            fragment, game, samples, symmetries = games[self._order[self._cursor]]
+            out[b] = (fragment, game, generator.integers(0, samples), generator.integers(0, symmetries))
+            self._cursor += 1
+            if self._cursor >= games.shape[0]:
+                self._order, self._cursor = generator.permutation(games.shape[0]), 0
+        return out
+
+    def close(self):
+        if self._h:
+            lib.agx_dataset_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown: the library may be gone already
+            pass

@@ -542,6 +542,8 @@ int agx_game_buffer_save(const AgxGameBuffer* buffer, const char* path, int comp
 /* GameDataBuffer::load (dataset/GameDataBuffer.cpp:115-131; called by GeneratorManager::loadState, GeneratorManager.cpp:263-275) for files written
  * by agx_game_buffer_save, compressed or not: the games are appended to the buffer */
 int agx_game_buffer_load(AgxGameBuffer* buffer, const char* path);
+/* the game configuration in the header of such a file */
+int agx_game_buffer_file_config(const char* path, int* rules, int* rows, int* cols);
 /* Checkpoints of games in flight (GameGenerator::save / load, selfplay/GameGenerator.cpp:122-141): the format-201 samples a game has collected
  * so far wait in the buffer, keyed by (engine, game_slot, game_index), until its AgxGameEnd arrives.  take_pending serialises and removes
  * them ({ i32 move number, u32 bytes, sample } records; h_bytes NULL: size only, nothing removed); restore_pending hands them to the game that
@@ -550,11 +552,79 @@ int agx_game_buffer_load(AgxGameBuffer* buffer, const char* path);
 int agx_game_buffer_take_pending(AgxGameBuffer* buffer, const AgxEngine* engine, int game_slot, int game_index, uint8_t* h_bytes, size_t capacity, size_t* size);
 int agx_game_buffer_restore_pending(AgxGameBuffer* buffer, const AgxEngine* engine, int game_slot, int game_index, const uint8_t* h_bytes, size_t size);
 int agx_game_buffer_forget_engine(AgxGameBuffer* buffer, const AgxEngine* engine);
+/* the game configuration the buffer was created for; any output may be NULL */
+int agx_game_buffer_config(const AgxGameBuffer* buffer, int* rules, int* rows, int* cols, int* draw_after);
 /* Host-only reader of one format-201 sample (SearchDataStorage_v201's parsing constructor + storeTo, dataset/SearchDataStorage.cpp:
  * 300-320,375-409): per cell visits int32[rows*cols], prior float[rows*cols], value float[rows*cols][2] = (win, draw), score
  * uint16[rows*cols]; header int[3] = (minimax score raw bits, move number, flags); minimax_value float[2].  consumed may be NULL. */
 int agx_sample_v201_unpack(const uint8_t* h_bytes, size_t size, int rows, int cols, int32_t* visits, float* prior, float* value, uint16_t* score,
 		int* header, float* minimax_value, size_t* consumed);
+
+/* ----------------------------------------------------------------------------------------------
+ * Training batches: format-201 games -> network tensors, on the device (csrc/training_batch.hip).
+ * What the reference's dataset reader does on one host thread (src/dataset/torch_api.cpp: load_dataset_fragment, get_dataset_size,
+ * get_tensor_shapes, load_batch): per sample the board is rebuilt from the game's moves, the sample dequantised
+ * (SearchDataStorage_v201::storeTo), one of the 8 symmetries applied, the input features encoded (PatternCalculator::setBoard +
+ * NNInputFeatures::encode) and the training targets written.  Here one wavefront does that per sample, a whole batch in one launch.
+ * A dataset holds numbered fragments of one game configuration (square boards up to 20x20).  Everything except the two load_batch
+ * calls is host work and needs no GPU: the games' bytes are uploaded at the first load_batch that uses their fragment.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct AgxDataset AgxDataset; /* opaque; every call locks the dataset's mutex */
+
+typedef struct AgxDatasetSample
+{ /* Sample_t (dataset/torch_api.h) */
+	int fragment, game, sample, augmentation; /* augmentation: symmetry 0..7 (utils/augmentations.hpp) */
+} AgxDatasetSample;
+
+typedef struct AgxTensorShape
+{ /* TensorSize_t (dataset/torch_api.h) */
+	int rank, dim[4];
+} AgxTensorShape;
+
+enum
+{
+	AGX_BATCH_INPUT_FP16 = 1,    /* d_input holds IEEE half values instead of float32 */
+	AGX_BATCH_POLICY_VISITS = 2  /* policy target of SamplerVisits (dataset/Sampler.cpp:96-133): a proven draw keeps its visit count; default: torch_api.cpp's max(1, visits) */
+};
+
+int agx_dataset_create(int rules, int rows, int cols, AgxDataset** out);
+int agx_dataset_destroy(AgxDataset* dataset);
+/* Fragment `fragment` (any number >= 0 that is not loaded yet) from a file written by agx_game_buffer_save (compressed or not), or a copy of
+ * the finished games of a live buffer.  AGX_ERR_INVALID with a message in agx_last_error() when the rules or the board differ from the
+ * dataset's, when a game's bytes do not follow the format-201 layout, or when a sample points outside its game or its board. */
+int agx_dataset_add_fragment_file(AgxDataset* dataset, int fragment, const char* path);
+int agx_dataset_add_fragment_buffer(AgxDataset* dataset, int fragment, const AgxGameBuffer* buffer);
+int agx_dataset_unload_fragment(AgxDataset* dataset, int fragment); /* waits for the batches of this dataset that are still in flight */
+int agx_dataset_games(const AgxDataset* dataset, int* games);
+/* get_dataset_size: per game, fragments in ascending order, (fragment, game, samples, symmetries) */
+int agx_dataset_sizes(const AgxDataset* dataset, int* h_sizes, int capacity_games);
+int agx_dataset_stats(const AgxDataset* dataset, AgxGameBufferStats* out); /* sums over all fragments */
+/* get_tensor_shapes for a batch of n samples; any output may be NULL.  input [n, rows, cols, 32], features [n, rows * cols],
+ * policy [n, rows, cols], value [n, 3], moves_left [n, 1], action_values [n, rows, cols, 3] */
+int agx_dataset_tensor_shapes(const AgxDataset* dataset, int n, AgxTensorShape* input, AgxTensorShape* features, AgxTensorShape* policy_target,
+		AgxTensorShape* value_target, AgxTensorShape* moves_left_target, AgxTensorShape* action_values_target);
+/* One launch on `stream` writes sample b of h_samples to index b of every output (device addresses, each aligned to its element type):
+ *   d_input          [n][rows][cols][32] bit j of the feature word as 0 / 1, float32 or (AGX_BATCH_INPUT_FP16) half; may be NULL
+ *   d_features       [n][rows * cols] the feature words themselves, the form agx_nn_forward takes; may be NULL
+ *   d_policy         [n][rows][cols] float32, sums to 1 (float32 sum in cell order of the transformed board, then * 1.0f / sum)
+ *   d_value          [n][3] (win, draw, loss) of the game's outcome for the side to move
+ *   d_moves_left     [n][1]
+ *   d_action_values  [n][rows][cols][3] (win, draw, loss) per cell — sample b at index b (see training_batch.hip on the reference here)
+ * The call returns when the launch is enqueued; h_samples may be reused at once.  In the steady state it waits for nothing on the
+ * device and synchronises nothing; on the host it may wait for the batch enqueued four calls earlier (whose record buffer it takes
+ * over).  Three things allocate device memory and may therefore be serialised with the device's work by the runtime: the dataset's
+ * first batch (tables, spill areas), the first batch that uses a fragment (its bytes are uploaded with a blocking copy) and a batch
+ * larger than any of the four before it in its record slot (at least 1024 samples fit from the start).  The dataset lives on the HIP
+ * device that is current at its first batch: AGX_ERR_STATE when a later call finds another one current.
+ * A fragment, game, sample or augmentation out of range is AGX_ERR_INVALID before anything is launched.  Under renju the foul test
+ * follows nested 3x3 forks 16 deep; a sample beyond that (no known game has one) gets features that are not to be trusted: the
+ * host-pointer form returns AGX_ERR_STATE for its batch, this form at the next call on the dataset, naming the sample. */
+int agx_dataset_load_batch(AgxDataset* dataset, int n, const AgxDatasetSample* h_samples, void* d_input, uint32_t* d_features, float* d_policy,
+		float* d_value, float* d_moves_left, float* d_action_values, int flags, void* stream);
+/* the same into host memory (the dataset owns the device staging and a stream of its own; one launch, one copy back per output, returns
+ * when the data is there).  Calls from several threads run one after the other. */
+int agx_dataset_load_batch_host(AgxDataset* dataset, int n, const AgxDatasetSample* h_samples, void* h_input, uint32_t* h_features, float* h_policy,
+		float* h_value, float* h_moves_left, float* h_action_values, int flags);
 
 /* Raw device-memory helpers so that non-HIP hosts (ctypes, cgo) can stage buffers. */
 int agx_malloc(void** d_ptr, size_t bytes);

@@ -501,6 +501,67 @@ namespace agx
 				return m_engine;
 			}
 	};
+
+	/* The consumer of the record sink: format-201 games -> training tensors on the device (agx.h: agx_dataset_*; what the reference's
+	 * dataset/torch_api.h reader does on one host thread).  Fragments are numbered like Dataset::load(i, path). */
+	class TrainingDataset
+	{
+			AgxDataset *m_dataset = nullptr;
+		public:
+			TrainingDataset(int rules, int rows, int cols)
+			{
+				check(agx_dataset_create(rules, rows, cols, &m_dataset));
+			}
+			TrainingDataset(const TrainingDataset&) = delete;
+			TrainingDataset& operator=(const TrainingDataset&) = delete;
+			~TrainingDataset()
+			{
+				agx_dataset_destroy(m_dataset);
+			}
+			void load(int fragment, const std::string &path)
+			{
+				check(agx_dataset_add_fragment_file(m_dataset, fragment, path.c_str()));
+			}
+			void load(int fragment, const AgxGameBuffer *buffer)
+			{
+				check(agx_dataset_add_fragment_buffer(m_dataset, fragment, buffer));
+			}
+			void unload(int fragment)
+			{
+				check(agx_dataset_unload_fragment(m_dataset, fragment));
+			}
+			int numberOfGames() const
+			{
+				int games = 0;
+				check(agx_dataset_games(m_dataset, &games));
+				return games;
+			}
+			/* (fragment, game, samples, symmetries) per game */
+			std::vector<int> sizes() const
+			{
+				std::vector<int> result(4 * static_cast<size_t>(numberOfGames()));
+				if (!result.empty())
+					check(agx_dataset_sizes(m_dataset, result.data(), static_cast<int>(result.size() / 4)));
+				return result;
+			}
+			AgxGameBufferStats getStats() const
+			{
+				AgxGameBufferStats stats;
+				check(agx_dataset_stats(m_dataset, &stats));
+				return stats;
+			}
+			/* device pointers, enqueued on `stream`; d_input / d_features may be null */
+			void loadBatch(const std::vector<AgxDatasetSample> &samples, void *d_input, uint32_t *d_features, float *d_policy, float *d_value, float *d_moves_left,
+					float *d_action_values, int flags = 0, void *stream = nullptr)
+			{
+				check(agx_dataset_load_batch(m_dataset, static_cast<int>(samples.size()), samples.data(), d_input, d_features, d_policy, d_value, d_moves_left,
+						d_action_values, flags, stream));
+			}
+			AgxDataset* handle() const noexcept
+			{
+				return m_dataset;
+			}
+	};
 }
 
 #endif /* AGX_HPP_ */
