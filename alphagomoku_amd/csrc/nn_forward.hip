@@ -29,8 +29,11 @@
  *   - 20x20 boards do not fit two planes: the INPLACE variant computes every layer over its own input (all outputs stay in
  *     accumulators until every wave has passed a barrier) and parks the residual input in a per-workgroup global scratch.
  *   - Template flags keep the variants apart: <F, ROWS, COLS, INPLACE, QHEAD>; the pv kernels carry no q-head code.
+ *   - These kernels are the 15x15 and 20x20 boards' own.  Every other shape (5..20 rows and columns) runs the run-time-shaped kernel of
+ *     nn_any_board.hip (AgxNet::any_board), and so do these two with AGX_NN_ANY_BOARD=1 in the environment.
  */
 #include "agx_internal.hpp"
+#include "nn_any_board.hpp"
 
 #include <vector>
 #include <mutex>
@@ -1973,6 +1976,7 @@ struct AgxNet
 		std::vector<StreamScratch> scratch_by_stream;
 		size_t skip_bytes = 0;
 		bool inplace = false;
+		bool any_board = false; // the run-time-shaped kernel (nn_any_board.hip): every shape but 15x15 / 20x20, or AGX_NN_ANY_BOARD=1
 		float bp2 = 0.0f;
 		float bv1[4] = { 0, 0, 0, 0 };
 		float bv3[3] = { 0, 0, 0 };
@@ -1984,7 +1988,7 @@ namespace
 {
 	bool is_supported(const AgxNetDesc &d)
 	{
-		return ((d.rows == 15 && d.cols == 15) || (d.rows == 20 && d.cols == 20)) && (d.filters == 64 || d.filters == 128) && d.blocks >= 0
+		return d.rows >= agx_any::MIN_SIDE && d.rows <= agx_any::MAX_SIDE && d.cols >= agx_any::MIN_SIDE && d.cols <= agx_any::MAX_SIDE && (d.filters == 64 || d.filters == 128) && d.blocks >= 0
 				&& (d.in_channels == 32 || (d.in_channels == 8 && d.action_values == 0)) // 8: ResnetPVraw (networks.cpp:107-129); the raw PVQ variant is off the path
 				&& d.value_hidden == ((2 * d.filters < 256) ? 2 * d.filters : 256) && (d.action_values == 0 || d.action_values == 1);
 	}
@@ -2036,7 +2040,7 @@ int agx_net_create(const AgxNetDesc *desc, AgxNet **out)
 {
 	AGX_REQUIRE(desc != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_net_create: null argument");
 	AGX_REQUIRE(is_supported(*desc), AGX_ERR_UNSUPPORTED,
-			"agx_net_create: unsupported network %dx%d blocks=%d filters=%d cin=%d hidden=%d (supported: 15x15 / 20x20, F in {64,128}, cin 32, or cin 8 without the action-values head)", desc->rows,
+			"agx_net_create: unsupported network %dx%d blocks=%d filters=%d cin=%d hidden=%d (supported: 5..20 rows and cols, F in {64,128}, cin 32, or cin 8 without the action-values head)", desc->rows,
 			desc->cols, desc->blocks, desc->filters, desc->in_channels, desc->value_hidden);
 	AgxNet *net = new AgxNet();
 	net->desc = *desc;
@@ -2070,10 +2074,15 @@ int agx_net_load_weights(AgxNet *net, const float *h_blob, size_t n_floats)
 	ptr += 25 * C * F;
 	bias.insert(bias.end(), ptr, ptr + F);
 	ptr += F;
-	// 15-column boards (row stride 16 = one MFMA tile) run the row-stationary k-loop, which reads the fragments in its own order
-	const bool row_order = (net->desc.cols + 1 == 16);
+	// 15x15 and 20x20 boards have kernels of their own; every other shape — and these two with AGX_NN_ANY_BOARD=1 — runs the run-time-shaped
+	// kernel (nn_any_board.hip), which reads its fragments tap-major (pack_conv)
+	const bool board15 = (net->desc.rows == 15 && net->desc.cols == 15), board20 = (net->desc.rows == 20 && net->desc.cols == 20);
+	const char *any = getenv("AGX_NN_ANY_BOARD");
+	net->any_board = !(board15 || board20) || (any != nullptr && any[0] == '1');
+	// 15x15 boards (row stride 16 = one MFMA tile) run the row-stationary k-loop, which reads the fragments in its own order
+	const bool row_order = board15 && !net->any_board;
 	// 20x20 boards with 128 filters run the column-tile k-loop (Geometry::COLT)
-	const bool column_order = (net->desc.rows == 20 && net->desc.cols == 20 && F == 128);
+	const bool column_order = board20 && F == 128 && !net->any_board;
 	auto pack3x3 = [&](const float *w)
 	{
 		if (row_order)
@@ -2135,10 +2144,12 @@ int agx_net_load_weights(AgxNet *net, const float *h_blob, size_t n_floats)
 
 	// 20x20 boards use the single-plane kernel (two planes do not fit into LDS); AGX_NN_SINGLE_PLANE=1 selects it for 15x15 too
 	const char *force = getenv("AGX_NN_SINGLE_PLANE");
-	net->inplace = (net->desc.rows == 20) || (force != nullptr && force[0] == '1');
-	if (net->inplace)
+	net->inplace = net->any_board || board20 || (force != nullptr && force[0] == '1');
+	if (net->any_board) // (one plane for every shape; its residual scratch is sized for the largest board)
+		net->skip_bytes = agx_any::skip_bytes_per_workgroup(F) * static_cast<size_t>(net->num_cus);
+	else if (net->inplace)
 	{
-		const size_t per_wg = (net->desc.rows == 20) ? ((F == 128) ? Geometry<128, 20, 20>::SKIP_PER_WG : Geometry<64, 20, 20>::SKIP_PER_WG)
+		const size_t per_wg = board20 ? ((F == 128) ? Geometry<128, 20, 20>::SKIP_PER_WG : Geometry<64, 20, 20>::SKIP_PER_WG)
 				: ((F == 128) ? Geometry<128, 15, 15>::SKIP_PER_WG : Geometry<64, 15, 15>::SKIP_PER_WG);
 		net->skip_bytes = per_wg * 8 * static_cast<size_t>(net->num_cus);
 	}
@@ -2227,7 +2238,38 @@ static int launch_forward(AgxNet *net, const uint32_t *d_features, const int *d_
 		p.skip = static_cast<half4*>(mine->skip);
 		p.vhead_x = static_cast<half_t*>(mine->vhead);
 	}
-	const bool big = (net->desc.rows == 20), wide = (net->desc.filters == 128), qhead = (p.q != nullptr), raw = (net->desc.in_channels == 8);
+	if (net->any_board)
+	{
+		agx_any::Params a;
+		a.w_in = p.w_in;
+		a.w_tower = p.w_tower;
+		a.bias = p.bias;
+		a.wp2 = p.wp2;
+		a.wv1 = p.wv1;
+		a.wv2 = p.wv2;
+		a.vhead_x = p.vhead_x;
+		a.bv2 = p.bv2;
+		a.wv3 = p.wv3;
+		a.bp2 = p.bp2;
+		for (int i = 0; i < 4; i++)
+			a.bv1[i] = p.bv1[i];
+		for (int i = 0; i < 3; i++)
+		{
+			a.bv3[i] = p.bv3[i];
+			a.bq2[i] = p.bq2[i];
+		}
+		a.blocks = p.blocks;
+		a.batch = p.batch;
+		a.slot_list = p.slot_list;
+		a.count_ptr = p.count_ptr;
+		a.wq2 = p.wq2;
+		a.q = p.q;
+		a.skip = p.skip;
+		a.rows = net->desc.rows;
+		a.cols = net->desc.cols;
+		return agx_any::launch(a, net->desc.filters, net->desc.in_channels == 8, grid, d_features, d_policy, d_value, s);
+	}
+	const bool big = (net->desc.rows == 20 && net->desc.cols == 20), wide = (net->desc.filters == 128), qhead = (p.q != nullptr), raw = (net->desc.in_channels == 8);
 	const dim3 g(grid), t(512);
 #define AGX_LAUNCH_TOWER(FF, NN, IP, QH, RW) hipLaunchKernelGGL((nn_tower_kernel<FF, NN, NN, IP, QH, RW>), g, t, 0, s, p, d_features, d_policy, d_value)
 #define AGX_LAUNCH_HEADS(FF, NN, IP) do { if (qhead) AGX_LAUNCH_TOWER(FF, NN, IP, true, false); else if (raw) AGX_LAUNCH_TOWER(FF, NN, IP, false, true); \

@@ -54,8 +54,9 @@ int agx_device_cu_count(int* count); /* compute units of the current device */
  * ---------------------------------------------------------------------------------------------- */
 typedef struct AgxNetDesc
 {
-	int rows;           /* board rows (15 or 20) */
-	int cols;           /* board cols */
+	int rows;           /* board rows, 5 .. 20 */
+	int cols;           /* board cols, 5 .. 20, independent of rows (15x15 and 20x20 run kernels of their own, every other shape the
+	                       run-time-shaped one, csrc/nn_any_board.hip; AGX_NN_ANY_BOARD=1 in the environment sends those two there as well) */
 	int blocks;         /* residual blocks */
 	int filters;        /* conv filters F (64 or 128) */
 	int in_channels;    /* 32 (bit-packed features, NNInputFeatures.cpp:59-113) or 8 (ResnetPVraw, networks.cpp:107-129: ml::unpackInput
