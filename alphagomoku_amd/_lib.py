@@ -311,3 +311,24 @@ def _declare(c):  # noqa: F811
     c.agx_dataset_tensor_shapes.argtypes = [vp, ci] + [shape] * 6
     c.agx_dataset_load_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp]
     c.agx_dataset_load_batch_host.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, ci]
+
+
+class AgxSampleScore(ctypes.Structure):
+    _fields_ = [("policy_ce", ctypes.c_double), ("value_ce", ctypes.c_double), ("q_ce", ctypes.c_double), ("q_cells", ctypes.c_int32),
+                ("topk_hit", ctypes.c_int32 * 4), ("reserved", ctypes.c_int32)]
+
+
+class AgxNetScore(ctypes.Structure):
+    _fields_ = [("samples", ctypes.c_int64), ("policy_ce", ctypes.c_double), ("value_ce", ctypes.c_double), ("q_ce", ctypes.c_double),
+                ("q_cells", ctypes.c_int64), ("topk_hit", ctypes.c_int64 * 4)]
+
+
+_declare_dataset = _declare
+
+
+def _declare(c):  # noqa: F811
+    _declare_dataset(c)
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    c.agx_net_score_clear.argtypes = [vp, vp]
+    c.agx_net_score_outputs.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    c.agx_net_score_dataset.argtypes = [vp, vp, ci, vp, ci, ctypes.POINTER(AgxNetScore), vp]

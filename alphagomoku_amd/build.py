@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libagx.so")
 
 INCLUDE = os.path.join(HERE, "..", "include")
-SOURCES = ["agx_api.hip", "nn_forward.hip", "nn_any_board.hip", "engine.hip", "training_batch.hip", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
+SOURCES = ["agx_api.hip", "nn_forward.hip", "nn_any_board.hip", "engine.hip", "training_batch.hip", "net_score.hip", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
 DRIVER = os.path.join(HERE, "agx_selfplay")
 AG_LIB = os.path.join(HERE, "libagx_ag.so")               # the reference-named C++ classes (include/alphagomoku_agx/) over the C ABI
 BOUNDARY_TEST = os.path.join(HERE, "agx_boundary_test")  # tests/cpp/boundary_main.cpp: the reference's call chain on those classes
@@ -21,6 +21,8 @@ BOUNDARY_TEST = os.path.join(HERE, "agx_boundary_test")  # tests/cpp/boundary_ma
 BOUNDARY_SRC = os.path.join(HERE, "..", "tests", "cpp", "boundary_main.cpp")
 TRAINING_TEST = os.path.join(HERE, "agx_training_batch_test")  # tests/cpp/training_batch_main.cpp: the reference's dataset entry points (dataset.hpp)
 TRAINING_SRC = os.path.join(HERE, "..", "tests", "cpp", "training_batch_main.cpp")
+SCORE_TEST = os.path.join(HERE, "agx_net_score_test")  # tests/cpp/net_score_main.cpp: ag::getAccuracy on the loaded dataset
+SCORE_SRC = os.path.join(HERE, "..", "tests", "cpp", "net_score_main.cpp")
 HOST_ONLY = ("ag_classes.cpp", "selfplay_main.cpp")  # plain g++ sources in csrc/ (not part of libagx.so)
 
 
@@ -84,6 +86,8 @@ def _stale_host_targets():
         out.append(BOUNDARY_TEST)
     if _mtime(TRAINING_TEST) < max(_mtime(TRAINING_SRC), headers, _mtime(AG_LIB)) or AG_LIB in out:
         out.append(TRAINING_TEST)
+    if _mtime(SCORE_TEST) < max(_mtime(SCORE_SRC), headers, _mtime(AG_LIB)) or AG_LIB in out:
+        out.append(SCORE_TEST)
     return out
 
 
@@ -148,7 +152,7 @@ def build(force=False, verbose=True):
         relink = True
     if relink:
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + [BUILD_ID_OBJ, "-lz"])
-    stale = [DRIVER, AG_LIB, BOUNDARY_TEST, TRAINING_TEST] if force else _stale_host_targets()
+    stale = [DRIVER, AG_LIB, BOUNDARY_TEST, TRAINING_TEST, SCORE_TEST] if force else _stale_host_targets()
     if DRIVER in stale:  # native C++ host driver over the C ABI (include/agx.hpp)
         run([cxx, "-std=c++17", "-O2", "-o", DRIVER, os.path.join(CSRC, "selfplay_main.cpp"), "-L" + HERE, "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     if AG_LIB in stale:  # the C++ boundary: plain host code (g++), no HIP types — a maintainer of the reference links it like any other library
@@ -158,6 +162,8 @@ def build(force=False, verbose=True):
         run([cxx, "-std=c++17", "-O2", "-Wall", "-o", BOUNDARY_TEST, BOUNDARY_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     if TRAINING_TEST in stale:
         run([cxx, "-std=c++17", "-O2", "-Wall", "-o", TRAINING_TEST, TRAINING_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
+    if SCORE_TEST in stale:
+        run([cxx, "-std=c++17", "-O2", "-Wall", "-o", SCORE_TEST, SCORE_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     return LIB
 
 

@@ -2302,4 +2302,17 @@ namespace ag
 					value_target, moves_left_target, action_values_target, 0));
 		}
 	}
+	std::vector<float> getAccuracy(const AGNetwork &network, const std::vector<Sample_t> &samples, int top_k)
+	{
+		if (top_k < 1 || top_k > 4)
+			throw std::invalid_argument("getAccuracy() : top_k must be 1 .. 4, got " + std::to_string(top_k));
+		AgxNetScore score { };
+		dataset_check(agx_net_score_dataset(network.handle(), loaded_dataset(), static_cast<int>(samples.size()),
+				reinterpret_cast<const AgxDatasetSample*>(samples.data()), 0, &score, nullptr));
+		std::vector<float> result(1 + top_k);
+		result[0] = static_cast<float>(score.samples);
+		for (int k = 0; k < top_k; k++)
+			result[1 + k] = static_cast<float>(score.topk_hit[k]);
+		return result;
+	}
 } /* namespace ag */

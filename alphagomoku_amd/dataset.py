@@ -143,6 +143,17 @@ class TrainingDataset:
                                               ptr("value_target"), ptr("moves_left_target"), ptr("action_values_target"), flags))
         return out
 
+    def score(self, net, samples, chunk=0, stream=None):
+        """How well `net` (networks.AGNetwork) fits these samples ([n, 4] as for load_batch): batch, network and reductions run on the
+        device, `chunk` samples at a time (0 = 1024), on `stream`; the call waits for the 72-byte result.  Returns networks.score_dict():
+        the sums (policy_ce, value_ce, q_ce, q_cells, topk_hit[4], samples) and their means (policy_loss, value_loss, q_loss,
+        accuracy[4]).  The total does not depend on chunk."""
+        from .networks import score_dict
+        rec = self._records(samples)
+        out = _lib.AgxNetScore()
+        check(lib.agx_net_score_dataset(net._net, self._h, rec.shape[0], rec.ctypes.data_as(ctypes.c_void_p), chunk, ctypes.byref(out), stream))
+        return score_dict(out)
+
     def sample(self, batch_size, generator):
         """BaseSampler::pick_sample (torch_api.cpp:46-77) batch_size times: the games in a shuffled order, of every game one random
         sample under one random symmetry; when every game has been visited the order is shuffled again.  generator: a

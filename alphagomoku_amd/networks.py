@@ -80,3 +80,70 @@ class AGNetwork:
         if self._net:
             lib.agx_net_destroy(self._net)
             self._net = ctypes.c_void_p()
+
+
+def score_dict(score):
+    """an AgxNetScore as a dict: the sums, and the means a learning curve plots (policy / value loss per sample, q loss per cell that had
+    an edge, accuracy[k - 1] = fraction of the samples whose best target move is among the network's k best)"""
+    n, cells = int(score.samples), int(score.q_cells)
+    hits = [int(h) for h in score.topk_hit]
+    return dict(samples=n, policy_ce=score.policy_ce, value_ce=score.value_ce, q_ce=score.q_ce, q_cells=cells, topk_hit=hits,
+                policy_loss=score.policy_ce / n if n else 0.0, value_loss=score.value_ce / n if n else 0.0,
+                q_loss=score.q_ce / cells if cells else 0.0, accuracy=[h / n if n else 0.0 for h in hits])
+
+
+def _address(x):
+    if x is None:
+        return None
+    if hasattr(x, "data_ptr"):   # a torch tensor
+        if not (x.is_cuda and x.is_contiguous()):
+            raise ValueError("score_outputs takes contiguous device tensors")
+        return ctypes.c_void_p(x.data_ptr())
+    return x.ptr if isinstance(x, DeviceBuffer) else ctypes.c_void_p(int(x))
+
+
+def score_outputs(rows, cols, n, policy, value, policy_target, value_target, action_values=None, action_values_target=None, *,
+                  sample_scores=None, total=None, stream=None):
+    """agx_net_score_outputs: losses and top-4 hits of n samples from a network's outputs (the layout agx_nn_forward[_pvq] writes: policy
+    [n, rows * cols], value [n, 3], action_values [n, rows * cols, 2]) and the targets (the layout load_batch writes: [n, rows, cols],
+    [n, 3], [n, rows, cols, 3]), all float32 on the device: torch tensors, DeviceBuffers or raw addresses.  With torch tensors the
+    launches go on torch.cuda.current_stream() unless `stream` names one (the library must share torch's HIP runtime, as for
+    TrainingDataset.load_batch).  sample_scores: room for n AgxSampleScore records (48 bytes each) or None.
+    total: a 72-byte device AgxNetScore the samples are ADDED to (clear it with score_clear; read it with score_total) — the call
+    then only enqueues and returns None.  Without it the call scores into a total of its own, waits and returns score_dict()."""
+    from . import _lib
+    tensors = [policy, value, policy_target, value_target, action_values, action_values_target, sample_scores, total]
+    if any(hasattr(t, "data_ptr") for t in tensors):
+        if not _lib.torch_shares_hip_runtime():
+            raise _lib.AgxError("this torch carries a HIP runtime of its own: call alphagomoku_amd._lib.share_torch_hip_runtime() before the "
+                                "library is first used in this process")
+        if stream is None:
+            import torch
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    own = DeviceBuffer(ctypes.sizeof(_lib.AgxNetScore)) if total is None else None
+    try:
+        if own is not None:
+            check(lib.agx_net_score_clear(own.ptr, stream))
+        check(lib.agx_net_score_outputs(rows, cols, n, _address(policy), _address(value), _address(action_values), _address(policy_target),
+                                        _address(value_target), _address(action_values_target), _address(sample_scores),
+                                        own.ptr if own is not None else _address(total), stream))
+        if own is None:
+            return None
+        check(lib.agx_stream_synchronize(stream))
+        return score_total(own)
+    finally:
+        if own is not None:
+            own.free()
+
+
+def score_clear(total, stream=None):
+    """agx_net_score_clear: zeroes a device AgxNetScore (a torch tensor, a DeviceBuffer or a raw address) on `stream`"""
+    check(lib.agx_net_score_clear(_address(total), stream))
+
+
+def score_total(total):
+    """reads a device AgxNetScore (a DeviceBuffer or a raw address) back with a blocking copy: score_dict()"""
+    from . import _lib
+    out = _lib.AgxNetScore()
+    check(lib.agx_memcpy_d2h(ctypes.byref(out), _address(total), ctypes.sizeof(out)))
+    return score_dict(out)

@@ -627,6 +627,60 @@ int agx_dataset_load_batch(AgxDataset* dataset, int n, const AgxDatasetSample* h
 int agx_dataset_load_batch_host(AgxDataset* dataset, int n, const AgxDatasetSample* h_samples, void* h_input, uint32_t* h_features, float* h_policy,
 		float* h_value, float* h_moves_left, float* h_action_values, int flags);
 
+/* ----------------------------------------------------------------------------------------------
+ * Scoring a network against saved games: losses and top-k accuracy, on the device (csrc/net_score.hip).
+ * The step a training loop runs between "new checkpoint" and "hand it to the self-play pool" (the reference: SupervisedLearning::validate
+ * with AGNetwork::getLoss and getAccuracy).  getAccuracy (src/networks/NetworkDataPack.cpp:321-345) is followed literally; MinML's loss
+ * code is not in the reference tree, so the loss formulas below are this project's own.  Per sample, with the network's outputs in the
+ * layout agx_nn_forward[_pvq] writes and the targets in the layout agx_dataset_load_batch writes:
+ *   policy_ce  = - sum over the cells with target t > 0 of t * log(max(p, FLT_MIN))
+ *   value_ce   = the same sum over the 3 value outputs
+ *   q_ce       = - sum of t_c * log(max(q_c, FLT_MIN)) over the 3 classes (win, draw, loss) of every cell whose POLICY target is > 0 (the
+ *                cells that had an edge: the other cells' action-value targets are filler); the output's loss class is the float32
+ *                1.0f - win - draw; q_cells counts those cells.  Both 0 without action values.
+ *   topk_hit   = getAccuracy with top_k = 4: correct = the first maximum of the policy target in row-major order (pickMove, utils/misc.cpp:
+ *                79-83); four times: best = the first maximum of the outputs, topk_hit[l..3] += 1 when best == correct, then the output at
+ *                best becomes 0 (in a copy: the caller's buffer is only read).  Once only zeros are left `best` stays on cell 0, so a sample
+ *                whose correct move is cell 0 can count more than once, as in the reference.  (std::max_element's way with NaNs is kept
+ *                too: a NaN on cell 0 is the maximum, any other NaN never is.)
+ * Every term is a float32 product of the float32 target and logf; a sample's terms are summed in float64 in a fixed order, the samples in
+ * sample order: totals are bit-identical however a set of samples is split into calls and wherever the launches run.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct AgxSampleScore
+{ /* 48 bytes */
+	double policy_ce, value_ce, q_ce;
+	int32_t q_cells;
+	int32_t topk_hit[4];
+	int32_t reserved; /* written as 0 */
+} AgxSampleScore;
+
+typedef struct AgxNetScore
+{ /* 72 bytes; sums over `samples` samples */
+	int64_t samples;
+	double policy_ce, value_ce, q_ce;
+	int64_t q_cells;
+	int64_t topk_hit[4];
+} AgxNetScore;
+
+/* Zeroes *d_total on `stream`. */
+int agx_net_score_clear(AgxNetScore* d_total, void* stream);
+/* Scores n samples and ADDS them to *d_total (device memory the caller has cleared or chained from earlier calls).  All pointers are device
+ * addresses: d_policy float[n][rows*cols], d_value float[n][3], d_action_values float[n][rows*cols][2] or NULL; d_policy_target
+ * float[n][rows*cols], d_value_target float[n][3], d_action_values_target float[n][rows*cols][3] (NULL exactly when d_action_values is).
+ * Two launches on `stream`, nothing else, nothing synchronised: one wavefront per sample writes d_sample_scores[n], one workgroup adds
+ * them up in sample order.  d_sample_scores == NULL is a CONVENIENCE PATH for callers with a few samples and no use for the records: they
+ * stay on the chip, in ONE launch of one workgroup that scores 16 samples at a time (the same bits, but a single compute unit does all the
+ * work: pass a records buffer for anything large, as agx_net_score_dataset does).  Boards 5..20 x 5..20. */
+int agx_net_score_outputs(int rows, int cols, int n, const float* d_policy, const float* d_value, const float* d_action_values,
+		const float* d_policy_target, const float* d_value_target, const float* d_action_values_target, AgxSampleScore* d_sample_scores,
+		AgxNetScore* d_total, void* stream);
+/* The whole path for n samples of a dataset, `chunk` at a time (0 = 1024): agx_dataset_load_batch (feature words and targets),
+ * agx_nn_forward or agx_nn_forward_pvq according to the network's description, agx_net_score_outputs — all on `stream`, in device
+ * scratch the call allocates for one chunk and frees before it returns; one 72-byte copy back into *h_out at the end (the call waits for
+ * it).  The total does not depend on `chunk`.  AGX_ERR_INVALID: null arguments, n <= 0, negative chunk, a dataset whose board is not the
+ * network's; the dataset's and the network's own errors pass through. */
+int agx_net_score_dataset(AgxNet* net, AgxDataset* dataset, int n, const AgxDatasetSample* h_samples, int chunk, AgxNetScore* h_out, void* stream);
+
 /* Raw device-memory helpers so that non-HIP hosts (ctypes, cgo) can stage buffers. */
 int agx_malloc(void** d_ptr, size_t bytes);
 int agx_free(void* d_ptr);

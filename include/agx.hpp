@@ -502,6 +502,35 @@ namespace agx
 			}
 	};
 
+	/* How well a network fits a set of samples (agx.h: agx_net_score_*): the sums of AgxNetScore and the means a learning curve plots.
+	 * The loss formulas are this project's own; accuracy(k) is the reference's getAccuracy (NetworkDataPack.cpp:321-345) / averageStats. */
+	struct NetScore: AgxNetScore
+	{
+			NetScore() :
+					AgxNetScore { }
+			{
+			}
+			double policy_loss() const noexcept
+			{
+				return (samples > 0) ? policy_ce / static_cast<double>(samples) : 0.0;
+			}
+			double value_loss() const noexcept
+			{
+				return (samples > 0) ? value_ce / static_cast<double>(samples) : 0.0;
+			}
+			double q_loss() const noexcept
+			{ // per cell that had an edge
+				return (q_cells > 0) ? q_ce / static_cast<double>(q_cells) : 0.0;
+			}
+			/* fraction of the samples whose best target move is among the network's k best, k = 1 .. 4 */
+			double accuracy(int k) const
+			{
+				if (k < 1 || k > 4)
+					throw std::invalid_argument("NetScore::accuracy: k must be 1 .. 4");
+				return (samples > 0) ? static_cast<double>(topk_hit[k - 1]) / static_cast<double>(samples) : 0.0;
+			}
+	};
+
 	/* The consumer of the record sink: format-201 games -> training tensors on the device (agx.h: agx_dataset_*; what the reference's
 	 * dataset/torch_api.h reader does on one host thread).  Fragments are numbered like Dataset::load(i, path). */
 	class TrainingDataset
@@ -556,6 +585,14 @@ namespace agx
 			{
 				check(agx_dataset_load_batch(m_dataset, static_cast<int>(samples.size()), samples.data(), d_input, d_features, d_policy, d_value, d_moves_left,
 						d_action_values, flags, stream));
+			}
+			/* losses and top-k accuracy of `net` on these samples: batch, network and reductions on the device, `chunk` samples at a time
+			 * (0 = 1024); waits for the result */
+			NetScore score(const AGNetwork &net, const std::vector<AgxDatasetSample> &samples, int chunk = 0, void *stream = nullptr)
+			{
+				NetScore result;
+				check(agx_net_score_dataset(net.handle(), m_dataset, static_cast<int>(samples.size()), samples.data(), chunk, &result, stream));
+				return result;
 			}
 			AgxDataset* handle() const noexcept
 			{

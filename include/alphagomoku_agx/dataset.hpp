@@ -16,6 +16,8 @@
 #ifndef ALPHAGOMOKU_AGX_DATASET_HPP_
 #define ALPHAGOMOKU_AGX_DATASET_HPP_
 
+#include <vector>
+
 namespace ag
 {
 	extern "C"
@@ -44,6 +46,14 @@ namespace ag
 		void load_batch(int batch_size, const Sample_t *samples, float *input, float *policy_target, float *value_target, float *moves_left_target,
 				float *action_values_target);
 	}
+
+	/* getAccuracy (include/alphagomoku/networks/NetworkDataPack.hpp, src/networks/NetworkDataPack.cpp:321-345) for samples of the loaded
+	 * dataset: the reference's vector of 1 + top_k floats — the number of samples, then for k = 1 .. top_k the samples whose best target
+	 * move (pickMove of the policy target) is among the network's k best — ready for averageStats.  The reference reads the outputs and
+	 * targets of a NetworkDataPack on the host; here batch, network and counting run on the device (agx.h: agx_net_score_dataset).
+	 * top_k is 1 .. 4 (std::invalid_argument otherwise: the device counts four ranks). */
+	class AGNetwork;
+	std::vector<float> getAccuracy(const AGNetwork &network, const std::vector<Sample_t> &samples, int top_k = 4);
 } /* namespace ag */
 
 #endif /* ALPHAGOMOKU_AGX_DATASET_HPP_ */
