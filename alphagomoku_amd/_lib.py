@@ -332,3 +332,24 @@ def _declare(c):  # noqa: F811
     c.agx_net_score_clear.argtypes = [vp, vp]
     c.agx_net_score_outputs.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     c.agx_net_score_dataset.argtypes = [vp, vp, ci, vp, ci, ctypes.POINTER(AgxNetScore), vp]
+
+
+class AgxPositionOutputs(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ["policy", "value", "action_values", "top_cells", "top_probs", "status"]]
+
+
+POSEVAL_MASK_FORBIDDEN, POSEVAL_RENORMALISE = 1, 2
+POSEVAL_STATUS_BAD_INPUT, POSEVAL_STATUS_FOUL_PROBE = 1, 2
+
+_declare_score = _declare
+
+
+def _declare(c):  # noqa: F811
+    _declare_score(c)
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    outputs = ctypes.POINTER(AgxPositionOutputs)
+    c.agx_position_evaluator_create.argtypes = [ci, ci, ci, ctypes.POINTER(vp)]
+    c.agx_position_evaluator_destroy.argtypes = [vp]
+    c.agx_position_evaluator_encode.argtypes = [vp, ci, vp, vp, ci, vp, vp, vp]
+    c.agx_position_evaluator_combine.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, outputs, vp]
+    c.agx_position_evaluator_evaluate.argtypes = [vp, vp, ci, vp, vp, ci, ci, ci, outputs, vp]

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libagx.so")
 
 INCLUDE = os.path.join(HERE, "..", "include")
-SOURCES = ["agx_api.hip", "nn_forward.hip", "nn_any_board.hip", "engine.hip", "training_batch.hip", "net_score.hip", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
+SOURCES = ["agx_api.hip", "nn_forward.hip", "nn_any_board.hip", "engine.hip", "training_batch.hip", "net_score.hip", "position_eval.hip", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
 DRIVER = os.path.join(HERE, "agx_selfplay")
 AG_LIB = os.path.join(HERE, "libagx_ag.so")               # the reference-named C++ classes (include/alphagomoku_agx/) over the C ABI
 BOUNDARY_TEST = os.path.join(HERE, "agx_boundary_test")  # tests/cpp/boundary_main.cpp: the reference's call chain on those classes
@@ -23,6 +23,8 @@ TRAINING_TEST = os.path.join(HERE, "agx_training_batch_test")  # tests/cpp/train
 TRAINING_SRC = os.path.join(HERE, "..", "tests", "cpp", "training_batch_main.cpp")
 SCORE_TEST = os.path.join(HERE, "agx_net_score_test")  # tests/cpp/net_score_main.cpp: ag::getAccuracy on the loaded dataset
 SCORE_SRC = os.path.join(HERE, "..", "tests", "cpp", "net_score_main.cpp")
+POSITION_TEST = os.path.join(HERE, "agx_position_eval_test")  # tests/cpp/position_eval_main.cpp: ag::AGNetwork::packInputData(index, board, sign)
+POSITION_SRC = os.path.join(HERE, "..", "tests", "cpp", "position_eval_main.cpp")
 HOST_ONLY = ("ag_classes.cpp", "selfplay_main.cpp")  # plain g++ sources in csrc/ (not part of libagx.so)
 
 
@@ -88,6 +90,8 @@ def _stale_host_targets():
         out.append(TRAINING_TEST)
     if _mtime(SCORE_TEST) < max(_mtime(SCORE_SRC), headers, _mtime(AG_LIB)) or AG_LIB in out:
         out.append(SCORE_TEST)
+    if _mtime(POSITION_TEST) < max(_mtime(POSITION_SRC), headers, _mtime(AG_LIB)) or AG_LIB in out:
+        out.append(POSITION_TEST)
     return out
 
 
@@ -152,7 +156,7 @@ def build(force=False, verbose=True):
         relink = True
     if relink:
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + [BUILD_ID_OBJ, "-lz"])
-    stale = [DRIVER, AG_LIB, BOUNDARY_TEST, TRAINING_TEST, SCORE_TEST] if force else _stale_host_targets()
+    stale = [DRIVER, AG_LIB, BOUNDARY_TEST, TRAINING_TEST, SCORE_TEST, POSITION_TEST] if force else _stale_host_targets()
     if DRIVER in stale:  # native C++ host driver over the C ABI (include/agx.hpp)
         run([cxx, "-std=c++17", "-O2", "-o", DRIVER, os.path.join(CSRC, "selfplay_main.cpp"), "-L" + HERE, "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     if AG_LIB in stale:  # the C++ boundary: plain host code (g++), no HIP types — a maintainer of the reference links it like any other library
@@ -164,6 +168,8 @@ def build(force=False, verbose=True):
         run([cxx, "-std=c++17", "-O2", "-Wall", "-o", TRAINING_TEST, TRAINING_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     if SCORE_TEST in stale:
         run([cxx, "-std=c++17", "-O2", "-Wall", "-o", SCORE_TEST, SCORE_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
+    if POSITION_TEST in stale:
+        run([cxx, "-std=c++17", "-O2", "-Wall", "-o", POSITION_TEST, POSITION_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     return LIB
 
 

@@ -111,13 +111,16 @@ namespace ag
 	}
 	void AGNetwork::release()
 	{
-		void **buffers[] = { &d_input, &d_policy, &d_value, &d_action_values };
+		void **buffers[] = { &d_input, &d_policy, &d_value, &d_action_values, &d_boards, &d_signs, &d_board_status };
 		for (void **p : buffers)
 		{
 			if (*p != nullptr)
 				agx_free(*p);
 			*p = nullptr;
 		}
+		if (position_evaluator != nullptr)
+			agx_position_evaluator_destroy(position_evaluator);
+		position_evaluator = nullptr;
 		if (net != nullptr)
 			agx_net_destroy(net);
 		net = nullptr;
@@ -147,6 +150,28 @@ namespace ag
 			throw std::logic_error("AGNetwork::packInputData() : index " + std::to_string(index) + " outside the batch of " + std::to_string(batch_size));
 		const int hw = desc.rows * desc.cols;
 		std::memcpy(input.data() + static_cast<size_t>(index) * hw, features, sizeof(uint32_t) * hw);
+		packed_as_board[index] = 0;
+	}
+	void AGNetwork::packInputData(int index, const matrix<Sign> &board, Sign signToMove)
+	{
+		if (index < 0 || index >= batch_size)
+			throw std::logic_error("AGNetwork::packInputData() : index " + std::to_string(index) + " outside the batch of " + std::to_string(batch_size));
+		if (board.rows() != desc.rows || board.cols() != desc.cols)
+			throw std::logic_error("AGNetwork::packInputData() : the board is " + std::to_string(board.rows()) + "x" + std::to_string(board.cols()) + ", the network's "
+					+ std::to_string(desc.rows) + "x" + std::to_string(desc.cols));
+		const size_t hw = static_cast<size_t>(desc.rows) * desc.cols;
+		if (position_evaluator == nullptr)
+		{ // (refuses boards other than 15x15 and 20x20)
+			check(agx_position_evaluator_create(static_cast<int>(game_config.rules), desc.rows, batch_size, &position_evaluator));
+			check(agx_malloc(&d_boards, hw * batch_size));
+			check(agx_malloc(&d_signs, batch_size));
+			check(agx_malloc(&d_board_status, sizeof(int32_t) * batch_size));
+		}
+		const auto byte_of = [](Sign s) { const int v = static_cast<int>(s); return static_cast<uint8_t>((v < 0 || v > 255) ? 255 : v); };
+		for (size_t i = 0; i < hw; i++)
+			boards[static_cast<size_t>(index) * hw + i] = byte_of(board[static_cast<int>(i)]);
+		signs[index] = byte_of(signToMove);
+		packed_as_board[index] = 1;
 	}
 	void AGNetwork::unpackOutput(int index, std::vector<float> &out_policy, std::vector<Value> &actionValues, Value &out_value, float &movesLeft) const
 	{ // NetworkDataPack::unpackPolicy / unpackValue / unpackActionValues (NetworkDataPack.cpp:199-236)
@@ -169,6 +194,22 @@ namespace ag
 			throw std::logic_error("AGNetwork::forward() : batch " + std::to_string(batch) + " exceeds the batch size " + std::to_string(batch_size));
 		const int hw = desc.rows * desc.cols;
 		check(agx_memcpy_h2d(d_input, input.data(), sizeof(uint32_t) * hw * batch));
+		encoded = 0;
+		for (int first = 0; first < batch; first++)
+			if (packed_as_board[first])
+			{ // a run of indices packed as boards: uploaded and encoded where the tower reads its rows (one launch per run; usually the whole batch)
+				int last = first;
+				while (last + 1 < batch && packed_as_board[last + 1])
+					last++;
+				const int count = last - first + 1;
+				check(agx_memcpy_h2d(static_cast<uint8_t*>(d_boards) + static_cast<size_t>(first) * hw, boards.data() + static_cast<size_t>(first) * hw, static_cast<size_t>(count) * hw));
+				check(agx_memcpy_h2d(static_cast<uint8_t*>(d_signs) + first, signs.data() + first, count));
+				check(agx_position_evaluator_encode(position_evaluator, count, static_cast<const uint8_t*>(d_boards) + static_cast<size_t>(first) * hw,
+						static_cast<const uint8_t*>(d_signs) + first, 0x01, static_cast<uint32_t*>(d_input) + static_cast<size_t>(first) * hw,
+						static_cast<int32_t*>(d_board_status) + first, nullptr));
+				encoded = last + 1;
+				first = last;
+			}
 		if (desc.action_values)
 			check(agx_nn_forward_pvq(net, static_cast<const uint32_t*>(d_input), batch, static_cast<float*>(d_policy), static_cast<float*>(d_value),
 					static_cast<float*>(d_action_values), nullptr));
@@ -185,6 +226,17 @@ namespace ag
 		if (desc.action_values)
 			check(agx_memcpy_d2h(action_values.data(), d_action_values, sizeof(float) * 2 * hw * launched));
 		launched = 0;
+		if (encoded > 0)
+		{
+			check(agx_memcpy_d2h(board_status.data(), d_board_status, sizeof(int32_t) * encoded));
+			const int upto = encoded;
+			encoded = 0;
+			for (int i = 0; i < upto; i++)
+				if (packed_as_board[i] && board_status[i] != 0)
+					throw std::logic_error("AGNetwork::forward() : index " + std::to_string(i) + (board_status[i] == AGX_POSEVAL_STATUS_BAD_INPUT ?
+							" was packed with a board that is no position (a cell or the sign to move is neither CROSS nor CIRCLE nor, for a cell, NONE)" :
+							" nests renju 3x3 forks deeper than the foul test follows: its forbidden bits are invalid"));
+		}
 	}
 	void AGNetwork::forward(int batch)
 	{
@@ -277,16 +329,23 @@ namespace ag
 			throw std::logic_error("AGNetwork::setBatchSize() : batch size must be positive");
 		if (batchSize == batch_size && d_input != nullptr)
 			return;
-		void **buffers[] = { &d_input, &d_policy, &d_value, &d_action_values };
+		void **buffers[] = { &d_input, &d_policy, &d_value, &d_action_values, &d_boards, &d_signs, &d_board_status };
 		for (void **p : buffers)
 		{
 			if (*p != nullptr)
 				agx_free(*p);
 			*p = nullptr;
 		}
+		if (position_evaluator != nullptr)
+			agx_position_evaluator_destroy(position_evaluator); // sized by the batch: the next board that is packed creates a new one
+		position_evaluator = nullptr;
 		batch_size = batchSize;
 		const size_t hw = static_cast<size_t>(desc.rows) * desc.cols, n = batchSize;
 		input.assign(n * hw, 0u);
+		boards.assign(n * hw, 0);
+		signs.assign(n, 0);
+		packed_as_board.assign(n, 0);
+		board_status.assign(n, 0);
 		policy.assign(n * hw, 0.0f);
 		value.assign(n * 3, 0.0f);
 		action_values.assign(desc.action_values ? n * hw * 2 : 0, 0.0f);

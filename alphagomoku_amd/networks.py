@@ -38,6 +38,8 @@ class AGNetwork:
         self._cdesc = AgxNetDesc(desc["rows"], desc["cols"], desc["blocks"], desc["filters"],
                                  desc["in_channels"], desc["value_hidden"], desc.get("action_values", 0))
         self._net = ctypes.c_void_p()
+        self._evaluators = {}          # rules -> (AgxPositionEvaluator, capacity), made by evaluate_positions
+        self._retired_evaluators = []  # replaced by larger ones; destroyed in close() (destroying one waits for its last launch)
         check(lib.agx_net_create(ctypes.byref(self._cdesc), ctypes.byref(self._net)))
 
     def blobFloats(self):
@@ -76,7 +78,79 @@ class AGNetwork:
             if q is not None:
                 q.free()
 
+    def _position_evaluator(self, rules, n):
+        """the network's AgxPositionEvaluator for `rules`, with room for n positions.  A larger batch than any before gets a new one (device
+        allocations, which the runtime may serialise with the device's work); the old one is kept until close(), so no call waits for it"""
+        cache = self._evaluators
+        have = cache.get(rules)
+        if have is None or have[1] < n:
+            if have is not None:
+                self._retired_evaluators.append(have[0])
+                del cache[rules]
+            handle = ctypes.c_void_p()
+            capacity = max(n, 64, 2 * have[1] if have is not None else 0)
+            check(lib.agx_position_evaluator_create(rules, self.desc["rows"], capacity, ctypes.byref(handle)))
+            cache[rules] = (handle, capacity)
+        return cache[rules][0]
+
+    def evaluate_positions(self, boards, signs, rules, symmetries=0x01, flags=0, top_k=0, stream=None, out=None):
+        """agx_position_evaluator_evaluate: boards [n, rows, cols] (or [n, rows * cols]) uint8 with 0 empty / 1 cross / 2 circle and signs [n]
+        uint8 (1 cross / 2 circle to move) -> policy [n, rows, cols], value [n, 3], action_values [n, rows, cols, 2] ('pvq' networks),
+        top_cells [n, top_k] int32 (row * cols + col, -1 once no legal cell is left), top_probs [n, top_k], status [n] int32.  The rows of
+        the symmetries in the mask `symmetries` are averaged; flags: _lib.POSEVAL_MASK_FORBIDDEN | _lib.POSEVAL_RENORMALISE (agx.h).
+        numpy arrays make a host round trip and come back as a dict of arrays.  Contiguous device torch tensors stay on the device: the
+        launches go on torch.cuda.current_stream() unless `stream` names one (the library must share torch's HIP runtime, as for
+        score_outputs), the outputs named in the dict `out` are written where they lie (without `out` torch allocates all of them), nothing
+        is waited for, and the dict is returned."""
+        from . import _lib
+        rows, cols = self.desc["rows"], self.desc["cols"]
+        hw, with_q = rows * cols, bool(self.desc.get("action_values", 0))
+        shapes = dict(policy=(rows, cols), value=(3,), action_values=(rows, cols, 2), top_cells=(top_k,), top_probs=(top_k,), status=())
+        kinds = dict(top_cells=np.int32, status=np.int32)
+        names = [k for k in shapes if (with_q or k != "action_values") and (top_k > 0 or not k.startswith("top_"))]
+        on_device = hasattr(boards, "data_ptr")
+        n = int(boards.shape[0])
+        if tuple(boards.shape[1:]) not in ((rows, cols), (hw,)) or tuple(signs.shape) != (n,):
+            raise ValueError("evaluate_positions: boards [n, %d, %d] and signs [n] expected" % (rows, cols))
+        pe = self._position_evaluator(rules, n)
+        c_out = _lib.AgxPositionOutputs()
+        if on_device:
+            import torch
+            if not _lib.torch_shares_hip_runtime():
+                raise _lib.AgxError("this torch carries a HIP runtime of its own: call alphagomoku_amd._lib.share_torch_hip_runtime() before the "
+                                    "library is first used in this process")
+            if boards.dtype != torch.uint8 or signs.dtype != torch.uint8:
+                raise ValueError("evaluate_positions: boards and signs are uint8 tensors")
+            if stream is None:
+                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if out is None:
+                out = {k: torch.empty((n,) + shapes[k], dtype=torch.int32 if k in kinds else torch.float32, device=boards.device) for k in names}
+            for k, t in out.items():
+                if k not in names or tuple(t.shape) != (n,) + shapes[k] or t.dtype != (torch.int32 if k in kinds else torch.float32):
+                    raise ValueError("evaluate_positions: output '%s' has no place in this call, or another shape or dtype than the call writes" % k)
+                setattr(c_out, k, _address(t))
+            check(lib.agx_position_evaluator_evaluate(pe, self._net, n, _address(boards), _address(signs), symmetries, flags, top_k, ctypes.byref(c_out), stream))
+            return out
+        b = np.ascontiguousarray(boards, dtype=np.uint8)
+        s = np.ascontiguousarray(signs, dtype=np.uint8)
+        bufs = {k: DeviceBuffer(n * int(np.prod(shapes[k], dtype=np.int64)) * 4) for k in names}
+        d_boards, d_signs = DeviceBuffer(b.nbytes), DeviceBuffer(s.nbytes)
+        try:
+            d_boards.upload(b)
+            d_signs.upload(s)
+            for k, buf in bufs.items():
+                setattr(c_out, k, buf.ptr)
+            check(lib.agx_position_evaluator_evaluate(pe, self._net, n, d_boards.ptr, d_signs.ptr, symmetries, flags, top_k, ctypes.byref(c_out), stream))
+            check(lib.agx_stream_synchronize(stream))
+            return {k: buf.download((n,) + shapes[k], kinds.get(k, np.float32)) for k, buf in bufs.items()}
+        finally:
+            for buf in list(bufs.values()) + [d_boards, d_signs]:
+                buf.free()
+
     def close(self):
+        for handle in [h for h, _ in self._evaluators.values()] + self._retired_evaluators:
+            lib.agx_position_evaluator_destroy(handle)
+        self._evaluators, self._retired_evaluators = {}, []
         if self._net:
             lib.agx_net_destroy(self._net)
             self._net = ctypes.c_void_p()
@@ -97,7 +171,7 @@ def _address(x):
         return None
     if hasattr(x, "data_ptr"):   # a torch tensor
         if not (x.is_cuda and x.is_contiguous()):
-            raise ValueError("score_outputs takes contiguous device tensors")
+            raise ValueError("a torch tensor passed as a device buffer must be a contiguous device tensor")
         return ctypes.c_void_p(x.data_ptr())
     return x.ptr if isinstance(x, DeviceBuffer) else ctypes.c_void_p(int(x))
 

@@ -681,6 +681,73 @@ int agx_net_score_outputs(int rows, int cols, int n, const float* d_policy, cons
  * network's; the dataset's and the network's own errors pass through. */
 int agx_net_score_dataset(AgxNet* net, AgxDataset* dataset, int n, const AgxDatasetSample* h_samples, int chunk, AgxNetScore* h_out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Positions evaluated on the device: boards -> policy, value, best moves (csrc/position_eval.hip).
+ * The primary entry point of the reference's network is AGNetwork::packInputData(index, board, signToMove) (AGNetwork.hpp:60), which encodes
+ * the board on the host; agx_nn_forward takes feature words.  A position evaluator closes the gap for callers that hold boards and no
+ * search: one launch encodes every (position, symmetry) row with the solver's own pattern code, the tower evaluates the rows, one launch
+ * maps the rows back, averages them and picks the best legal cells.  Averaging over symmetries and the top-k are this project's own
+ * (NNEvaluator draws one random symmetry per position).  With S = popcount(symmetry_mask), j the rank of symmetry s in the mask and T_s
+ * the board under s (utils/augmentations.hpp):
+ *   row p * S + j    = NNInputFeatures::encode(T_s(board p)), for every s in the mask in ascending order
+ *   policy[p][c]     = (0.0f + row_s0[image_s0(c)] + row_s1[image_s1(c)] + ...) * (1.0f / S), float32, ascending s; image_s(c) is the cell
+ *                      of T_s that shows cell c; then 0.0f on occupied cells and, with AGX_POSEVAL_MASK_FORBIDDEN, on the cells whose
+ *                      identity-row feature word carries the renju forbidden bit (bit 6)
+ *   value, action values: the same sum and multiplication (action values through image_s, not masked)
+ *   AGX_POSEVAL_RENORMALISE: sum = the policy values added in cell order, one float32 addition after the other, from 0.0f; every value
+ *                      is multiplied by 1.0f / sum; a sum of 0.0f leaves the values as they are (no NaN)
+ *   top_k picks      k times: the largest policy value among the legal cells (empty and, with AGX_POSEVAL_MASK_FORBIDDEN, not
+ *                      forbidden) not picked yet, of equal ones the lowest cell index (a NaN orders as -inf); cell -1 and probability
+ *                      0.0f once no legal cell is left
+ * Every output is a pure function of the tower's rows.  Boards of 15x15 and 20x20, all five rule sets.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct AgxPositionEvaluator AgxPositionEvaluator; /* opaque: pattern tables, the encode kernel's per-wave spill areas, and a features /
+                                                             policy / value / action-values workspace of capacity x 8 rows; every call locks its mutex */
+
+enum
+{
+	AGX_POSEVAL_MASK_FORBIDDEN = 1, /* policy 0.0f on renju fouls, which are then no legal cells either; needs symmetry 0 in the mask */
+	AGX_POSEVAL_RENORMALISE = 2     /* the masked policy is scaled to sum 1 */
+};
+enum
+{ /* status words */
+	AGX_POSEVAL_STATUS_BAD_INPUT = 1,  /* a cell value above 2 or a sign other than 1 / 2: zero feature rows, zero outputs, cells -1 */
+	AGX_POSEVAL_STATUS_FOUL_PROBE = 2  /* renju: 3x3 forks nest deeper than the foul test follows (16); the forbidden bits are not to be trusted */
+};
+
+typedef struct AgxPositionOutputs
+{ /* device addresses; any of them may be NULL */
+	float* policy;         /* [n][cells] */
+	float* value;          /* [n][3] = (win, draw, loss) */
+	float* action_values;  /* [n][cells][2] = (win, draw); 'pvq' networks only */
+	int32_t* top_cells;    /* [n][top_k] row * board_size + col, or -1 */
+	float* top_probs;      /* [n][top_k] */
+	int32_t* status;       /* [n] 0 or AGX_POSEVAL_STATUS_* */
+} AgxPositionOutputs;
+
+/* Allocates everything the calls below use, on the current HIP device: they allocate nothing and synchronise nothing.  AGX_ERR_UNSUPPORTED for a
+ * board size other than 15 or 20. */
+int agx_position_evaluator_create(int rules, int board_size, int capacity, AgxPositionEvaluator** out);
+int agx_position_evaluator_destroy(AgxPositionEvaluator* pe);
+/* The encode launch alone, for callers that run the tower themselves: d_boards uint8[n][cells] (0 empty, 1 cross, 2 circle, what
+ * agx_engine_set_board takes), d_signs uint8[n] (1 cross / 2 circle to move) -> d_features uint32[n * S][cells], d_status int32[n] (may be
+ * NULL).  AGX_ERR_INVALID before anything is launched: n above the capacity, a mask of 0 or above 0xFF. */
+int agx_position_evaluator_encode(AgxPositionEvaluator* pe, int n, const uint8_t* d_boards, const uint8_t* d_signs, int symmetry_mask,
+		uint32_t* d_features, int32_t* d_status, void* stream);
+/* The combine launch alone, on rows the caller got from the tower: d_policy_rows float[n * S][cells], d_value_rows float[n * S][3],
+ * d_action_value_rows float[n * S][cells][2] (NULL unless out->action_values is set), d_features the encode launch's rows (read only with
+ * AGX_POSEVAL_MASK_FORBIDDEN, else may be NULL), d_status_in its status words (may be NULL: every position counts as valid). */
+int agx_position_evaluator_combine(AgxPositionEvaluator* pe, int n, const uint8_t* d_boards, int symmetry_mask, int flags, int top_k,
+		const uint32_t* d_features, const float* d_policy_rows, const float* d_value_rows, const float* d_action_value_rows, const int32_t* d_status_in,
+		const AgxPositionOutputs* out, void* stream);
+/* Encode into the workspace, agx_nn_forward or (when out->action_values is set) agx_nn_forward_pvq on it, combine: three launches on
+ * `stream`, nothing synchronised.  Refused before anything is launched — AGX_ERR_INVALID: n above the capacity, a mask of 0 or above 0xFF,
+ * top_k outside 0..8, unknown flags, a network whose rows or cols differ from the evaluator's board, out->action_values with a network
+ * that has no such head; AGX_ERR_UNSUPPORTED: AGX_POSEVAL_MASK_FORBIDDEN with a mask that leaves symmetry 0 out.  Calls on one evaluator
+ * share its workspace: a call on another stream than the previous one is ordered behind it on the device. */
+int agx_position_evaluator_evaluate(AgxPositionEvaluator* pe, AgxNet* net, int n, const uint8_t* d_boards, const uint8_t* d_signs, int symmetry_mask,
+		int flags, int top_k, const AgxPositionOutputs* out, void* stream);
+
 /* Raw device-memory helpers so that non-HIP hosts (ctypes, cgo) can stage buffers. */
 int agx_malloc(void** d_ptr, size_t bytes);
 int agx_free(void* d_ptr);

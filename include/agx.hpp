@@ -599,6 +599,41 @@ namespace agx
 				return m_dataset;
 			}
 	};
+
+	/* Boards to policy, value and best moves on the device (agx.h: agx_position_evaluator_*): the encode launch in front of the tower, the
+	 * combine launch behind it.  What AGNetwork::packInputData(index, board, signToMove) + forward + unpackOutput do for one caller at a
+	 * time on the reference's host, for `capacity` positions per call; the average over several symmetries and the top-k are this
+	 * project's own.  All pointers are device addresses; every call only enqueues on `stream`. */
+	class PositionEvaluator
+	{
+			AgxPositionEvaluator *m_evaluator = nullptr;
+		public:
+			PositionEvaluator(int rules, int board_size, int capacity)
+			{
+				check(agx_position_evaluator_create(rules, board_size, capacity, &m_evaluator));
+			}
+			PositionEvaluator(const PositionEvaluator&) = delete;
+			PositionEvaluator& operator=(const PositionEvaluator&) = delete;
+			~PositionEvaluator()
+			{
+				agx_position_evaluator_destroy(m_evaluator);
+			}
+			/* feature words of every (position, symmetry) row: d_features uint32[n * popcount(symmetry_mask)][cells]; d_status may be null */
+			void encode(int n, const uint8_t *d_boards, const uint8_t *d_signs, int symmetry_mask, uint32_t *d_features, int32_t *d_status = nullptr, void *stream = nullptr)
+			{
+				check(agx_position_evaluator_encode(m_evaluator, n, d_boards, d_signs, symmetry_mask, d_features, d_status, stream));
+			}
+			/* encode, tower, combine; any pointer of `out` may be null */
+			void evaluate(const AGNetwork &net, int n, const uint8_t *d_boards, const uint8_t *d_signs, const AgxPositionOutputs &out, int symmetry_mask = 0x01, int flags = 0,
+					int top_k = 0, void *stream = nullptr)
+			{
+				check(agx_position_evaluator_evaluate(m_evaluator, net.handle(), n, d_boards, d_signs, symmetry_mask, flags, top_k, &out, stream));
+			}
+			AgxPositionEvaluator* handle() const noexcept
+			{
+				return m_evaluator;
+			}
+	};
 }
 
 #endif /* AGX_HPP_ */

@@ -11,6 +11,7 @@
 #ifndef ALPHAGOMOKU_AGX_NETWORKS_HPP_
 #define ALPHAGOMOKU_AGX_NETWORKS_HPP_
 
+#include "board.hpp"
 #include "configs.hpp"
 #include "../agx.h"
 
@@ -55,6 +56,12 @@ namespace ag
 			std::vector<float> policy, value, action_values;
 			void *d_input = nullptr, *d_policy = nullptr, *d_value = nullptr, *d_action_values = nullptr;
 			int launched = 0;
+			// the indices packed as boards: encoded on the device by forward (agx_position_evaluator_encode), in front of the tower
+			std::vector<uint8_t> boards, signs, packed_as_board;
+			std::vector<int32_t> board_status;
+			AgxPositionEvaluator *position_evaluator = nullptr;
+			void *d_boards = nullptr, *d_signs = nullptr, *d_board_status = nullptr;
+			int encoded = 0;
 		public:
 			AGNetwork() noexcept = default;
 			/* architecture "ResnetPV" / "ResnetPVraw" (outputs "pv"; the raw network reads the 8 low bits of a feature word) or "ResnetPVQ" ("pvq") */
@@ -68,6 +75,14 @@ namespace ag
 			size_t numberOfWeights() const;
 			void loadWeights(const std::vector<float> &blob); // the canonical blob of include/agx.h
 
+			/* AGNetwork.hpp:60: the board is kept on the host; forward / asyncForwardLaunch uploads the boards of the batch and encodes them on
+			 * the device (PatternCalculator::setBoard + NNInputFeatures::encode in one launch) before the tower runs.  15x15 and 20x20 boards.
+			 * asyncForwardJoin throws std::logic_error, naming the index, for a board that is no position (a cell that is neither NONE, CROSS
+			 * nor CIRCLE, a signToMove that is neither CROSS nor CIRCLE: its outputs come from zero features) and for a renju position whose
+			 * 3x3 forks nest deeper than the foul test follows (16; no known game has one: its forbidden bits are not to be trusted).  The
+			 * outputs of the other indices are valid.  Like packed feature words a packed board stays packed: a later forward encodes it
+			 * again until the index is packed anew, in either form. */
+			void packInputData(int index, const matrix<Sign> &board, Sign signToMove);
 			/* "Can be used to pack the data if the features were already calculated" (AGNetwork.hpp:66-69): one uint32 per cell */
 			void packInputData(int index, const uint32_t *features);
 			void unpackOutput(int index, std::vector<float> &policy, std::vector<Value> &actionValues, Value &value, float &movesLeft) const;
