@@ -17,24 +17,20 @@
  *     the loop divides: the only run-time divisions by S (cell of a position: the epilogue's mask, the input conv's plane index) are a
  *     multiply and a shift (Shape::magic), a few times per lane and board.
  *   - Residual values through a per-workgroup global scratch, written and read by the same lane (conv3x3_inplace of nn_forward.hip).
- *   - The value head's dense layers run behind the tower for all boards of the launch, K = 4 * rows * cols padded to 32 at run time.
+ *   - The value head's dense layers are not launched here: launch_forward() (nn_forward.hip) runs value_head_kernel behind the tower for all
+ *     boards of the launch, K = 4 * rows * cols padded to 32 (AgxNet::kpad(), handed to launch() for the row stride of NetParams::vhead_x).
+ *   - The types, the launch record and the helpers shared with nn_forward.hip are in nn_device.hpp.
  *
  * Slower per FLOP than the two specialised kernels (DESIGN.md 3.1 has the measured ratios): no row- or column-stationary reuse of
  * activation fragments, one fragment read per (tap, tile) for MT = 2 MFMAs.
  */
+#include "nn_device.hpp"
 #include "nn_any_board.hpp"
 
 #include <cmath>
-#include <cstdint>
 
 namespace
 {
-	typedef _Float16 half_t;
-	typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-	typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-	typedef _Float16 half2 __attribute__((ext_vector_type(2)));
-	typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 	struct Shape
 	{
 			int rows, cols;
@@ -42,31 +38,11 @@ namespace
 			int NT;       // 16-position tiles of the output: ceil(rows * S / 16)
 			int ntw;      // tiles per position group: ceil(NT / PG)
 			int HW;
-			int kpad;     // value-head dense input length: 4 HW rounded up to 32
+			int kpad;     // value-head dense input length (the host's AgxNet::kpad()): 4 HW rounded up to 32
 			int plane16;  // 16-byte units of the activation plane: (1 + S + NT * 16 + S + 2) positions
 			int S5;       // row stride of the padded input plane: S + 4
 			int npos5;    // its positions: (rows + 4) * S5 + 4
 			int magic;    // position / S == (position * magic) >> 16 for every position of a plane (65536 / S + 1: exact below 65536 / S)
-	};
-
-	struct NetParams
-	{
-			const half8 *w_in;
-			const half8 *w_tower;
-			const float *bias;
-			const float *wp2;
-			const float *wv1;
-			half_t *vhead_x;
-			float bp2;
-			float bv1[4];
-			int blocks;
-			int batch;
-			const int *slot_list;
-			const int *count_ptr;
-			const float *wq2;
-			float bq2[3];
-			float *q;
-			half4 *skip;
 	};
 
 	template<int F>
@@ -123,30 +99,6 @@ namespace
 		return (position * sh.magic) >> 16;
 	}
 
-	__device__ __forceinline__ void lds_barrier()
-	{ // a workgroup barrier for hand-offs through LDS only: does not wait for this wave's global stores in flight (nn_forward.hip)
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-		__builtin_amdgcn_s_barrier();
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-	}
-	__device__ __forceinline__ float half_plus_float_lo(uint32_t packed_halves, float addend)
-	{ // (float) low half + addend, rounded once
-		float d;
-		asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(packed_halves), "v"(addend));
-		return d;
-	}
-	__device__ __forceinline__ float half_plus_float_hi(uint32_t packed_halves, float addend)
-	{
-		float d;
-		asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(packed_halves), "v"(addend));
-		return d;
-	}
-
-	template<int MT>
-	struct BiasCarry
-	{ // a layer's bias values, requested by the layer in front of it behind its k-loop
-			floatx4 b[MT];
-	};
 	template<int F>
 	struct SkipCarry
 	{ // the residual input of a block's second layer, requested by its first layer behind its k-loop
@@ -237,6 +189,8 @@ namespace
 	 * MODE 3: action-values conv + tanh folded with its 1x1 conv to 3 outputs: `ppart` is [3][PS], the channel groups add their
 	 *         partial sums one after the other (a fixed order: results do not depend on wave timing).
 	 * valid_bits: bit n = this lane's cell of the wave's tile n is on the board.
+	 * (The head epilogues of modes 2 and 3, the policy softmax and the value head's conv1x1 stand here a second time on purpose: written once
+	 *  over a tile map, each of them moved the register allocation of the fixed-shape kernels — DESIGN.md 3.1.)
 	 */
 	template<int F, int MODE>
 	__device__ __forceinline__ void conv3x3_layer(char *plane, const half8 *__restrict__ wpk, BiasCarry<Cfg<F>::MT> &bias_carry, const float *__restrict__ next_bias,
@@ -262,10 +216,7 @@ namespace
 				if (MODE == 1)
 				{
 					const uint2 sk = skip_carry->v[i][n];
-					v[0] = half_plus_float_lo(sk.x, bv[0]);
-					v[1] = half_plus_float_hi(sk.x, bv[1]);
-					v[2] = half_plus_float_lo(sk.y, bv[2]);
-					v[3] = half_plus_float_hi(sk.y, bv[3]);
+					v = bias_plus_residual(sk, bv);
 				}
 				acc[i][n] = v;
 			}
@@ -510,29 +461,6 @@ namespace
 		}
 	}
 
-	__device__ __forceinline__ float block_reduce_max(float v, float *red, int tid)
-	{
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1)
-			v = fmaxf(v, __shfl_xor(v, o));
-		__syncthreads();
-		if ((tid & 63) == 0)
-			red[tid >> 6] = v;
-		__syncthreads();
-		return fmaxf(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7])));
-	}
-	__device__ __forceinline__ float block_reduce_sum(float v, float *red, int tid)
-	{
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1)
-			v += __shfl_xor(v, o);
-		__syncthreads();
-		if ((tid & 63) == 0)
-			red[tid >> 6] = v;
-		__syncthreads();
-		return ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
-	}
-
 	template<int F, bool QHEAD, bool RAW>
 	__global__ __launch_bounds__(512) void nn_any_board_kernel(NetParams p, Shape sh, const uint32_t *__restrict__ features, float *__restrict__ policy)
 	{
@@ -553,20 +481,7 @@ namespace
 		const int layer_halves8 = 9 * C::KC * C::MTILES * 64; // half8 elements per packed 3x3 layer
 		const WaveTiles wt = wave_tiles<F>(sh, wave);
 
-		for (int i = tid; i < C::KC * 64; i += C::THREADS)
-		{ // A fragments of the F x 4 value-head conv1x1 (p.wv1 is [F][4] fp32)
-			const int kc = i / 64, l = i % 64, unit = l & 15;
-			half8 f;
-#pragma unroll
-			for (int j = 0; j < 8; j++)
-				f[j] = static_cast<half_t>((unit < 4) ? p.wv1[(kc * 32 + 8 * (l >> 4) + j) * 4 + unit] : 0.0f);
-			s_wv1f[i] = f;
-		}
-		for (int i = tid; i < F; i += C::THREADS)
-			s_wp2[i] = p.wp2[i];
-		if (QHEAD)
-			for (int i = tid; i < F * 4; i += C::THREADS)
-				s_wq2[i] = p.wq2[i];
+		stage_head_weights<F, C::THREADS, QHEAD>(p.wv1, p.wp2, p.wq2, tid, s_wv1f, s_wp2, s_wq2);
 
 		// once per kernel: this thread's cell (one feature word / one policy output per thread) and this lane's on-board mask of the wave's tiles
 		const int cell_y = (tid < sh.HW) ? tid / sh.cols : 0, cell_x = (tid < sh.HW) ? tid - cell_y * sh.cols : 0;
@@ -602,11 +517,7 @@ namespace
 				for (int k = 0; k < (RAW ? 1 : 4); k++)
 				{
 					const uint32_t bits = (word >> (8 * k)) & 255u;
-					uint4 v;
-					v.x = ((bits & 1u) ? 0x3C00u : 0u) | ((bits & 2u) ? 0x3C000000u : 0u);
-					v.y = ((bits & 4u) ? 0x3C00u : 0u) | ((bits & 8u) ? 0x3C000000u : 0u);
-					v.z = ((bits & 16u) ? 0x3C00u : 0u) | ((bits & 32u) ? 0x3C000000u : 0u);
-					v.w = ((bits & 64u) ? 0x3C00u : 0u) | ((bits & 128u) ? 0x3C000000u : 0u);
+					const uint4 v = unpack_feature_byte(bits);
 					if (RAW) // the low byte of the word, 16 bytes per position
 						*reinterpret_cast<uint4*>(plane + q * 16) = v;
 					else
@@ -632,7 +543,7 @@ namespace
 			}
 
 			// ---- value head, stage 1: conv1x1 F -> 4 + ReLU as one 16 x 16 MFMA tile per 16 positions (4 of the 16 units are real), the tiles dealt
-			//      round-robin to the waves; the dense layers run in value_head_any_kernel for all boards of the launch ----
+			//      round-robin to the waves; the dense layers run in value_head_kernel (nn_forward.hip) for all boards of the launch ----
 			{
 				const int r = lane & 15, q4 = lane >> 4;
 				for (int n = wave; n < sh.NT; n += C::THREADS / 64)
@@ -674,12 +585,7 @@ namespace
 				float logit = -3.0e38f;
 				if (tid < sh.HW)
 				{
-					float s = p.bp2; // the channel groups' partial sums, added in a fixed order
-					if constexpr (C::CG == 4)
-						s += (ppart[cell_pos] + ppart[C::PS + cell_pos]) + (ppart[2 * C::PS + cell_pos] + ppart[3 * C::PS + cell_pos]);
-					else
-						s += ppart[cell_pos] + ppart[C::PS + cell_pos];
-					logit = s;
+					logit = p.bp2 + sum_partial_logits<C::CG, C::PS>(ppart, cell_pos);
 				}
 				const float m = block_reduce_max(logit, red, tid);
 				const float e = (tid < sh.HW) ? __expf(logit - m) : 0.0f;
@@ -695,82 +601,16 @@ namespace
 				if (tid < sh.HW)
 				{
 					const float z0 = p.bq2[0] + qpart[cell_pos], z1 = p.bq2[1] + qpart[C::PS + cell_pos], z2 = p.bq2[2] + qpart[2 * C::PS + cell_pos];
-					const float m = fmaxf(z0, fmaxf(z1, z2));
-					const float e0 = __expf(z0 - m), e1 = __expf(z1 - m), e2 = __expf(z2 - m);
-					const float inv = 1.0f / (e0 + e1 + e2);
+					const float2 win_draw = softmax3_win_draw(z0, z1, z2);
 					float *out = p.q + (static_cast<size_t>(b) * sh.HW + tid) * 2;
-					out[0] = e0 * inv; // win
-					out[1] = e1 * inv; // draw
+					out[0] = win_draw.x;
+					out[1] = win_draw.y;
 				}
 			}
 		}
 	}
 
-	/*
-	 * Value head behind the tower, for every board of a launch (value_head_kernel of nn_forward.hip with the input length a run-time
-	 * argument): hidden = ReLU(W2^T x + b2) (kpad -> D), out = softmax(W3^T hidden + b3).  One workgroup = 16 boards x all D hidden units.
-	 */
-	template<int D>
-	__global__ __launch_bounds__(256) void value_head_any_kernel(const half_t *__restrict__ x, const half8 *__restrict__ w2, const float *__restrict__ b2,
-			const float *__restrict__ w3, float b30, float b31, float b32, const int *__restrict__ slot_list, const int *__restrict__ count_ptr, int batch_cap,
-			int kpad, float *__restrict__ value)
-	{
-		constexpr int MTW = D / 64; // 16-unit tiles per wave
-		__shared__ float hid[16][D + 1];
-		const int batch = (count_ptr != nullptr) ? min(*count_ptr, batch_cap) : batch_cap;
-		const int b0 = blockIdx.x * 16;
-		if (b0 >= batch)
-			return;
-		const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q4 = lane >> 4;
-		const int board = min(b0 + r, batch - 1); // the tail tile repeats the last board (never stored)
-		floatx4 acc[MTW];
-#pragma unroll
-		for (int i = 0; i < MTW; i++)
-			acc[i] = floatx4 { 0.0f, 0.0f, 0.0f, 0.0f };
-		const half8 *xb = reinterpret_cast<const half8*>(x + static_cast<size_t>(board) * kpad) + q4;
-		const half8 *wp = w2 + (wave * MTW) * 64 + lane;
-		const int ksteps = kpad / 32;
-		for (int kc = 0; kc < ksteps; kc++)
-		{
-			const half8 bfrag = xb[kc * 4];
-#pragma unroll
-			for (int i = 0; i < MTW; i++)
-				acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wp[(kc * (D / 16) + i) * 64], bfrag, acc[i], 0, 0, 0);
-		}
-#pragma unroll
-		for (int i = 0; i < MTW; i++)
-		{ // lane holds hidden units 4 * q4 .. + 3 of tile i for board r
-			const int u = (wave * MTW + i) * 16 + 4 * q4;
-#pragma unroll
-			for (int e = 0; e < 4; e++)
-				hid[r][u + e] = fmaxf(acc[i][e] + b2[u + e], 0.0f);
-		}
-		__syncthreads();
-		__shared__ float logits[16][3];
-		if (tid < 48)
-		{ // 16 boards x 3 outputs, each reduced in a fixed order
-			const int bb = tid / 3, o = tid % 3;
-			float sacc = 0.0f;
-			for (int j = 0; j < D; j++)
-				sacc += hid[bb][j] * w3[j * 3 + o];
-			logits[bb][o] = sacc + ((o == 0) ? b30 : ((o == 1) ? b31 : b32));
-		}
-		__syncthreads();
-		if (tid < 16 && b0 + tid < batch)
-		{
-			const int bi = b0 + tid;
-			const int slot = (slot_list != nullptr) ? slot_list[bi] : bi;
-			const float z0 = logits[tid][0], z1 = logits[tid][1], z2 = logits[tid][2];
-			const float m = fmaxf(z0, fmaxf(z1, z2));
-			const float e0 = __expf(z0 - m), e1 = __expf(z1 - m), e2 = __expf(z2 - m);
-			const float inv = 1.0f / (e0 + e1 + e2);
-			value[static_cast<size_t>(slot) * 3 + 0] = e0 * inv;
-			value[static_cast<size_t>(slot) * 3 + 1] = e1 * inv;
-			value[static_cast<size_t>(slot) * 3 + 2] = e2 * inv;
-		}
-	}
-
-	Shape make_shape(int rows, int cols, int position_groups)
+	Shape make_shape(int rows, int cols, int position_groups, int kpad)
 	{
 		Shape sh;
 		sh.rows = rows;
@@ -779,7 +619,7 @@ namespace
 		sh.NT = (rows * sh.S + 15) / 16;
 		sh.ntw = (sh.NT + position_groups - 1) / position_groups;
 		sh.HW = rows * cols;
-		sh.kpad = (sh.HW * 4 + 31) / 32 * 32;
+		sh.kpad = kpad;
 		sh.S5 = sh.S + 4;
 		sh.npos5 = (rows + 4) * sh.S5 + 4;
 		sh.magic = 65536 / sh.S + 1;
@@ -794,34 +634,15 @@ namespace agx_any
 		return sizeof(half4) * static_cast<size_t>((filters == 128) ? Cfg<128>::SKIP_PER_WG : Cfg<64>::SKIP_PER_WG);
 	}
 
-	int launch(const Params &in, int filters, bool raw, int grid, const uint32_t *d_features, float *d_policy, float *d_value, hipStream_t stream)
+	int launch(const NetParams &p, int rows, int cols, int filters, bool raw, int grid, int kpad, const uint32_t *d_features, float *d_policy, hipStream_t stream)
 	{
-		AGX_REQUIRE(in.rows >= MIN_SIDE && in.rows <= MAX_SIDE && in.cols >= MIN_SIDE && in.cols <= MAX_SIDE && (filters == 64 || filters == 128), AGX_ERR_UNSUPPORTED,
-				"agx_nn_forward: no kernel for a %dx%d board with %d filters", in.rows, in.cols, filters);
-		AGX_REQUIRE(in.skip != nullptr && in.vhead_x != nullptr && grid > 0, AGX_ERR_STATE, "agx_nn_forward: launch scratch missing");
-		NetParams p;
-		p.w_in = static_cast<const half8*>(in.w_in);
-		p.w_tower = static_cast<const half8*>(in.w_tower);
-		p.bias = in.bias;
-		p.wp2 = in.wp2;
-		p.wv1 = in.wv1;
-		p.vhead_x = static_cast<half_t*>(in.vhead_x);
-		p.bp2 = in.bp2;
-		for (int i = 0; i < 4; i++)
-			p.bv1[i] = in.bv1[i];
-		p.blocks = in.blocks;
-		p.batch = in.batch;
-		p.slot_list = in.slot_list;
-		p.count_ptr = in.count_ptr;
-		p.wq2 = in.wq2;
-		for (int i = 0; i < 3; i++)
-			p.bq2[i] = in.bq2[i];
-		p.q = in.q;
-		p.skip = static_cast<half4*>(in.skip);
-		const bool qhead = (in.q != nullptr);
+		AGX_REQUIRE(rows >= MIN_SIDE && rows <= MAX_SIDE && cols >= MIN_SIDE && cols <= MAX_SIDE && (filters == 64 || filters == 128), AGX_ERR_UNSUPPORTED,
+				"agx_nn_forward: no kernel for a %dx%d board with %d filters", rows, cols, filters);
+		AGX_REQUIRE(p.skip != nullptr && p.vhead_x != nullptr && grid > 0, AGX_ERR_STATE, "agx_nn_forward: launch scratch missing");
+		const bool qhead = (p.q != nullptr);
 		AGX_REQUIRE(!(qhead && raw), AGX_ERR_UNSUPPORTED, "agx_nn_forward: no action-values head on an 8-channel network");
 		const dim3 g(grid), t(512);
-#define AGX_ANY_TOWER(FF, QH, RW) do { Shape sh = make_shape(in.rows, in.cols, Cfg<FF>::PG); sh.plane16 = (1 + sh.S + sh.NT * 16 + sh.S + 2) * Cfg<FF>::POS_BYTES / 16; \
+#define AGX_ANY_TOWER(FF, QH, RW) do { Shape sh = make_shape(rows, cols, Cfg<FF>::PG, kpad); sh.plane16 = (1 + sh.S + sh.NT * 16 + sh.S + 2) * Cfg<FF>::POS_BYTES / 16; \
 		hipLaunchKernelGGL((nn_any_board_kernel<FF, QH, RW>), g, t, 0, stream, p, sh, d_features, d_policy); } while (0)
 #define AGX_ANY_VARIANTS(FF) do { if (qhead) AGX_ANY_TOWER(FF, true, false); else if (raw) AGX_ANY_TOWER(FF, false, true); else AGX_ANY_TOWER(FF, false, false); } while (0)
 		if (filters == 128)
@@ -830,15 +651,6 @@ namespace agx_any
 			AGX_ANY_VARIANTS(64);
 #undef AGX_ANY_VARIANTS
 #undef AGX_ANY_TOWER
-		const int kpad = (in.rows * in.cols * 4 + 31) / 32 * 32;
-		const dim3 vg((in.batch + 15) / 16), vt(256);
-#define AGX_ANY_VALUE(DD) hipLaunchKernelGGL((value_head_any_kernel<DD>), vg, vt, 0, stream, p.vhead_x, static_cast<const half8*>(in.wv2), in.bv2, in.wv3, in.bv3[0], \
-		in.bv3[1], in.bv3[2], in.slot_list, in.count_ptr, in.batch, kpad, d_value)
-		if (filters == 128)
-			AGX_ANY_VALUE(256);
-		else
-			AGX_ANY_VALUE(128);
-#undef AGX_ANY_VALUE
 		AGX_HIP_CHECK(hipGetLastError());
 		return AGX_OK;
 	}

@@ -31,8 +31,14 @@
  *   - Template flags keep the variants apart: <F, ROWS, COLS, INPLACE, QHEAD>; the pv kernels carry no q-head code.
  *   - These kernels are the 15x15 and 20x20 boards' own.  Every other shape (5..20 rows and columns) runs the run-time-shaped kernel of
  *     nn_any_board.hip (AgxNet::any_board), and so do these two with AGX_NN_ANY_BOARD=1 in the environment.
+ *   - What the two files have in common is in nn_device.hpp: the vector types, the launch record NetParams, the layers' small helpers, the
+ *     unpacking of a feature byte, the staging of the heads' weights, the heads' fixed-order sums and softmax.  The k-loops and the layer
+ *     epilogues are each file's own.
+ *   - The value head's dense layers are one kernel (value_head_kernel, the input length an argument) launched from one place:
+ *     launch_forward(), behind whichever tower ran.
  */
 #include "agx_internal.hpp"
+#include "nn_device.hpp"
 #include "nn_any_board.hpp"
 
 #include <vector>
@@ -68,36 +74,6 @@
 
 namespace
 {
-	typedef _Float16 half_t;
-	typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-	typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-	typedef _Float16 half2 __attribute__((ext_vector_type(2)));
-	typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-	struct NetParams
-	{
-			const half8 *w_in;      // packed conv5x5 fragments
-			const half8 *w_tower;   // packed 3x3 fragments: 2*blocks layers, then the policy conv
-			const float *bias;      // [1 + 2*blocks + 1][F]
-			const float *wp2;       // [F]
-			const float *wv1;       // [F][4]
-			const half_t *wv2;      // value-head dense weights in MFMA A-fragment order [KPAD/32][D/16][lane][8] (value_head_kernel)
-			half_t *vhead_x;        // [batch][KPAD]: the value head's conv1x1 output of every board of the launch, input of value_head_kernel
-			const float *bv2;       // [D]
-			const float *wv3;       // [D][3]
-			float bp2;
-			float bv1[4];
-			float bv3[3];
-			int blocks;
-			int batch;
-			const int *slot_list; // optional: batch element i is slot slot_list[i]
-			const int *count_ptr; // optional: batch size read on the device
-			const float *wq2;     // [F][4] action-values head 1x1 weights (3 outputs, padded), null without the head
-			float bq2[3];
-			float *q;             // action values out: float[slots][HW][2] = (win, draw) per cell, null = head not evaluated
-			half4 *skip;          // single-plane variant only: residual inputs in accumulator layout, [workgroup][wave][MT][NTW][lane]
-	};
-
 #ifdef AGX_NN_PROFILE
 	// profile builds only: shader cycles per phase, waves 0 and 4 of every workgroup
 	__device__ unsigned long long g_nn_prof[2][16];
@@ -234,16 +210,6 @@ namespace
 			static constexpr int SKIP_PER_WG = 8 * MT * NTW * 64;               // half4 elements of residual scratch per workgroup
 	};
 
-	/* A workgroup barrier for hand-offs through LDS only: orders (and waits for) this wave's LDS accesses, not its global stores in flight.
-	 * __syncthreads() is s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier: in the single-plane kernel every wave reaches the layer barrier right
-	 * behind the 2 * NTW global stores of its residual values (read back only by the same lane, a layer later) and would sit there for a
-	 * store round trip, twice per residual block. */
-	__device__ __forceinline__ void lds_barrier()
-	{
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-		__builtin_amdgcn_s_barrier();
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-	}
 	/*
 	 * The two waves of a SIMD (wave w and w + 4: the same channel group, the two position groups) share its MFMA pipe, and the hardware
 	 * issues oldest-first: left alone the older wave runs ahead, reaches the layer barrier early and the younger one finishes ALONE — a
@@ -304,14 +270,6 @@ namespace
 	{
 			half8 a[G::WRING - 1][G::STAGE_TAPS][G::MT]; // the first WRING - 1 stages of the layer
 			const half8 *next;
-	};
-	/* A layer's bias values, requested by the layer in front of it behind its k-loop: requested at the layer's own top — straight behind the
-	 * layer barrier — every wave of the workgroup waits out an L2 round trip there, per channel tile, with nothing to hide it (the
-	 * accumulators start from the bias).  Carried across the epilogue and the barrier only, where the k-loop's weight registers are free. */
-	template<int MT>
-	struct BiasCarry
-	{
-			floatx4 b[MT];
 	};
 	/* The residual input of a block's second layer (single-plane kernels: parked in the workgroup's global scratch), requested by the block's FIRST
 	 * layer behind its k-loop — its accumulator registers are free there — so that the round trips ride through that layer's barrier and plane
@@ -758,18 +716,6 @@ namespace
 			conv3x3_mac_taps<F, ROWS, COLS, ZERO>(src, wpk, wave, lane, acc);
 	}
 
-	__device__ __forceinline__ float half_plus_float_lo(uint32_t packed_halves, float addend)
-	{
-		float d;
-		asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(packed_halves), "v"(addend));
-		return d;
-	}
-	__device__ __forceinline__ float half_plus_float_hi(uint32_t packed_halves, float addend)
-	{
-		float d;
-		asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(packed_halves), "v"(addend));
-		return d;
-	}
 	template<bool TANH>
 	__device__ __forceinline__ float activation(float x)
 	{ // ReLU of the tower / policy head, tanh of the action-values head (blocks.cpp:119-127)
@@ -839,10 +785,7 @@ namespace
 					// exactly like the conversion followed by the add)
 					const uint2 sk = ROW_TILES ? *reinterpret_cast<const uint2*>(skip0 + n * 16 * G::POS_BYTES)
 							: *reinterpret_cast<const uint2*>(dst + plane_offset<G>(pos + 1, ch / 8) + (ch % 8) * 2);
-					v[0] = half_plus_float_lo(sk.x, bv[0]);
-					v[1] = half_plus_float_hi(sk.x, bv[1]);
-					v[2] = half_plus_float_lo(sk.y, bv[2]);
-					v[3] = half_plus_float_hi(sk.y, bv[3]);
+					v = bias_plus_residual(sk, bv);
 				}
 				acc[i][n] = v;
 			}
@@ -975,10 +918,7 @@ namespace
 					if (MODE == 1)
 					{ // bias + (float) residual as one v_fma_mix_f32 per value (conv3x3: h * 1.0 + b rounds once, like the conversion followed by the add)
 						const uint2 sk = (skip_carry != nullptr) ? skip_carry->v[i][n] : __builtin_bit_cast(uint2, my_skip[(i * G::NTW + n) * 64]);
-						v[0] = half_plus_float_lo(sk.x, bv[0]);
-						v[1] = half_plus_float_hi(sk.x, bv[1]);
-						v[2] = half_plus_float_lo(sk.y, bv[2]);
-						v[3] = half_plus_float_hi(sk.y, bv[3]);
+						v = bias_plus_residual(sk, bv);
 					}
 					acc[i][n] = v;
 				}
@@ -1485,29 +1425,6 @@ namespace
 		}
 	}
 
-	__device__ __forceinline__ float block_reduce_max(float v, float *red, int tid)
-	{
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1)
-			v = fmaxf(v, __shfl_xor(v, o));
-		__syncthreads();
-		if ((tid & 63) == 0)
-			red[tid >> 6] = v;
-		__syncthreads();
-		return fmaxf(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7])));
-	}
-	__device__ __forceinline__ float block_reduce_sum(float v, float *red, int tid)
-	{
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1)
-			v += __shfl_xor(v, o);
-		__syncthreads();
-		if ((tid & 63) == 0)
-			red[tid >> 6] = v;
-		__syncthreads();
-		return ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
-	}
-
 	template<int F, int ROWS, int COLS, bool INPLACE, bool QHEAD, bool RAW = false>
 #ifndef AGX_NN_WAVES_PER_EU
 #define AGX_NN_WAVES_PER_EU 2 /* register budget of the tower: 2 = 256 registers per wave (its 8 waves fill a compute unit's register file); 3 = 168, which
@@ -1546,20 +1463,7 @@ namespace
 		const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
 		for (int i = tid; i < G::PLANE_BYTES / 16; i += G::THREADS)
 			reinterpret_cast<uint4*>(plane_x)[i] = zero4;
-		for (int i = tid; i < G::KC * 64; i += G::THREADS)
-		{ // A fragments of the F x 4 value-head conv1x1 (p.wv1 is [F][4] fp32)
-			const int kc = i / 64, l = i % 64, unit = l & 15;
-			half8 f;
-#pragma unroll
-			for (int j = 0; j < 8; j++)
-				f[j] = static_cast<half_t>((unit < 4) ? p.wv1[(kc * 32 + 8 * (l >> 4) + j) * 4 + unit] : 0.0f);
-			s_wv1f[i] = f;
-		}
-		for (int i = tid; i < F; i += G::THREADS)
-			s_wp2[i] = p.wp2[i];
-		if (QHEAD)
-			for (int i = tid; i < F * 4; i += G::THREADS)
-				s_wq2[i] = p.wq2[i];
+		stage_head_weights<F, G::THREADS, QHEAD>(p.wv1, p.wp2, p.wq2, tid, s_wv1f, s_wp2, s_wq2);
 
 #if AGX_NN_PAIR_BALANCE
 		if (tid < 8)
@@ -1589,12 +1493,8 @@ namespace
 				for (int k = 0; k < (RAW ? 1 : 4); k++)
 				{
 					const uint32_t bits = (word >> (8 * k)) & 255u;
-					uint4 v;
-					v.x = ((bits & 1u) ? 0x3C00u : 0u) | ((bits & 2u) ? 0x3C000000u : 0u);
-					v.y = ((bits & 4u) ? 0x3C00u : 0u) | ((bits & 8u) ? 0x3C000000u : 0u);
-					v.z = ((bits & 16u) ? 0x3C00u : 0u) | ((bits & 32u) ? 0x3C000000u : 0u);
-					v.w = ((bits & 64u) ? 0x3C00u : 0u) | ((bits & 128u) ? 0x3C000000u : 0u);
-					if (RAW) // ml::unpackInput into 8 channels (AGNetwork.cpp:249-258): the low byte of the word, 16 bytes per position
+					const uint4 v = unpack_feature_byte(bits);
+					if (RAW) // 8 channels: the low byte of the word, 16 bytes per position
 						*reinterpret_cast<uint4*>(plane_t + q * 16) = v;
 					else
 						*reinterpret_cast<uint4*>(plane_t + (q * 4 + (k ^ ((q >> 2) & 3))) * 16) = v;
@@ -1721,14 +1621,7 @@ namespace
 					if (INPLACE)
 					{
 						const int idx = (c / COLS) * G::S + (c % COLS);
-						constexpr int PS = G::NT * 16; // the channel groups' partial sums, added in a fixed order
-						if constexpr (G::CG == 8)
-							s += ((ppart[idx] + ppart[PS + idx]) + (ppart[2 * PS + idx] + ppart[3 * PS + idx]))
-									+ ((ppart[4 * PS + idx] + ppart[5 * PS + idx]) + (ppart[6 * PS + idx] + ppart[7 * PS + idx]));
-						else if constexpr (G::CG == 4)
-							s += (ppart[idx] + ppart[PS + idx]) + (ppart[2 * PS + idx] + ppart[3 * PS + idx]);
-						else
-							s += ppart[idx] + ppart[PS + idx];
+						s += sum_partial_logits<G::CG, G::NT * 16>(ppart, idx);
 					}
 					else
 					{
@@ -1792,12 +1685,10 @@ namespace
 							}
 						}
 					}
-					const float m = fmaxf(z0, fmaxf(z1, z2));
-					const float e0 = __expf(z0 - m), e1 = __expf(z1 - m), e2 = __expf(z2 - m);
-					const float inv = 1.0f / (e0 + e1 + e2);
+					const float2 win_draw = softmax3_win_draw(z0, z1, z2);
 					float *out = p.q + (static_cast<size_t>(b) * G::HW + c) * 2;
-					out[0] = e0 * inv; // win
-					out[1] = e1 * inv; // draw
+					out[0] = win_draw.x;
+					out[1] = win_draw.y;
 				}
 			}
 			AGX_NN_MARK(8);
@@ -1808,12 +1699,13 @@ namespace
 	 * Value head behind the tower, for every board of a launch: hidden = ReLU(W2^T x + b2) (4 HW -> D), out = softmax(W3^T hidden + b3)
 	 * (createValueHead, blocks.cpp:108-118).  One workgroup = 16 boards (one MFMA position tile) x all D hidden units: wave w owns the
 	 * 16-unit tiles w * D/64 .. and walks K in 32-input steps (weights pre-packed in A-fragment order, the boards' inputs are rows of
-	 * KPAD halves).  3.1 GFLOP for a whole self-play batch — microseconds.
+	 * kpad halves: AgxNet::kpad()).  3.1 GFLOP for a whole self-play batch — microseconds.  The one kernel behind every tower, the
+	 * run-time-shaped one included: the input length is an argument.
 	 */
-	template<int KPAD, int D>
+	template<int D>
 	__global__ __launch_bounds__(256) void value_head_kernel(const half_t *__restrict__ x, const half8 *__restrict__ w2, const float *__restrict__ b2,
 			const float *__restrict__ w3, float b30, float b31, float b32, const int *__restrict__ slot_list, const int *__restrict__ count_ptr, int batch_cap,
-			float *__restrict__ value)
+			int kpad, float *__restrict__ value)
 	{
 		constexpr int MTW = D / 64; // 16-unit tiles per wave
 		__shared__ float hid[16][D + 1];
@@ -1827,10 +1719,10 @@ namespace
 #pragma unroll
 		for (int i = 0; i < MTW; i++)
 			acc[i] = floatx4 { 0.0f, 0.0f, 0.0f, 0.0f };
-		const half8 *xb = reinterpret_cast<const half8*>(x + static_cast<size_t>(board) * KPAD) + q4;
+		const half8 *xb = reinterpret_cast<const half8*>(x + static_cast<size_t>(board) * kpad) + q4;
 		const half8 *wp = w2 + (wave * MTW) * 64 + lane;
-#pragma unroll 4
-		for (int kc = 0; kc < KPAD / 32; kc++)
+		const int ksteps = kpad / 32;
+		for (int kc = 0; kc < ksteps; kc++)
 		{
 			const half8 bfrag = xb[kc * 4];
 #pragma unroll
@@ -1982,6 +1874,7 @@ struct AgxNet
 		float bv3[3] = { 0, 0, 0 };
 		int num_cus = 256;
 		int launch_width = 0; // 0 = every CU
+		int kpad() const { return (desc.rows * desc.cols * 4 + 31) / 32 * 32; } // value-head dense input length: 4 HW padded to whole MFMA k-steps
 };
 
 namespace
@@ -2107,7 +2000,7 @@ int agx_net_load_weights(AgxNet *net, const float *h_blob, size_t n_floats)
 	for (int i = 0; i < 4; i++)
 		net->bv1[i] = *ptr++;
 	{ // dense 4 HW -> D in MFMA A-fragment order [k-step][16-unit tile][lane][8] (value_head_kernel), zero beyond the last input
-		const int kpad = (HW * 4 + 31) / 32 * 32, mtiles = D / 16;
+		const int kpad = net->kpad(), mtiles = D / 16;
 		wv2.assign(static_cast<size_t>(kpad) * D, static_cast<half_t>(0.0f));
 		for (int kc = 0; kc < kpad / 32; kc++)
 			for (int mt = 0; mt < mtiles; mt++)
@@ -2208,7 +2101,7 @@ static int launch_forward(AgxNet *net, const uint32_t *d_features, const int *d_
 	const int grid = (batch < width) ? batch : width;
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	p.skip = nullptr;
-	const int kpad = (net->desc.rows * net->desc.cols * 4 + 31) / 32 * 32;
+	const int kpad = net->kpad();
 	{ // per-stream scratch: launches on one stream are ordered and share it, launches on different streams may overlap
 		std::lock_guard<std::mutex> lock(net->skip_mutex);
 		AgxNet::StreamScratch *mine = nullptr;
@@ -2238,43 +2131,18 @@ static int launch_forward(AgxNet *net, const uint32_t *d_features, const int *d_
 		p.skip = static_cast<half4*>(mine->skip);
 		p.vhead_x = static_cast<half_t*>(mine->vhead);
 	}
-	if (net->any_board)
-	{
-		agx_any::Params a;
-		a.w_in = p.w_in;
-		a.w_tower = p.w_tower;
-		a.bias = p.bias;
-		a.wp2 = p.wp2;
-		a.wv1 = p.wv1;
-		a.wv2 = p.wv2;
-		a.vhead_x = p.vhead_x;
-		a.bv2 = p.bv2;
-		a.wv3 = p.wv3;
-		a.bp2 = p.bp2;
-		for (int i = 0; i < 4; i++)
-			a.bv1[i] = p.bv1[i];
-		for (int i = 0; i < 3; i++)
-		{
-			a.bv3[i] = p.bv3[i];
-			a.bq2[i] = p.bq2[i];
-		}
-		a.blocks = p.blocks;
-		a.batch = p.batch;
-		a.slot_list = p.slot_list;
-		a.count_ptr = p.count_ptr;
-		a.wq2 = p.wq2;
-		a.q = p.q;
-		a.skip = p.skip;
-		a.rows = net->desc.rows;
-		a.cols = net->desc.cols;
-		return agx_any::launch(a, net->desc.filters, net->desc.in_channels == 8, grid, d_features, d_policy, d_value, s);
-	}
 	const bool big = (net->desc.rows == 20 && net->desc.cols == 20), wide = (net->desc.filters == 128), qhead = (p.q != nullptr), raw = (net->desc.in_channels == 8);
 	const dim3 g(grid), t(512);
 #define AGX_LAUNCH_TOWER(FF, NN, IP, QH, RW) hipLaunchKernelGGL((nn_tower_kernel<FF, NN, NN, IP, QH, RW>), g, t, 0, s, p, d_features, d_policy, d_value)
 #define AGX_LAUNCH_HEADS(FF, NN, IP) do { if (qhead) AGX_LAUNCH_TOWER(FF, NN, IP, true, false); else if (raw) AGX_LAUNCH_TOWER(FF, NN, IP, false, true); \
 		else AGX_LAUNCH_TOWER(FF, NN, IP, false, false); } while (0)
-	if (net->inplace)
+	if (net->any_board)
+	{
+		const int status = agx_any::launch(p, net->desc.rows, net->desc.cols, net->desc.filters, raw, grid, kpad, d_features, d_policy, s);
+		if (status != AGX_OK)
+			return status;
+	}
+	else if (net->inplace)
 	{
 		if (big && wide)
 			AGX_LAUNCH_HEADS(128, 20, true);
@@ -2291,18 +2159,14 @@ static int launch_forward(AgxNet *net, const uint32_t *d_features, const int *d_
 		AGX_LAUNCH_HEADS(64, 15, false);
 #undef AGX_LAUNCH_HEADS
 #undef AGX_LAUNCH_TOWER
-	{ // the value head's dense layers for all boards of the launch
+	{ // the value head's dense layers for all boards of the launch, behind whichever tower ran
 		const dim3 vg((batch + 15) / 16), vt(256);
-#define AGX_LAUNCH_VALUE(KP, DD) hipLaunchKernelGGL((value_head_kernel<KP, DD>), vg, vt, 0, s, p.vhead_x, reinterpret_cast<const half8*>(p.wv2), p.bv2, p.wv3, \
-		p.bv3[0], p.bv3[1], p.bv3[2], d_slot_list, d_count, batch, d_value)
-		if (big && wide)
-			AGX_LAUNCH_VALUE(1600, 256);
-		else if (big)
-			AGX_LAUNCH_VALUE(1600, 128);
-		else if (wide)
-			AGX_LAUNCH_VALUE(928, 256);
+#define AGX_LAUNCH_VALUE(DD) hipLaunchKernelGGL((value_head_kernel<DD>), vg, vt, 0, s, p.vhead_x, reinterpret_cast<const half8*>(p.wv2), p.bv2, p.wv3, \
+		p.bv3[0], p.bv3[1], p.bv3[2], d_slot_list, d_count, batch, kpad, d_value)
+		if (wide)
+			AGX_LAUNCH_VALUE(256);
 		else
-			AGX_LAUNCH_VALUE(928, 128);
+			AGX_LAUNCH_VALUE(128);
 #undef AGX_LAUNCH_VALUE
 	}
 	AGX_HIP_CHECK(hipGetLastError());

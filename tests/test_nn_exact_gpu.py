@@ -64,7 +64,7 @@ def test_parametrisation_covers_the_dispatch_table(agx_lib):
 
 @pytest.mark.parametrize("rows,single,filters,kind,blocks,heads,seed", nx.network_cases())
 def test_tower_instantiation_is_exact(agx_lib, monkeypatch, rows, single, filters, kind, blocks, heads, seed):
-    """all 18 instantiations of nn_tower_kernel (and so the four value_head_kernels), at 0 blocks (input conv and heads alone), 1 block
+    """all 18 instantiations of nn_tower_kernel (and so the two value_head_kernels), at 0 blocks (input conv and heads alone), 1 block
     (first = last) and 10 blocks, random and transparent heads, random and directed boards"""
     monkeypatch.setenv("AGX_NN_SINGLE_PLANE", single)
     desc, blob = nx.cached_weights(rows, filters, kind, blocks, heads, seed)
