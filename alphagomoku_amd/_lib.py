@@ -353,3 +353,12 @@ def _declare(c):  # noqa: F811
     c.agx_position_evaluator_encode.argtypes = [vp, ci, vp, vp, ci, vp, vp, vp]
     c.agx_position_evaluator_combine.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, outputs, vp]
     c.agx_position_evaluator_evaluate.argtypes = [vp, vp, ci, vp, vp, ci, ci, ci, outputs, vp]
+
+
+_declare_position = _declare
+
+
+def _declare(c):  # noqa: F811
+    _declare_position(c)
+    vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    c.agx_head_loss_grad.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, vp, vp, vp, vp, vp, vp]

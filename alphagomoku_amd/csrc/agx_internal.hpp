@@ -19,6 +19,10 @@ namespace agx
 	{
 			hipError_t code;
 	};
+
+	/* net_score.hip: one launch of one workgroup on `stream` that adds the n records of d_scores into *d_total in sample order (the ordered
+	 * reduction behind agx_net_score_outputs); checks hipGetLastError, so a caller's launch just before it is covered too */
+	int add_sample_scores(int n, AgxSampleScore *d_scores, AgxNetScore *d_total, hipStream_t stream);
 }
 
 #define AGX_HIP_CHECK(expr)                                                                         \

@@ -230,6 +230,18 @@ namespace agx
 				}
 		};
 	}
+
+	/* agx_internal.hpp: k_score_reduce for the other files that write per-sample records (head_loss.hip) */
+	int add_sample_scores(int n, AgxSampleScore *d_scores, AgxNetScore *d_total, hipStream_t stream)
+	{
+		ScoreArgs A { };
+		A.n = n;
+		A.scores = d_scores;
+		A.total = d_total;
+		hipLaunchKernelGGL(k_score_reduce, dim3(1), dim3(64), 0, stream, A);
+		AGX_HIP_CHECK(hipGetLastError());
+		return AGX_OK;
+	}
 }
 
 extern "C" {

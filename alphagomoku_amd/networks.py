@@ -49,6 +49,14 @@ class AGNetwork:
         blob = np.ascontiguousarray(blob, dtype=np.float32)
         check(lib.agx_net_load_weights(self._net, blob.ctypes.data_as(ctypes.c_void_p), blob.size))
 
+    def load_module(self, module):
+        """loadWeights(training.export_blob(module)): a training.TowerModule of this network's description, its batch norms folded with their
+        running statistics"""
+        from .training import export_blob
+        if {k: module.desc.get(k, 0) for k in self.desc} != {k: self.desc.get(k, 0) for k in self.desc}:
+            raise ValueError("load_module: the module's description %s is not the network's %s" % (module.desc, self.desc))
+        self.loadWeights(export_blob(module))
+
     def forwardDevice(self, d_features, batch, d_policy, d_value, stream=None, d_action_values=None):
         if d_action_values is None:
             check(lib.agx_nn_forward(self._net, d_features, batch, d_policy, d_value, stream))

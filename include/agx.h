@@ -682,6 +682,38 @@ int agx_net_score_outputs(int rows, int cols, int n, const float* d_policy, cons
 int agx_net_score_dataset(AgxNet* net, AgxDataset* dataset, int n, const AgxDatasetSample* h_samples, int chunk, AgxNetScore* h_out, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Training: the loss of the three heads and its gradients with respect to the LOGITS, on the device (csrc/head_loss.hip).
+ * The last layer of a training step: a torch module (alphagomoku_amd/training.py: TowerModule) produces pre-softmax outputs from the tensors
+ * agx_dataset_load_batch writes, this call turns them into the losses agx_net_score_* reports and into dL/dlogits, torch's autograd and
+ * optimiser do the rest.  The reference trains with MinML's graph (networks.cpp:89 graph.setOptimizer(ml::RAdam())); its loss code is not
+ * in the reference tree, so the formulas are this project's own: the cross-entropies above in their log-sum-exp form.  Per sample and head
+ * (policy over the board's cells, value over its 3 outputs, action values over the 3 classes of every cell on its own), with logits z:
+ *   m = max z;  e_i = expf(z_i - m);  S = sum of e_i in float64 (per lane in cell order, then a fixed butterfly);  lse = m + logf((float) S)
+ *   loss       = sum over the entries with target t > 0 of the float32 product t * (lse - z_i), added in float64.  A probability that
+ *                underflows costs t * (lse - z), where agx_net_score_outputs floors it at FLT_MIN.
+ *   gradient_i = scale * (p_i * T - t_i) with p_i = e_i / (float) S, T = the float32 of the float64 sum of the positive targets, and t_i
+ *                counted as 0 unless it is > 0.  Written for EVERY element: the buffers need no clearing.
+ *   q_ce, q_cells, d_q_grad: only the cells whose POLICY target is > 0 count (the mask of agx_net_score_outputs); on every other cell the
+ *                gradient is exactly 0.0f and neither its logits nor its targets are read — the targets there are filler, a NaN among them
+ *                reaches neither a loss nor a gradient.
+ * Non-finite logits propagate, nothing is clamped.  d_sample_scores[n] receives the records (topk_hit and reserved written as 0), which
+ * are added to *d_total in sample order by the reduction of agx_net_score_outputs: totals are bit-identical however a set of samples is
+ * split into calls and wherever the launches run.  Two launches on `stream`, nothing synchronised.  d_q_logits / d_q_target: both or
+ * neither; the gradients: one for every head that has logits, or all three NULL (losses only).  Boards 5..20 x 5..20.
+ * AGX_ERR_INVALID before anything is launched otherwise. */
+int agx_head_loss_grad(int rows, int cols, int n,
+		const float* d_policy_logits,  /* [n][rows*cols], pre-softmax */
+		const float* d_value_logits,   /* [n][3] */
+		const float* d_q_logits,       /* [n][rows*cols][3] or NULL */
+		const float* d_policy_target, const float* d_value_target,
+		const float* d_q_target,       /* layouts of agx_dataset_load_batch; NULL exactly when d_q_logits is */
+		float policy_scale, float value_scale, float q_scale,
+		float* d_policy_grad, float* d_value_grad, float* d_q_grad,  /* same shapes as the logits; all three NULL = losses only */
+		AgxSampleScore* d_sample_scores, /* [n], required */
+		AgxNetScore* d_total,            /* added to, like agx_net_score_outputs */
+		void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Positions evaluated on the device: boards -> policy, value, best moves (csrc/position_eval.hip).
  * The primary entry point of the reference's network is AGNetwork::packInputData(index, board, signToMove) (AGNetwork.hpp:60), which encodes
  * the board on the host; agx_nn_forward takes feature words.  A position evaluator closes the gap for callers that hold boards and no

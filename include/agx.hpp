@@ -531,6 +531,16 @@ namespace agx
 			}
 	};
 
+	/* The training loss of the three heads and dL/dlogits in one call (agx.h: agx_head_loss_grad; device pointers, enqueued on `stream`, nothing
+	 * synchronised).  The records of the n samples are added to *d_total in sample order; read it back into a NetScore for the means. */
+	inline void head_loss_grad(int rows, int cols, int n, const float *d_policy_logits, const float *d_value_logits, const float *d_q_logits,
+			const float *d_policy_target, const float *d_value_target, const float *d_q_target, float policy_scale, float value_scale, float q_scale,
+			float *d_policy_grad, float *d_value_grad, float *d_q_grad, AgxSampleScore *d_sample_scores, AgxNetScore *d_total, void *stream = nullptr)
+	{
+		check(agx_head_loss_grad(rows, cols, n, d_policy_logits, d_value_logits, d_q_logits, d_policy_target, d_value_target, d_q_target, policy_scale,
+				value_scale, q_scale, d_policy_grad, d_value_grad, d_q_grad, d_sample_scores, d_total, stream));
+	}
+
 	/* The consumer of the record sink: format-201 games -> training tensors on the device (agx.h: agx_dataset_*; what the reference's
 	 * dataset/torch_api.h reader does on one host thread).  Fragments are numbered like Dataset::load(i, path). */
 	class TrainingDataset
