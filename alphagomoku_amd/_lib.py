@@ -362,3 +362,23 @@ def _declare(c):  # noqa: F811
     _declare_position(c)
     vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     c.agx_head_loss_grad.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, vp, vp, vp, vp, vp, vp]
+
+
+class AgxSolvedPositions(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ["score", "flags", "n_actions", "moves", "move_scores", "nodes", "value", "status"]]
+
+
+POSSOLVE_STATUS_BAD_INPUT, POSSOLVE_STATUS_SOLVER_ERROR = 1, 2
+
+_declare_loss = _declare
+
+
+def _declare(c):  # noqa: F811
+    _declare_loss(c)
+    vp, ci, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64
+    solved = ctypes.POINTER(AgxSolvedPositions)
+    c.agx_position_solver_create.argtypes = [ci, ci, ci, ci, u64, u64, ctypes.POINTER(vp)]
+    c.agx_position_solver_solve.argtypes = [vp, ci, vp, vp, solved, vp]
+    c.agx_position_solver_destroy.argtypes = [vp]
+    c.agx_position_solver_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    c.agx_position_evaluator_evaluate_solved.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, ci, ctypes.POINTER(AgxPositionOutputs), solved, vp]

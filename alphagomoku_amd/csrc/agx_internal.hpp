@@ -23,6 +23,12 @@ namespace agx
 	/* net_score.hip: one launch of one workgroup on `stream` that adds the n records of d_scores into *d_total in sample order (the ordered
 	 * reduction behind agx_net_score_outputs); checks hipGetLastError, so a caller's launch just before it is covered too */
 	int add_sample_scores(int n, AgxSampleScore *d_scores, AgxNetScore *d_total, hipStream_t stream);
+
+	/* engine.hip, for agx_position_evaluator_evaluate_solved (position_eval.hip): what a position solver was created for and its device
+	 * workspace [capacity] (score, n_actions, moves, move_scores, status; the other members null) ... */
+	int position_solver_describe(AgxPositionSolver *solver, int *rules, int *board_size, int *capacity, AgxSolvedPositions *workspace);
+	/* ... and "the work enqueued on `stream` so far still reads the solver's workspace": the solver's next call on another stream waits for it */
+	int position_solver_mark(AgxPositionSolver *solver, hipStream_t stream);
 }
 
 #define AGX_HIP_CHECK(expr)                                                                         \

@@ -3186,6 +3186,113 @@ namespace
 			gs.nn_queued = 0;
 		}
 	}
+	/* ------------------------------------------------------------------------------------------------------------ */
+	/*
+	 * k_solve_positions — the threat solver on a batch of boards (agx_position_solver_solve): every position as a fresh AlphaBetaSearch with an
+	 * empty table would solve it.  One wavefront per position, grid-stride: wave w owns table w, spill area w, task w and game record w of a
+	 * minimal EngineDev (tt_mod = the wave count), clears its table, loads the position into its task and runs solve_task on it — the loop
+	 * around solver_run / solver_place is that function's.  Nothing is shared between waves: no atomics, no waiting; a solve ends by its node
+	 * budget and solve_task's depth loop.
+	 */
+	struct SolvePositionsArgs
+	{
+			const uint8_t *boards; // [n][hw] 0 empty, 1 cross, 2 circle
+			const uint8_t *signs;  // [n] 1 cross, 2 circle
+			int n;
+			AgxSolvedPositions out; // each may be null
+	};
+	template<bool RENJU, int NFIX>
+	__global__ __launch_bounds__(64, AGX_SOLVE_WAVES) void k_solve_positions(EngineDev E, SolvePositionsArgs A)
+	{
+		if (NFIX != 0)
+		{
+			E.n = NFIX;
+			E.hw = NFIX * NFIX;
+		}
+		typedef SolverSharedT<(NFIX != 0) ? NFIX : MAXN> SH;
+		__shared__ SH sh;
+		const int w = blockIdx.x, lane = threadIdx.x, hw = E.hw;
+		DTask &t = E.tasks[w];
+		GameState &gs = E.games[w];
+		ulonglong2 *tt = reinterpret_cast<ulonglong2*>(E.tt + static_cast<size_t>(w) * (E.tt_bucket_mask + 1ull) * 8ull);
+		const size_t entries = (E.tt_bucket_mask + 1ull) * 4ull;
+		solver_load_threat_table(sh, E, lane);
+		for (int p = w; p < A.n; p += gridDim.x)
+		{
+			const uint8_t *src = A.boards + static_cast<size_t>(p) * hw;
+			const int sign = A.signs[p];
+			bool bad = false;
+			for (int i = lane; i < hw; i += 64)
+			{
+				const uint8_t v = src[i];
+				bad |= (v > 2);
+				t.board[i] = v;
+			}
+			// not a position: nothing of it reaches the solver, whose tables are indexed by cell values (the rule of k_encode_positions)
+			const bool refused = __ballot(bad) != 0ull || (sign != 1 && sign != 2);
+			int status = AGX_POSSOLVE_STATUS_BAD_INPUT, size = 0;
+			uint32_t score = 0, flags = 0, nodes = 0;
+			if (!refused)
+			{
+				ulonglong2 empty;
+				empty.x = 0ull;
+				empty.y = tt_pack(0, 0, s_unknown(0), 0);
+				for (size_t i = lane; i < entries; i += 64)
+					tt[i] = empty;
+				if (lane == 0)
+				{ // one fresh leaf, as k_debug_load_tasks makes it
+					t.path_len = 1;
+					t.final_node = -1;
+					t.n_edges = 0;
+					t.flags = 0;
+					t.sign_to_move = sign;
+					t.score = s_unknown(0);
+					t.win = t.draw = t.moves_left = 0.0f;
+					t.needs_nn = 0;
+					gs.error = 0;
+				}
+				__threadfence(); // the board, the task and the empty table are read back by other lanes
+				wave_sync();
+				unsigned long long solver_nodes = 0;
+				solve_task<RENJU>(sh, E, w, t, w, 0, lane, solver_nodes, w);
+				__threadfence(); // lane 0 wrote the task's words and the game's error
+				wave_sync();
+				size = __builtin_amdgcn_readfirstlane(t.n_edges);
+				score = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(t.score)));
+				flags = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(t.flags)));
+				nodes = static_cast<uint32_t>(solver_nodes);
+				status = (__builtin_amdgcn_readfirstlane(gs.error) != 0) ? AGX_POSSOLVE_STATUS_SOLVER_ERROR : 0;
+			}
+			for (int i = lane; i < hw; i += 64)
+			{ // the whole row, zeros behind the list: the outputs are a function of the position alone
+				if (A.out.moves != nullptr)
+					A.out.moves[static_cast<size_t>(p) * hw + i] = (i < size) ? t.emove[i] : static_cast<uint16_t>(0);
+				if (A.out.move_scores != nullptr)
+					A.out.move_scores[static_cast<size_t>(p) * hw + i] = (i < size) ? t.escore[i] : static_cast<uint16_t>(0);
+			}
+			if (lane < 3 && A.out.value != nullptr)
+			{ // Score::convertToValue of a proven score as (win, draw, loss)
+				const int pv = s_pv(score);
+				const bool proven = !refused && s_proven(score);
+				A.out.value[static_cast<size_t>(p) * 3 + lane] = (proven && pv == ((lane == 0) ? 3 : ((lane == 1) ? 1 : 0))) ? 1.0f : 0.0f;
+			}
+			if (lane == 0)
+			{
+				if (A.out.score != nullptr)
+					A.out.score[p] = static_cast<uint16_t>(score);
+				if (A.out.flags != nullptr)
+					A.out.flags[p] = flags;
+				if (A.out.n_actions != nullptr)
+					A.out.n_actions[p] = size;
+				if (A.out.nodes != nullptr)
+					A.out.nodes[p] = nodes;
+				if (A.out.status != nullptr)
+					A.out.status[p] = status;
+			}
+			wave_sync(); // the next position reuses the task and the LDS state
+		}
+	}
+
 	__global__ __launch_bounds__(64) void k_debug_pattern_state(EngineDev E, const uint8_t *boards, const int *signs, const uint16_t *moves, int n_moves,
 			uint8_t *ptypes, uint8_t *threats, int16_t *lists, int lists_stride)
 	{
@@ -5210,6 +5317,235 @@ int agx_host_tables(int rules, uint8_t *h_pattern, uint8_t *h_half_open_three, u
 		std::memcpy(h_threat, t.threat.data(), t.threat.size());
 	if (h_defense != nullptr)
 		std::memcpy(h_defense, t.defense.data(), t.defense.size() * sizeof(uint16_t));
+	return AGX_OK;
+}
+
+} /* extern "C" */
+
+/* ================================================================================================================ */
+/* agx_position_solver_*: the threat solver on boards (k_solve_positions) */
+struct AgxPositionSolver
+{
+		int rules = 0, n = 0, capacity = 0, waves = 0;
+		int device = -1;
+		std::mutex mutex;
+		EngineDev dev; // only what solve_task reads: tables, limits, the per-wave areas, a task and a game record per wave
+		std::vector<void*> allocations;
+		unsigned long long device_bytes = 0, bytes_per_wave = 0;
+		AgxSolvedPositions workspace; // [capacity] outputs of agx_position_evaluator_evaluate_solved the caller did not ask for
+		// the waves of two launches share the per-wave areas: a call on another stream than the previous one is ordered behind it on the device
+		hipEvent_t done = nullptr;
+		hipStream_t last_stream = nullptr;
+		bool launched = false;
+};
+
+namespace
+{
+	typedef void (*SolvePositionsKernel)(EngineDev, SolvePositionsArgs);
+	SolvePositionsKernel solve_positions_kernel(int rules, int n)
+	{
+#ifdef AGX_QUICK
+		(void) rules;
+		(void) n;
+		return k_solve_positions<AGX_QUICK_RENJU, 15>;
+#else
+		if (rules == AGX_RENJU)
+			return (n == 15) ? k_solve_positions<true, 15> : k_solve_positions<true, 0>;
+		if (n == 15)
+			return k_solve_positions<false, 15>;
+		return (n == 20) ? k_solve_positions<false, 20> : k_solve_positions<false, 0>;
+#endif
+	}
+	template<typename T>
+	int solver_alloc(AgxPositionSolver *ps, T **ptr, size_t count, bool per_wave)
+	{
+		const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+		void *p = nullptr;
+		const hipError_t err = hipMalloc(&p, bytes);
+		if (err != hipSuccess)
+		{
+			(void) hipGetLastError();
+			agx::set_error("agx_position_solver_create: hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(err));
+			return AGX_ERR_HIP;
+		}
+		ps->allocations.push_back(p);
+		ps->device_bytes += bytes;
+		if (per_wave)
+			ps->bytes_per_wave += bytes / static_cast<size_t>(ps->waves);
+		*ptr = static_cast<T*>(p);
+		return AGX_OK;
+	}
+	template<typename T>
+	int solver_upload(AgxPositionSolver *ps, const T **ptr, const std::vector<T> &src)
+	{
+		T *p = nullptr;
+		const int st = solver_alloc(ps, &p, src.size(), false);
+		if (st != AGX_OK)
+			return st;
+		AGX_HIP_CHECK(hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+		*ptr = p;
+		return AGX_OK;
+	}
+}
+
+int agx::position_solver_describe(AgxPositionSolver *ps, int *rules, int *board_size, int *capacity, AgxSolvedPositions *workspace)
+{
+	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "null position solver");
+	*rules = ps->rules;
+	*board_size = ps->n;
+	*capacity = ps->capacity;
+	*workspace = ps->workspace;
+	return AGX_OK;
+}
+int agx::position_solver_mark(AgxPositionSolver *ps, hipStream_t stream)
+{
+	std::lock_guard<std::mutex> lock(ps->mutex);
+	AGX_HIP_CHECK(hipEventRecord(ps->done, stream));
+	ps->launched = true;
+	ps->last_stream = stream;
+	return AGX_OK;
+}
+
+extern "C" {
+
+int agx_position_solver_create(int rules, int board_size, int capacity, int max_positions, uint64_t table_entries, uint64_t zobrist_seed, AgxPositionSolver **out)
+{
+	AGX_REQUIRE(out != nullptr, AGX_ERR_INVALID, "agx_position_solver_create: null argument");
+	*out = nullptr;
+	AGX_REQUIRE(rules >= 0 && rules <= AGX_CARO6, AGX_ERR_INVALID, "agx_position_solver_create: unknown rules %d", rules);
+	AGX_REQUIRE(board_size >= 5 && board_size <= MAXN, AGX_ERR_UNSUPPORTED, "agx_position_solver_create: board size %d not in [5, %d]", board_size, MAXN);
+	AGX_REQUIRE(capacity > 0 && capacity <= (1 << 20), AGX_ERR_INVALID, "agx_position_solver_create: capacity %d", capacity);
+	AGX_REQUIRE(max_positions >= 1 && max_positions <= 1000, AGX_ERR_UNSUPPORTED, "agx_position_solver_create: max_positions must be in [1, 1000]");
+	AGX_REQUIRE(table_entries <= (1ull << 32), AGX_ERR_INVALID, "agx_position_solver_create: %llu table entries per wave (at most 2^32)",
+			static_cast<unsigned long long>(table_entries));
+	AgxPositionSolver *ps = new AgxPositionSolver();
+	ps->rules = rules;
+	ps->n = board_size;
+	ps->capacity = capacity;
+	std::memset(&ps->workspace, 0, sizeof(ps->workspace));
+	EngineDev &d = ps->dev;
+	std::memset(&d, 0, sizeof(d));
+	int status = AGX_OK, cus = 0;
+	if (hipGetDevice(&ps->device) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ps->device) != hipSuccess)
+	{
+		(void) hipGetLastError();
+		agx::set_error("agx_position_solver_create: no HIP device");
+		status = AGX_ERR_HIP;
+	}
+	// one wave per SIMD: k_solve_positions is compiled like k_solve, for the fastest single wave (uncapped registers), and every wave brings
+	// a table and spill areas of its own
+	ps->waves = std::min(capacity, 4 * std::max(1, cus));
+	if (const char *cap = std::getenv("AGX_POSSOLVE_MAX_WAVES"))
+		if (std::atoi(cap) > 0)
+			ps->waves = std::min(ps->waves, std::atoi(cap));
+	d.rules = rules;
+	d.n = board_size;
+	d.hw = board_size * board_size;
+	d.draw_after = d.hw;
+	d.n_games = ps->waves;
+	d.batch = d.batch_limit = 1;
+	d.tss_max_nodes = max_positions;
+	d.tss_max_depth = 100;
+	d.solve_time_ticks = 0ull;
+	d.zobrist_seed = zobrist_seed;
+	const size_t buckets = round_pow2(std::max<size_t>(table_entries, 4)) / 4;
+	d.tt_bucket_mask = buckets - 1;
+	d.act_cap = d.hw * (d.hw + 1) / 2 + 64;
+	d.tt_mod = ps->waves;
+	const size_t W = ps->waves, hw = d.hw, C = capacity;
+	HostTables tables;
+	build_host_tables(rules, tables);
+	std::vector<uint8_t> packed(4096); // cross type | circle type << 4 (dev_solver.hpp: threat_lookup)
+	for (int i = 0; i < 4096; i++)
+		packed[i] = static_cast<uint8_t>((tables.threat[2 * i] & 15u) | ((tables.threat[2 * i + 1] & 15u) << 4));
+#define AGX_TRY(expr) if (status == AGX_OK) status = (expr)
+	AGX_TRY(solver_alloc(ps, &d.tt, W * buckets * 8, true));
+	AGX_TRY(solver_alloc(ps, &d.act, W * d.act_cap, true));
+	AGX_TRY(solver_alloc(ps, &d.list_spill, W * 20 * static_cast<size_t>(MAXHW), true));
+	AGX_TRY(solver_alloc(ps, &d.frame_spill, W * MAX_FRAMES, true));
+	AGX_TRY(solver_alloc(ps, &d.snap_spill, W * (hw + 2) * 64, true)); // one undo-snapshot level per stone on the board, whatever the rules
+	AGX_TRY(solver_alloc(ps, &d.tasks, W, true));
+	AGX_TRY(solver_alloc(ps, &d.games, W, true));
+	AGX_TRY(solver_alloc(ps, &d.nn_features, W * hw, true)); // solve_task encodes the network input of its task on the way
+	AGX_TRY(solver_upload(ps, &d.t_pattern, tables.pattern));
+	AGX_TRY(solver_upload(ps, &d.t_ho3, tables.half_open_three));
+	AGX_TRY(solver_upload(ps, &d.t_threat, tables.threat));
+	AGX_TRY(solver_upload(ps, &d.t_threat_packed, packed));
+	AGX_TRY(solver_upload(ps, &d.t_defense, tables.defense));
+	AGX_TRY(solver_alloc(ps, &ps->workspace.score, C, false));
+	AGX_TRY(solver_alloc(ps, &ps->workspace.n_actions, C, false));
+	AGX_TRY(solver_alloc(ps, &ps->workspace.moves, C * hw, false));
+	AGX_TRY(solver_alloc(ps, &ps->workspace.move_scores, C * hw, false));
+	AGX_TRY(solver_alloc(ps, &ps->workspace.status, C, false));
+#undef AGX_TRY
+	if (status == AGX_OK && (hipMemset(d.games, 0, W * sizeof(GameState)) != hipSuccess || hipMemset(d.tasks, 0, W * sizeof(DTask)) != hipSuccess
+			|| hipEventCreateWithFlags(&ps->done, hipEventDisableTiming) != hipSuccess))
+	{
+		agx::set_error("agx_position_solver_create: clearing the per-wave records failed");
+		status = AGX_ERR_HIP;
+	}
+	if (status != AGX_OK)
+	{ // one way out for every failure: what was allocated is freed, *out stays null
+		const std::string message = agx_last_error();
+		agx_position_solver_destroy(ps);
+		agx::set_error("%s", message.c_str());
+		return status;
+	}
+	*out = ps;
+	return AGX_OK;
+}
+
+int agx_position_solver_destroy(AgxPositionSolver *ps)
+{
+	if (ps == nullptr)
+		return AGX_OK;
+	if (ps->launched)
+		(void) hipEventSynchronize(ps->done);
+	for (void *p : ps->allocations)
+		(void) hipFree(p);
+	if (ps->done != nullptr)
+		(void) hipEventDestroy(ps->done);
+	delete ps;
+	return AGX_OK;
+}
+
+int agx_position_solver_info(const AgxPositionSolver *ps, int *waves, uint64_t *bytes_per_wave, uint64_t *device_bytes)
+{
+	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "agx_position_solver_info: null solver");
+	if (waves != nullptr)
+		*waves = ps->waves;
+	if (bytes_per_wave != nullptr)
+		*bytes_per_wave = ps->bytes_per_wave;
+	if (device_bytes != nullptr)
+		*device_bytes = ps->device_bytes;
+	return AGX_OK;
+}
+
+int agx_position_solver_solve(AgxPositionSolver *ps, int n, const uint8_t *d_boards, const uint8_t *d_signs, const AgxSolvedPositions *out, void *stream_)
+{
+	AGX_REQUIRE(ps != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_position_solver_solve: null argument");
+	AGX_REQUIRE(n >= 0 && n <= ps->capacity, AGX_ERR_INVALID, "agx_position_solver_solve: %d positions, the solver was created for %d", n, ps->capacity);
+	if (n == 0)
+		return AGX_OK;
+	AGX_REQUIRE(d_boards != nullptr && d_signs != nullptr, AGX_ERR_INVALID, "agx_position_solver_solve: null boards or signs");
+	hipStream_t stream = static_cast<hipStream_t>(stream_);
+	std::lock_guard<std::mutex> lock(ps->mutex);
+	int current = -1;
+	AGX_HIP_CHECK(hipGetDevice(&current));
+	AGX_REQUIRE(current == ps->device, AGX_ERR_STATE, "agx_position_solver_solve: the solver lives on device %d, the calling thread's current device is %d", ps->device, current);
+	if (ps->launched && ps->last_stream != stream)
+		AGX_HIP_CHECK(hipStreamWaitEvent(stream, ps->done, 0));
+	SolvePositionsArgs A;
+	A.boards = d_boards;
+	A.signs = d_signs;
+	A.n = n;
+	A.out = *out;
+	hipLaunchKernelGGL(solve_positions_kernel(ps->rules, ps->n), dim3(std::min(n, ps->waves)), dim3(64), 0, stream, ps->dev, A);
+	const hipError_t launched = hipGetLastError();
+	AGX_HIP_CHECK(hipEventRecord(ps->done, stream));
+	ps->launched = true;
+	ps->last_stream = stream;
+	AGX_HIP_CHECK(launched);
 	return AGX_OK;
 }
 

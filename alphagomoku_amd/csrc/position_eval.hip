@@ -14,8 +14,10 @@
  *                        18 undo-snapshot levels in HBM), the feature words to row p * S + j.
  *   k_combine_positions  one wave per POSITION behind the tower: the S rows of a position are added cell by cell through the inverse
  *                        symmetry map (built once per wave in LDS), masked, optionally renormalised, and the top_k legal cells picked.
+ *   k_combine_solved_positions  the same behind the threat solver (agx_position_evaluator_evaluate_solved; the solve itself is
+ *                        k_solve_positions in engine.hip): the solver's action list is the move set, a proven position gets its score's value.
  * Every sum has a fixed order (ascending symmetry; cell order for the renormalisation), so the outputs are a pure function of the
- * tower's rows: tests/position_eval_ref.py restates the combine step in numpy float32 and the comparison is on the bits.
+ * tower's rows: tests/position_eval_ref.py (position_solve_ref.py behind the solver) restates the combine step in numpy float32 and the comparison is on the bits.
  * Like training_batch.hip the file is built with -ffp-contract=off and correctly rounded float32 division.
  */
 #include "agx_internal.hpp"
@@ -144,6 +146,8 @@ namespace agx
 				int *status;                   // [n] or null
 		};
 
+		/* (k_combine_solved_positions below repeats the sums, the ordered renormalising sum and the top-k rounds of this kernel: a change to
+		 * an order or a tie-break here is a change there, and in tests/position_eval_ref.py / position_solve_ref.py) */
 		template<int N>
 		__global__ __launch_bounds__(64) void k_combine_positions(CombineArgs A)
 		{
@@ -290,6 +294,199 @@ namespace agx
 				}
 			}
 		}
+		struct SolvedArgs
+		{ // what agx_position_solver_solve wrote for the batch
+				const uint16_t *score;       // [n]
+				const int *n_actions;        // [n]
+				const uint16_t *moves;       // [n][hw]
+				const uint16_t *move_scores; // [n][hw]
+				const int *status;           // [n]
+		};
+
+		/* k_combine_positions behind the solver (agx_position_evaluator_evaluate_solved): the same sums in the same orders, then the solver's
+		 * action list as the move set — an unproven position keeps the network's policy on the list only, a proven one gets its score's value
+		 * and 1.0f / k on the k best actions.  A kernel of its own: k_combine_positions stays as it is. */
+		template<int N>
+		__global__ __launch_bounds__(64) void k_combine_solved_positions(CombineArgs A, SolvedArgs V)
+		{
+			constexpr int HW = N * N, CHUNKS = (HW + 63) / 64;
+			__shared__ uint16_t image[8][HW]; // as in k_combine_positions
+			__shared__ uint8_t listed[HW];    // 0: not in the action list, 1: in it, 2: in it with the list's best score
+			const int lane = threadIdx.x;
+			const int S = A.S;
+			for (int j = 0; j < S; j++)
+			{
+				const int s = symmetry_of_rank(A.mask, j);
+				for (int i = lane; i < HW; i += 64)
+				{
+					int sr, sc;
+					symmetry_source(s, N, i / N, i % N, sr, sc);
+					image[j][sr * N + sc] = static_cast<uint16_t>(i);
+				}
+			}
+			__syncthreads();
+			const float inv_s = 1.0f / static_cast<float>(S);
+
+			for (int p = blockIdx.x; p < A.n; p += gridDim.x)
+			{
+				const int st_eval = (A.status_in != nullptr) ? A.status_in[p] : 0, st_solver = V.status[p];
+				const bool bad = (st_eval & AGX_POSEVAL_STATUS_BAD_INPUT) != 0 || st_solver == AGX_POSSOLVE_STATUS_BAD_INPUT;
+				const size_t row0 = static_cast<size_t>(p) * S;
+				const uint32_t score = V.score[p];
+				const int pv = (score >> 13) & 3;
+				const bool proven = !bad && pv != 2 && score != 0u && score != 0xFFFFu; // Score::isProven
+				const int count = bad ? 0 : min(V.n_actions[p], HW);
+				uint32_t best = 0;
+				for (int i = lane; i < count; i += 64)
+					best = max(best, static_cast<uint32_t>(V.move_scores[static_cast<size_t>(p) * HW + i]));
+#pragma unroll
+				for (int off = 1; off < 64; off <<= 1)
+					best = max(best, static_cast<uint32_t>(__shfl_xor(static_cast<int>(best), off, 64)));
+				__syncthreads(); // the previous position's marks have been read
+				for (int i = lane; i < HW; i += 64)
+					listed[i] = 0;
+				__syncthreads();
+				int n_best = 0;
+				for (int i = lane; i < count; i += 64)
+				{
+					const uint32_t m = V.moves[static_cast<size_t>(p) * HW + i];
+					const int cell = static_cast<int>((m >> 2) & 127u) * N + static_cast<int>((m >> 9) & 127u);
+					const bool is_best = V.move_scores[static_cast<size_t>(p) * HW + i] == best;
+					if (cell < HW)
+					{
+						listed[cell] = is_best ? 2 : 1;
+						n_best += is_best ? 1 : 0;
+					}
+				}
+#pragma unroll
+				for (int off = 1; off < 64; off <<= 1)
+					n_best += __shfl_xor(n_best, off, 64);
+				__syncthreads();
+				const float share = (n_best > 0) ? 1.0f / static_cast<float>(n_best) : 0.0f;
+				if (lane == 0 && A.status != nullptr)
+					A.status[p] = max(st_eval, st_solver);
+				if (lane < 3 && A.value != nullptr)
+				{
+					float sum = 0.0f;
+					for (int j = 0; j < S; j++)
+						sum += A.value_rows[(row0 + j) * 3 + lane];
+					const float of_score = (pv == ((lane == 0) ? 3 : ((lane == 1) ? 1 : 0))) ? 1.0f : 0.0f;
+					A.value[static_cast<size_t>(p) * 3 + lane] = bad ? 0.0f : (proven ? of_score : sum * inv_s);
+				}
+				float prob[CHUNKS];
+				uint32_t legal = 0; // bit ch: cell ch * 64 + lane may be picked
+				float total = 0.0f;
+#pragma unroll
+				for (int ch = 0; ch < CHUNKS; ch++)
+				{
+					const int cell = ch * 64 + lane;
+					const bool inside = cell < HW;
+					float sum = 0.0f, win = 0.0f, draw = 0.0f;
+					bool free_cell = false;
+					if (inside && !bad)
+					{
+						for (int j = 0; j < S; j++)
+						{
+							const size_t at = (row0 + j) * HW + image[j][cell];
+							sum += A.policy_rows[at];
+							if (A.q_rows != nullptr && A.action_values != nullptr)
+							{
+								win += A.q_rows[at * 2 + 0];
+								draw += A.q_rows[at * 2 + 1];
+							}
+						}
+						sum *= inv_s;
+						free_cell = (A.boards[static_cast<size_t>(p) * HW + cell] == 0);
+						if (free_cell && (A.flags & AGX_POSEVAL_MASK_FORBIDDEN) != 0)
+							free_cell = ((A.features[row0 * HW + cell] >> 6) & 1u) == 0u;
+						const int mark = listed[cell];
+						if (!free_cell || mark == 0)
+							sum = 0.0f;
+						if (proven)
+							sum = (mark == 2) ? share : 0.0f;
+						free_cell = free_cell && mark != 0;
+					}
+					if (inside && A.action_values != nullptr)
+					{
+						float *q = A.action_values + (static_cast<size_t>(p) * HW + cell) * 2;
+						q[0] = win * inv_s;
+						q[1] = draw * inv_s;
+					}
+					prob[ch] = sum;
+					legal |= free_cell ? (1u << ch) : 0u;
+					if ((A.flags & AGX_POSEVAL_RENORMALISE) != 0 && !proven)
+					{ // total += prob[cell], in cell order; + 0.0f changes nothing
+						unsigned long long nonzero = __ballot(sum != 0.0f);
+						while (nonzero != 0ull)
+						{
+							const int from = __builtin_amdgcn_readfirstlane(__ffsll(static_cast<long long>(nonzero)) - 1);
+							nonzero &= nonzero - 1ull;
+							total += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sum), from));
+						}
+					}
+				}
+				if ((A.flags & AGX_POSEVAL_RENORMALISE) != 0 && !proven && total != 0.0f)
+				{
+					const float scale = 1.0f / total;
+#pragma unroll
+					for (int ch = 0; ch < CHUNKS; ch++)
+						prob[ch] *= scale;
+				}
+				if (A.policy != nullptr)
+				{
+#pragma unroll
+					for (int ch = 0; ch < CHUNKS; ch++)
+						if (ch * 64 + lane < HW)
+							A.policy[static_cast<size_t>(p) * HW + ch * 64 + lane] = prob[ch];
+				}
+				// the top_k rounds of k_combine_positions
+				for (int k = 0; k < A.top_k; k++)
+				{
+					float best_p = -INFINITY;
+					int at = 0x7FFFFFFF; // "no cell": loses against every cell
+#pragma unroll
+					for (int ch = 0; ch < CHUNKS; ch++)
+					{
+						const float key = (prob[ch] != prob[ch]) ? -INFINITY : prob[ch];
+						if (((legal >> ch) & 1u) != 0u && (key > best_p || at == 0x7FFFFFFF))
+						{
+							best_p = key;
+							at = ch * 64 + lane;
+						}
+					}
+#pragma unroll
+					for (int off = 1; off < 64; off <<= 1)
+					{
+						const float ov = __shfl_xor(best_p, off, 64);
+						const int oi = __shfl_xor(at, off, 64);
+						if (oi != 0x7FFFFFFF && (at == 0x7FFFFFFF || ov > best_p || (ov == best_p && oi < at)))
+						{
+							best_p = ov;
+							at = oi;
+						}
+					}
+					const size_t slot = static_cast<size_t>(p) * A.top_k + k;
+					if (at == 0x7FFFFFFF)
+					{ // fewer legal cells than top_k
+						if (lane == 0 && A.top_cells != nullptr)
+							A.top_cells[slot] = -1;
+						if (lane == 0 && A.top_probs != nullptr)
+							A.top_probs[slot] = 0.0f;
+						continue;
+					}
+#pragma unroll
+					for (int ch = 0; ch < CHUNKS; ch++)
+						if (ch * 64 + lane == at)
+						{ // the winner's own lane
+							if (A.top_cells != nullptr)
+								A.top_cells[slot] = at;
+							if (A.top_probs != nullptr)
+								A.top_probs[slot] = prob[ch];
+							legal &= ~(1u << ch);
+						}
+				}
+			}
+		}
 	}
 }
 
@@ -368,7 +565,8 @@ namespace
 		return AGX_OK;
 	}
 	int launch_combine(AgxPositionEvaluator *pe, int n, const uint8_t *d_boards, int mask, int flags, int top_k, const uint32_t *d_features, const float *d_policy_rows,
-			const float *d_value_rows, const float *d_q_rows, const int *d_status_in, const AgxPositionOutputs *out, hipStream_t stream)
+			const float *d_value_rows, const float *d_q_rows, const int *d_status_in, const AgxPositionOutputs *out, hipStream_t stream,
+			const agx::SolvedArgs *solved = nullptr)
 	{
 		agx::CombineArgs A;
 		A.n = n;
@@ -389,7 +587,14 @@ namespace
 		A.top_probs = out->top_probs;
 		A.status = out->status;
 		const int waves = std::min(n, agx::PE_MAX_WAVES);
-		if (pe->n == 15)
+		if (solved != nullptr)
+		{
+			if (pe->n == 15)
+				hipLaunchKernelGGL(agx::k_combine_solved_positions<15>, dim3(waves), dim3(64), 0, stream, A, *solved);
+			else
+				hipLaunchKernelGGL(agx::k_combine_solved_positions<agx::MAXN>, dim3(waves), dim3(64), 0, stream, A, *solved);
+		}
+		else if (pe->n == 15)
 			hipLaunchKernelGGL(agx::k_combine_positions<15>, dim3(waves), dim3(64), 0, stream, A);
 		else
 			hipLaunchKernelGGL(agx::k_combine_positions<agx::MAXN>, dim3(waves), dim3(64), 0, stream, A);
@@ -568,6 +773,74 @@ int agx_position_evaluator_evaluate(AgxPositionEvaluator *pe, AgxNet *net, int n
 	// also behind a launch that failed half way: whatever was enqueued still uses the spill areas and the workspace
 	const int marked = mark_launched(pe, stream);
 	return (st != AGX_OK) ? st : marked;
+}
+
+int agx_position_evaluator_evaluate_solved(AgxPositionEvaluator *pe, AgxPositionSolver *solver, AgxNet *net, int n, const uint8_t *d_boards, const uint8_t *d_signs,
+		int symmetry_mask, int flags, int top_k, const AgxPositionOutputs *out, const AgxSolvedPositions *solved_out, void *stream_)
+{
+	AGX_REQUIRE(pe != nullptr && solver != nullptr && net != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_position_evaluator_evaluate_solved: null argument");
+	int st = check_batch(pe, "agx_position_evaluator_evaluate_solved", n, symmetry_mask);
+	if (st == AGX_OK)
+		st = check_combine("agx_position_evaluator_evaluate_solved", symmetry_mask, flags, top_k);
+	if (st != AGX_OK)
+		return st;
+	int solver_rules = 0, solver_n = 0, solver_capacity = 0;
+	AgxSolvedPositions use;
+	st = agx::position_solver_describe(solver, &solver_rules, &solver_n, &solver_capacity, &use);
+	if (st != AGX_OK)
+		return st;
+	AGX_REQUIRE(solver_rules == pe->rules && solver_n == pe->n, AGX_ERR_INVALID,
+			"agx_position_evaluator_evaluate_solved: the solver was created for rules %d on %dx%d, the evaluator for rules %d on %dx%d", solver_rules, solver_n, solver_n, pe->rules,
+			pe->n, pe->n);
+	AGX_REQUIRE(n <= solver_capacity, AGX_ERR_INVALID, "agx_position_evaluator_evaluate_solved: %d positions, the solver was created for %d", n, solver_capacity);
+	AgxNetDesc desc;
+	st = agx_net_description(net, &desc);
+	if (st != AGX_OK)
+		return st;
+	AGX_REQUIRE(desc.rows == pe->n && desc.cols == pe->n, AGX_ERR_INVALID, "agx_position_evaluator_evaluate_solved: the network's board is %dx%d, the evaluator's %dx%d", desc.rows,
+			desc.cols, pe->n, pe->n);
+	AGX_REQUIRE(out->action_values == nullptr || desc.action_values != 0, AGX_ERR_INVALID,
+			"agx_position_evaluator_evaluate_solved: action values asked of a network without that head ('pv')");
+	if (n == 0)
+		return AGX_OK;
+	AGX_REQUIRE(d_boards != nullptr && d_signs != nullptr, AGX_ERR_INVALID, "agx_position_evaluator_evaluate_solved: null boards or signs");
+	if (solved_out != nullptr)
+	{ // the combine launch reads five of the solver's outputs: the caller's arrays where given, the solver's workspace otherwise
+		use.score = (solved_out->score != nullptr) ? solved_out->score : use.score;
+		use.n_actions = (solved_out->n_actions != nullptr) ? solved_out->n_actions : use.n_actions;
+		use.moves = (solved_out->moves != nullptr) ? solved_out->moves : use.moves;
+		use.move_scores = (solved_out->move_scores != nullptr) ? solved_out->move_scores : use.move_scores;
+		use.status = (solved_out->status != nullptr) ? solved_out->status : use.status;
+		use.flags = solved_out->flags;
+		use.nodes = solved_out->nodes;
+		use.value = solved_out->value;
+	}
+	agx::SolvedArgs V;
+	V.score = use.score;
+	V.n_actions = use.n_actions;
+	V.moves = use.moves;
+	V.move_scores = use.move_scores;
+	V.status = use.status;
+	hipStream_t stream = static_cast<hipStream_t>(stream_);
+	const int rows = n * popcount8(symmetry_mask);
+	const bool with_q = (out->action_values != nullptr);
+	std::lock_guard<std::mutex> lock(pe->mutex);
+	st = order_behind_previous(pe, stream);
+	if (st != AGX_OK)
+		return st;
+	st = agx_position_solver_solve(solver, n, d_boards, d_signs, &use, stream);
+	if (st != AGX_OK)
+		return st; // (the solver has marked its own launch; nothing of the evaluator's is enqueued)
+	st = launch_encode(pe, n, d_boards, d_signs, symmetry_mask, pe->d_features, pe->d_status, stream);
+	if (st == AGX_OK)
+		st = with_q ? agx_nn_forward_pvq(net, pe->d_features, rows, pe->d_policy, pe->d_value, pe->d_q, stream) :
+				agx_nn_forward(net, pe->d_features, rows, pe->d_policy, pe->d_value, stream);
+	if (st == AGX_OK)
+		st = launch_combine(pe, n, d_boards, symmetry_mask, flags, top_k, pe->d_features, pe->d_policy, pe->d_value, with_q ? pe->d_q : nullptr, pe->d_status, out, stream, &V);
+	// also behind a launch that failed half way: whatever was enqueued still uses the workspaces of both
+	const int marked = mark_launched(pe, stream);
+	const int marked_solver = agx::position_solver_mark(solver, stream);
+	return (st != AGX_OK) ? st : ((marked != AGX_OK) ? marked : marked_solver);
 }
 
 } /* extern "C" */

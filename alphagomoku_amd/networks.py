@@ -101,7 +101,7 @@ class AGNetwork:
             cache[rules] = (handle, capacity)
         return cache[rules][0]
 
-    def evaluate_positions(self, boards, signs, rules, symmetries=0x01, flags=0, top_k=0, stream=None, out=None):
+    def evaluate_positions(self, boards, signs, rules, symmetries=0x01, flags=0, top_k=0, stream=None, out=None, solver=None):
         """agx_position_evaluator_evaluate: boards [n, rows, cols] (or [n, rows * cols]) uint8 with 0 empty / 1 cross / 2 circle and signs [n]
         uint8 (1 cross / 2 circle to move) -> policy [n, rows, cols], value [n, 3], action_values [n, rows, cols, 2] ('pvq' networks),
         top_cells [n, top_k] int32 (row * cols + col, -1 once no legal cell is left), top_probs [n, top_k], status [n] int32.  The rows of
@@ -109,7 +109,10 @@ class AGNetwork:
         numpy arrays make a host round trip and come back as a dict of arrays.  Contiguous device torch tensors stay on the device: the
         launches go on torch.cuda.current_stream() unless `stream` names one (the library must share torch's HIP runtime, as for
         score_outputs), the outputs named in the dict `out` are written where they lie (without `out` torch allocates all of them), nothing
-        is waited for, and the dict is returned."""
+        is waited for, and the dict is returned.
+        solver: a solver.PositionSolver of the same rules and board selects agx_position_evaluator_evaluate_solved — the solver's action
+        list is the move set (policy 0.0 outside it), a proven position gets its score's value and 1 / k on its k best actions; the dict
+        then has one more entry, 'solved': the dict PositionSolver.solve returns (with tensors, `out['solved']` names the ones to write)."""
         from . import _lib
         rows, cols = self.desc["rows"], self.desc["cols"]
         hw, with_q = rows * cols, bool(self.desc.get("action_values", 0))
@@ -122,6 +125,15 @@ class AGNetwork:
             raise ValueError("evaluate_positions: boards [n, %d, %d] and signs [n] expected" % (rows, cols))
         pe = self._position_evaluator(rules, n)
         c_out = _lib.AgxPositionOutputs()
+        c_solved = _lib.AgxSolvedPositions()
+
+        def launch(d_boards, d_signs, on_stream):
+            if solver is None:
+                check(lib.agx_position_evaluator_evaluate(pe, self._net, n, d_boards, d_signs, symmetries, flags, top_k, ctypes.byref(c_out), on_stream))
+            else:
+                check(lib.agx_position_evaluator_evaluate_solved(pe, solver.handle, self._net, n, d_boards, d_signs, symmetries, flags, top_k, ctypes.byref(c_out),
+                                                                 ctypes.byref(c_solved), on_stream))
+        solved_shapes = solver._shapes() if solver is not None else {}
         if on_device:
             import torch
             if not _lib.torch_shares_hip_runtime():
@@ -131,28 +143,43 @@ class AGNetwork:
                 raise ValueError("evaluate_positions: boards and signs are uint8 tensors")
             if stream is None:
                 stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            torch_kinds = {np.uint16: torch.int16, np.uint32: torch.int32, np.int32: torch.int32, np.float32: torch.float32}   # (the same bits: PositionSolver.solve)
             if out is None:
                 out = {k: torch.empty((n,) + shapes[k], dtype=torch.int32 if k in kinds else torch.float32, device=boards.device) for k in names}
+                if solver is not None:
+                    out["solved"] = {k: torch.empty((n,) + shape, dtype=torch_kinds[dtype], device=boards.device) for k, (shape, dtype) in solved_shapes.items()}
             for k, t in out.items():
+                if k == "solved" and solver is not None:
+                    continue
                 if k not in names or tuple(t.shape) != (n,) + shapes[k] or t.dtype != (torch.int32 if k in kinds else torch.float32):
                     raise ValueError("evaluate_positions: output '%s' has no place in this call, or another shape or dtype than the call writes" % k)
                 setattr(c_out, k, _address(t))
-            check(lib.agx_position_evaluator_evaluate(pe, self._net, n, _address(boards), _address(signs), symmetries, flags, top_k, ctypes.byref(c_out), stream))
+            for k, t in (out.get("solved", {}) if solver is not None else {}).items():
+                if k not in solved_shapes or tuple(t.shape) != (n,) + solved_shapes[k][0] or t.dtype != torch_kinds[solved_shapes[k][1]]:
+                    raise ValueError("evaluate_positions: output 'solved.%s' has no place in this call, or another shape or dtype than the call writes" % k)
+                setattr(c_solved, k, _address(t))
+            launch(_address(boards), _address(signs), stream)
             return out
         b = np.ascontiguousarray(boards, dtype=np.uint8)
         s = np.ascontiguousarray(signs, dtype=np.uint8)
         bufs = {k: DeviceBuffer(n * int(np.prod(shapes[k], dtype=np.int64)) * 4) for k in names}
+        solved_bufs = {k: DeviceBuffer(n * int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize) for k, (shape, dtype) in solved_shapes.items()}
         d_boards, d_signs = DeviceBuffer(b.nbytes), DeviceBuffer(s.nbytes)
         try:
             d_boards.upload(b)
             d_signs.upload(s)
             for k, buf in bufs.items():
                 setattr(c_out, k, buf.ptr)
-            check(lib.agx_position_evaluator_evaluate(pe, self._net, n, d_boards.ptr, d_signs.ptr, symmetries, flags, top_k, ctypes.byref(c_out), stream))
+            for k, buf in solved_bufs.items():
+                setattr(c_solved, k, buf.ptr)
+            launch(d_boards.ptr, d_signs.ptr, stream)
             check(lib.agx_stream_synchronize(stream))
-            return {k: buf.download((n,) + shapes[k], kinds.get(k, np.float32)) for k, buf in bufs.items()}
+            result = {k: buf.download((n,) + shapes[k], kinds.get(k, np.float32)) for k, buf in bufs.items()}
+            if solver is not None:
+                result["solved"] = {k: buf.download((n,) + solved_shapes[k][0], solved_shapes[k][1]) for k, buf in solved_bufs.items()}
+            return result
         finally:
-            for buf in list(bufs.values()) + [d_boards, d_signs]:
+            for buf in list(bufs.values()) + list(solved_bufs.values()) + [d_boards, d_signs]:
                 buf.free()
 
     def close(self):

@@ -780,6 +780,71 @@ int agx_position_evaluator_combine(AgxPositionEvaluator* pe, int n, const uint8_
 int agx_position_evaluator_evaluate(AgxPositionEvaluator* pe, AgxNet* net, int n, const uint8_t* d_boards, const uint8_t* d_signs, int symmetry_mask,
 		int flags, int top_k, const AgxPositionOutputs* out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Positions solved on the device: boards -> proven scores and the solver's action lists (k_solve_positions, csrc/engine.hip).
+ * The threat solver of the search (AlphaBetaSearch) for callers that hold boards: filtering provable samples out of a training set, puzzle
+ * sets, opening checks, a move suggestion that respects forced defences.  Every position is solved as a fresh AlphaBetaSearch with an empty
+ * table and node limit max_positions would solve it, so a position's result is a function of the position and of the arguments of
+ * agx_position_solver_create alone — not of the batch, of the position's place in it, or of the number of waves.  One wavefront per
+ * position; each wave owns a transposition table of table_entries entries (rounded up to a power of two, 16 bytes each), which it clears
+ * before every position, and the solver's spill areas: agx_position_solver_info reports the waves and the bytes.  The wave count is
+ * min(capacity, 4 per compute unit); the environment variable AGX_POSSOLVE_MAX_WAVES, read at create, caps it.  Square boards 5..20, all
+ * five rule sets.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct AgxPositionSolver AgxPositionSolver;
+
+enum
+{ /* status words */
+	AGX_POSSOLVE_STATUS_BAD_INPUT = 1,    /* a cell value above 2 or a sign other than 1 / 2: zeroed outputs, nothing reached the solver */
+	AGX_POSSOLVE_STATUS_SOLVER_ERROR = 2  /* the solver gave up (the renju foul probe nested too deep, an action stack or frame overflow): outputs not to be trusted */
+};
+
+typedef struct AgxSolvedPositions
+{ /* device addresses; any of them may be NULL */
+	uint16_t* score;        /* [n] the 16-bit Score encoding of AgxEdgeView.score / agx_debug_solve's h_result_scores */
+	uint32_t* flags;        /* [n] 1 must defend, 4 processed by the solver, 16 statically solved (at most one node), 32 recursively solved (proven) */
+	int32_t* n_actions;     /* [n] */
+	uint16_t* moves;        /* [n][cells] the solver's action list in the solver's ORDER (Move::toShort: sign | row << 2 | col << 9), zeros behind it */
+	uint16_t* move_scores;  /* [n][cells] */
+	uint32_t* nodes;        /* [n] AlphaBetaSearch::solve's return value */
+	float* value;           /* [n][3] = (win, draw, loss) of a proven score (Score::convertToValue), zeros when unproven */
+	int32_t* status;        /* [n] 0 or AGX_POSSOLVE_STATUS_* */
+} AgxSolvedPositions;
+
+/* Allocates everything agx_position_solver_solve uses, on the current HIP device.  AGX_ERR_UNSUPPORTED: board_size outside 5..20,
+ * max_positions outside 1..1000; AGX_ERR_INVALID: a null argument, unknown rules, capacity outside 1..2^20, table_entries above 2^32 (below
+ * that every value is taken, as by agx_engine_create: at least 4, rounded up to a power of two). */
+int agx_position_solver_create(int rules, int board_size, int capacity, int max_positions, uint64_t table_entries, uint64_t zobrist_seed,
+		AgxPositionSolver** out);
+/* One launch on `stream`; nothing is allocated, nothing synchronised.  d_boards uint8[n][cells] (0 empty, 1 cross, 2 circle), d_signs
+ * uint8[n] (1 cross / 2 circle to move).  AGX_ERR_INVALID before anything is launched: a null solver, `out`, boards or signs, n negative or
+ * above the capacity.  Calls on one solver share its per-wave areas: a call on another stream than the previous one is ordered behind it on
+ * the device. */
+int agx_position_solver_solve(AgxPositionSolver* solver, int n, const uint8_t* d_boards, const uint8_t* d_signs, const AgxSolvedPositions* out,
+		void* stream);
+int agx_position_solver_destroy(AgxPositionSolver* solver);
+/* waves of a launch, device bytes each wave owns (table, action stack, threat-list tails, frames, undo snapshots, task, game record,
+ * feature words), and everything the solver allocated: waves x bytes_per_wave + the rule tables + the capacity-sized workspace of
+ * agx_position_evaluator_evaluate_solved.  Any output may be NULL. */
+int agx_position_solver_info(const AgxPositionSolver* solver, int* waves, uint64_t* bytes_per_wave, uint64_t* device_bytes);
+
+/* The solver in front of the position evaluator: solve, encode, the tower, combine — four launches on `stream`, nothing synchronised.
+ * `solved_out` (may be NULL, as may each of its members) receives what agx_position_solver_solve writes.  The tower runs on every row.
+ * With L the solver's action list of a position:
+ *   unproven score   policy as agx_position_evaluator_evaluate computes it, then 0.0f on every cell outside L (what the search does with a
+ *                    task processed by the solver: the list is the move set, the network supplies the priors on it); then
+ *                    AGX_POSEVAL_RENORMALISE by its rule; value: the network's
+ *   proven score     value = the score's (win, draw, loss); policy = 1.0f / k on the k actions of L whose 16-bit score is the largest in L,
+ *                    0.0f elsewhere (not renormalised, no mask applied); this split is the project's own definition
+ *   top_k picks      by the rule of agx_position_evaluator_evaluate over that policy, among the cells of L that are legal there
+ *   action values    the network's, unchanged
+ *   status           the larger of the solver's and the evaluator's word; a position with bad input has zero outputs and cells -1
+ * Refused before anything is launched: whatever agx_position_evaluator_evaluate refuses, a null solver, n above the solver's capacity,
+ * and (AGX_ERR_INVALID) a solver whose rules or board size differ from the evaluator's. */
+int agx_position_evaluator_evaluate_solved(AgxPositionEvaluator* pe, AgxPositionSolver* solver, AgxNet* net, int n, const uint8_t* d_boards,
+		const uint8_t* d_signs, int symmetry_mask, int flags, int top_k, const AgxPositionOutputs* out, const AgxSolvedPositions* solved_out,
+		void* stream);
+
 /* Raw device-memory helpers so that non-HIP hosts (ctypes, cgo) can stage buffers. */
 int agx_malloc(void** d_ptr, size_t bytes);
 int agx_free(void* d_ptr);

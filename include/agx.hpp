@@ -610,6 +610,8 @@ namespace agx
 			}
 	};
 
+	class PositionSolver;
+
 	/* Boards to policy, value and best moves on the device (agx.h: agx_position_evaluator_*): the encode launch in front of the tower, the
 	 * combine launch behind it.  What AGNetwork::packInputData(index, board, signToMove) + forward + unpackOutput do for one caller at a
 	 * time on the reference's host, for `capacity` positions per call; the average over several symmetries and the top-k are this
@@ -639,11 +641,69 @@ namespace agx
 			{
 				check(agx_position_evaluator_evaluate(m_evaluator, net.handle(), n, d_boards, d_signs, symmetry_mask, flags, top_k, &out, stream));
 			}
+			/* the same behind the threat solver (agx_position_evaluator_evaluate_solved): the solver's action list is the move set, a proven
+			 * position gets its score's value; `solved` (may be null, as may its members) receives the solver's own outputs.  Declared below. */
+			void evaluate_solved(const PositionSolver &solver, const AGNetwork &net, int n, const uint8_t *d_boards, const uint8_t *d_signs,
+					const AgxPositionOutputs &out, const AgxSolvedPositions *solved = nullptr, int symmetry_mask = 0x01, int flags = 0, int top_k = 0, void *stream = nullptr);
 			AgxPositionEvaluator* handle() const noexcept
 			{
 				return m_evaluator;
 			}
 	};
+
+	/* The threat solver on boards (agx.h: agx_position_solver_*): every position solved as a fresh AlphaBetaSearch with an empty table and
+	 * node limit max_positions would solve it, `capacity` positions per call, one wavefront per position.  All pointers are device
+	 * addresses; solve only enqueues on `stream`. */
+	class PositionSolver
+	{
+			AgxPositionSolver *m_solver = nullptr;
+		public:
+			PositionSolver(int rules, int board_size, int capacity, int max_positions = 100, uint64_t table_entries = 1u << 16, uint64_t zobrist_seed = 0x9E3779B97F4A7C15ull)
+			{
+				check(agx_position_solver_create(rules, board_size, capacity, max_positions, table_entries, zobrist_seed, &m_solver));
+			}
+			PositionSolver(const PositionSolver&) = delete;
+			PositionSolver& operator=(const PositionSolver&) = delete;
+			~PositionSolver()
+			{
+				agx_position_solver_destroy(m_solver);
+			}
+			/* any pointer of `out` may be null */
+			void solve(int n, const uint8_t *d_boards, const uint8_t *d_signs, const AgxSolvedPositions &out, void *stream = nullptr)
+			{
+				check(agx_position_solver_solve(m_solver, n, d_boards, d_signs, &out, stream));
+			}
+			int waves() const
+			{
+				int w = 0;
+				check(agx_position_solver_info(m_solver, &w, nullptr, nullptr));
+				return w;
+			}
+			/* device bytes one wave owns: its table, action stack, threat-list tails, frames, undo snapshots, task, game record, feature words */
+			uint64_t bytes_per_wave() const
+			{
+				uint64_t bytes = 0;
+				check(agx_position_solver_info(m_solver, nullptr, &bytes, nullptr));
+				return bytes;
+			}
+			/* everything the solver allocated on the device: waves x the bytes a wave owns + tables + workspace */
+			uint64_t device_bytes() const
+			{
+				uint64_t bytes = 0;
+				check(agx_position_solver_info(m_solver, nullptr, nullptr, &bytes));
+				return bytes;
+			}
+			AgxPositionSolver* handle() const noexcept
+			{
+				return m_solver;
+			}
+	};
+
+	inline void PositionEvaluator::evaluate_solved(const PositionSolver &solver, const AGNetwork &net, int n, const uint8_t *d_boards, const uint8_t *d_signs,
+			const AgxPositionOutputs &out, const AgxSolvedPositions *solved, int symmetry_mask, int flags, int top_k, void *stream)
+	{
+		check(agx_position_evaluator_evaluate_solved(m_evaluator, solver.handle(), net.handle(), n, d_boards, d_signs, symmetry_mask, flags, top_k, &out, solved, stream));
+	}
 }
 
 #endif /* AGX_HPP_ */
