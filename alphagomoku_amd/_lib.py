@@ -382,3 +382,31 @@ def _declare(c):  # noqa: F811
     c.agx_position_solver_destroy.argtypes = [vp]
     c.agx_position_solver_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(u64), ctypes.POINTER(u64)]
     c.agx_position_evaluator_evaluate_solved.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, ci, ctypes.POINTER(AgxPositionOutputs), solved, vp]
+
+
+class AgxPositionSearchOutputs(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ["status", "root", "root_value", "best_move", "visits", "prior", "q", "score", "edge_index", "pv",
+                                                "pv_length", "info"]]
+
+
+POSSEARCH_STATUS_BAD_INPUT, POSSEARCH_STATUS_ENGINE_ERROR, POSSEARCH_STATUS_STEP_LIMIT = 1, 2, 3
+
+_declare_solver = _declare
+
+
+def _declare(c):  # noqa: F811
+    _declare_solver(c)
+    vp, ci, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64
+    outputs = ctypes.POINTER(AgxPositionSearchOutputs)
+    c.agx_position_searcher_create.argtypes = [ctypes.POINTER(AgxEngineConfig), ctypes.POINTER(vp)]
+    c.agx_position_searcher_destroy.argtypes = [vp]
+    c.agx_position_searcher_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(u64)]
+    c.agx_position_searcher_engine.argtypes = [vp, ctypes.POINTER(vp)]
+    c.agx_position_searcher_begin.argtypes = [vp, ci, vp, vp, vp, outputs, ci, ci, vp]
+    for name in ["select_solve", "expand", "harvest"]:
+        getattr(c, "agx_position_searcher_" + name).argtypes = [vp, vp]
+    c.agx_position_searcher_buffers.argtypes = [vp, ctypes.POINTER(AgxEngineBuffers)]
+    c.agx_position_searcher_evaluate.argtypes = [vp, vp, vp]
+    c.agx_position_searcher_slots.argtypes = [vp, vp, vp]
+    c.agx_position_searcher_finished.argtypes = [vp, vp, ctypes.POINTER(ci)]
+    c.agx_position_searcher_search.argtypes = [vp, vp, ci, vp, vp, vp, outputs, ci, ci, vp]

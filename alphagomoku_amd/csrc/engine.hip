@@ -3157,6 +3157,450 @@ namespace
 			*second = 0;
 	}
 
+	/* ------------------------------------------------------------------------------------------------------------ */
+	/*
+	 * Positions searched on the device (agx_position_searcher_*): the pool's slots take boards off a list instead of openings, search each
+	 * as a fresh GameGenerator would search for its first move (empty tree, empty solver table, generation 1, nn_queued 0), and hand the
+	 * root over when the move rule of k_expand fires — nothing is played.  k_load_positions is the front end (begin_game's work, from a
+	 * board), k_harvest_positions the back end (k_advance's place in the step: final selector, dense per-cell rows, principal variation),
+	 * and a harvested slot is left as a finished game is, so that k_arena_service takes grown arenas back before the next load.
+	 */
+	struct PositionJob
+	{
+			const uint8_t *boards;  // [n][hw] 0 empty, 1 cross, 2 circle
+			const uint8_t *signs;   // [n] 1 cross, 2 circle to move
+			const int32_t *serials; // [n] noise / symmetry serial (GameState::opening_id), null = 0
+			int n, max_pv, max_steps;
+			AgxPositionSearchOutputs out; // each may be null
+			int *cursor;        // next position of the list
+			int *finished;      // positions whose outputs are written
+			int *slot_position; // [n_games] the position a slot searches, -1 = free
+			int *slot_steps;    // [n_games] steps the slot has spent on it
+	};
+	/* every output of position p that has no root behind it: zeros, no edge anywhere (whole workgroup of `threads`) */
+	__device__ void position_write_empty(const PositionJob &J, int p, int hw, int status, int nodes, int edges, int steps, int error, int tid, int threads)
+	{
+		const AgxPositionSearchOutputs &o = J.out;
+		const size_t row = static_cast<size_t>(p) * hw;
+		for (int i = tid; i < hw; i += threads)
+		{
+			if (o.visits != nullptr)
+				o.visits[row + i] = 0;
+			if (o.prior != nullptr)
+				o.prior[row + i] = 0.0f;
+			if (o.q != nullptr)
+			{
+				o.q[2 * (row + i)] = 0.0f;
+				o.q[2 * (row + i) + 1] = 0.0f;
+			}
+			if (o.score != nullptr)
+				o.score[row + i] = 0;
+			if (o.edge_index != nullptr)
+				o.edge_index[row + i] = -1;
+		}
+		if (o.pv != nullptr)
+			for (int i = tid; i < J.max_pv; i += threads)
+				o.pv[static_cast<size_t>(p) * J.max_pv + i] = 0;
+		if (tid == 0)
+		{
+			if (o.status != nullptr)
+				o.status[p] = status;
+			if (o.root != nullptr)
+				o.root[4 * p] = o.root[4 * p + 1] = o.root[4 * p + 2] = o.root[4 * p + 3] = 0;
+			if (o.root_value != nullptr)
+				o.root_value[2 * p] = o.root_value[2 * p + 1] = 0.0f;
+			if (o.best_move != nullptr)
+				o.best_move[p] = 0;
+			if (o.pv_length != nullptr)
+				o.pv_length[p] = 0;
+			if (o.info != nullptr)
+			{
+				o.info[4 * p] = nodes;
+				o.info[4 * p + 1] = edges;
+				o.info[4 * p + 2] = steps;
+				o.info[4 * p + 3] = error;
+			}
+		}
+	}
+	__global__ __launch_bounds__(64) void k_positions_init(EngineDev E, PositionJob J)
+	{ // what k_begin does for a pool without openings: every slot idle and free, counting from zero
+		const int g = blockIdx.x;
+		if (threadIdx.x != 0)
+			return;
+		GameState &gs = E.games[g];
+		gs.generation = 0;
+		gs.error = 0;
+		gs.games_done = 0;
+		gs.arena = 0;
+		for (int i = 0; i < 12; i++)
+			gs.stats[i] = 0;
+		gs.active = 0;
+		gs.root = -1;
+		gs.n_nodes = 0;
+		gs.n_edges = 0;
+		gs.n_tasks = 0;
+		gs.need_move = 0;
+		gs.solve_pos = 0;
+		gs.solve_pending = 0;
+		gs.outcome = 0;
+		gs.n_moves = 0;
+		gs.restart_id = -1;
+		J.slot_position[g] = -1;
+		J.slot_steps[g] = 0;
+		if (g == 0)
+		{
+			*J.cursor = 0;
+			*J.finished = 0;
+		}
+	}
+	__global__ void k_positions_reset(PositionJob J)
+	{ // a new list: every slot is free (the previous job has finished)
+		*J.cursor = 0;
+		*J.finished = 0;
+	}
+	/* A free slot takes the next position of the list: a sibling of begin_game, from a board.  Tree::clear + AlphaBetaSearch::clear, a new
+	 * AlphaBetaSearch's generation (0, prepare_search makes it 1), the board with its stones as a move list in cell order, nn_queued 0, the
+	 * caller's serial where a game has its opening id.  A position that is none (k_encode_positions' rule) gets status 1 and the slot goes on
+	 * to the next one.  One workgroup of 256 threads per slot. */
+	__global__ __launch_bounds__(256) void k_load_positions(EngineDev E, PositionJob J)
+	{
+		__shared__ u64 scratch[4];
+		__shared__ int sh_p, sh_bad, sh_count;
+		const int g = E.g0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, hw = E.hw;
+		if (J.slot_position[g] >= 0)
+			return;
+		GameState &gs = E.games[g];
+		const uint8_t *src = nullptr;
+		int p = -1, sign = 0;
+		while (true)
+		{
+			if (tid == 0)
+			{
+				int next = -1;
+				if (__hip_atomic_load(J.cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < J.n)
+				{
+					next = atomicAdd(J.cursor, 1);
+					if (next >= J.n)
+						next = -1;
+				}
+				sh_p = next;
+				sh_bad = 0;
+			}
+			__syncthreads();
+			p = sh_p;
+			if (p < 0)
+				return; // the list is used up: the slot stays free
+			src = J.boards + static_cast<size_t>(p) * hw;
+			sign = J.signs[p];
+			bool bad = (sign != 1 && sign != 2);
+			for (int i = tid; i < hw; i += 256)
+				bad |= (src[i] > 2);
+			if (bad)
+				sh_bad = 1;
+			__syncthreads();
+			if (!sh_bad)
+				break;
+			position_write_empty(J, p, hw, AGX_POSSEARCH_STATUS_BAD_INPUT, 0, 0, 0, 0, tid, 256);
+			if (tid == 0)
+				atomicAdd(J.finished, 1);
+			__syncthreads();
+		}
+		clear_tree_and_table(E, g, tid);
+		for (int k = tid; k < E.batch; k += 256)
+		{ // a new GameGenerator's Search has new SearchTasks: what survives SearchTask::set (the solved flags, moves_left) must not come from the slot's previous position
+			DTask &t = E.tasks[static_cast<size_t>(g) * E.batch + k];
+			t.path_len = 0;
+			t.final_node = 0;
+			t.n_edges = 0;
+			t.flags = 0;
+			t.sign_to_move = 0;
+			t.score = 0;
+			t.win = 0.0f;
+			t.draw = 0.0f;
+			t.moves_left = 0.0f;
+			t.needs_nn = 0;
+			t.symmetry = 0;
+		}
+		for (int i = tid; i < hw; i += 256)
+			gs.board[i] = src[i];
+		if (tid < BWORDS)
+		{
+			u64 w = 0;
+			for (int c = 0; c < 32; c++)
+			{
+				const int cell = 32 * tid + c;
+				if (cell < hw)
+					w |= static_cast<u64>(src[cell]) << (2 * c);
+			}
+			gs.cboard[tid] = w;
+		}
+		if (tid < 64)
+		{ // the stones as moves, in cell order (up to hw of them)
+			int count = 0;
+			for (int base = 0; base < hw; base += 64)
+			{
+				const int i = base + lane;
+				const uint32_t v = (i < hw) ? src[i] : 0u;
+				const u64 m = __ballot(v != 0u);
+				if (v != 0u)
+					gs.moves[count + __popcll(m & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))))] = static_cast<uint16_t>(v | (static_cast<uint32_t>(i / E.n) << 2) | (static_cast<uint32_t>(i % E.n) << 9));
+				count += __popcll(m);
+			}
+			if (lane == 0)
+				sh_count = count;
+		}
+		__syncthreads();
+		if (tid == 0)
+		{
+			gs.sign_to_move = sign;
+			gs.n_moves = sh_count;
+			gs.outcome = 0;
+			gs.root = -1;
+			gs.n_nodes = 0;
+			gs.n_edges = 0;
+			gs.n_tasks = 0;
+			gs.need_move = 0;
+			gs.solve_pos = 0;
+			gs.solve_pending = 0;
+			park_forget_game(E, g);
+			gs.grow_pending = 0;
+			gs.max_depth = 0;
+			gs.nn_queued = 0;
+			gs.restart_id = 0;
+			gs.noise_ready = 0;
+			gs.generation = 1; // a new AlphaBetaSearch counts from 0, prepare_search -> increaseGeneration
+			gs.opening_id = (J.serials != nullptr) ? J.serials[p] : 0;
+			gs.error = 0;
+			gs.arena = 0;
+			gs.active = 1;
+		}
+		__syncthreads();
+		u64 h = 0;
+		for (int i = tid; i < hw; i += 256)
+			h ^= E.nc_keys[3 + 3 * i + gs.board[i]];
+		block_reduce_xor(h, scratch, tid);
+		if (tid == 0)
+		{
+			gs.root_hash = h ^ E.nc_keys[sign];
+			J.slot_steps[g] = 0;
+			J.slot_position[g] = p;
+		}
+	}
+	/* the rating of cfg.final_selector for one root edge: k_advance's switch, the same arithmetic (EdgeSelector.cpp:446-536) */
+	__device__ __forceinline__ float final_selector_rating(const EngineDev &E, const DEdge &e, const DNode &root)
+	{
+		switch (E.final_selector)
+		{
+			default:
+				return best_edge_rating(e, root);
+			case 1:
+				return e.visits;
+			case 2:
+				return -e.visits;
+			case 3:
+				switch (s_pv(e.score))
+				{
+					case 0:
+						return -1000.0f + s_distance(e.score);
+					case 1:
+						return 0.5f; // Value::draw().getExpectation()
+					case 3:
+						return +1000.0f - s_distance(e.score);
+					default:
+						return e.win + 0.5f * e.draw;
+				}
+			case 4:
+				return e.prior;
+			case 5:
+			{ // LCB (EdgeSelector.cpp:446-475)
+				const int pv = s_pv(e.score);
+				if (pv == 0)
+					return -1.0e6f + s_distance(e.score) + e.prior;
+				if (pv == 3)
+					return +1.0e6f - s_distance(e.score) + e.prior;
+				const int vl = e.flag_vl & 0x7FFF;
+				const float visits = 1.0e-8f + e.visits;
+				const float vl_factor = visits / (visits + static_cast<float>(vl));
+				const float Q = (e.visits > 0) ? (e.win + 0.5f * e.draw) : (root.win + 0.5f * root.draw);
+				const float parent_log_visit = static_cast<float>(det_log(static_cast<double>(root.visits + root.vl)));
+				const float U = E.c_puct * sqrtf(parent_log_visit / (1.0f + e.visits + vl));
+				return Q * vl_factor - U;
+			}
+		}
+	}
+	/* k_advance's place in a step of the position searcher, one wave per slot: a slot whose move rule has fired (or whose engine error word is
+	 * set, or that has spent max_steps steps) writes the outputs of its position and becomes a finished game: leaves still in flight give their
+	 * virtual losses back (k_cancel_pending), park buffers are forgotten, grown arenas wait for k_arena_service, the slot is free. */
+	__global__ __launch_bounds__(64) void k_harvest_positions(EngineDev E, PositionJob J)
+	{
+		__shared__ u64 sh_cboard[BWORDS];
+		__shared__ int16_t cell_edge[MAXHW];
+		const int g = E.g0 + blockIdx.x, lane = threadIdx.x, hw = E.hw, n = E.n;
+		const int p = J.slot_position[g];
+		if (p < 0)
+			return;
+		GameState &gs = E.games[g];
+		const int steps = J.slot_steps[g] + 1, error = gs.error;
+		const bool searched = gs.active && gs.need_move && !gs.solve_pending && !gs.grow_pending && error == 0;
+		if (!searched && error == 0 && steps < J.max_steps)
+		{
+			if (lane == 0)
+				J.slot_steps[g] = steps;
+			return;
+		}
+		const int status = searched ? 0 : ((error != 0) ? AGX_POSSEARCH_STATUS_ENGINE_ERROR : AGX_POSSEARCH_STATUS_STEP_LIMIT);
+		use_game_arenas(E, g);
+		DNode *nodes = nodes_of(E, g, gs.arena);
+		DEdge *edges = edges_of(E, g, gs.arena);
+		if (status == AGX_POSSEARCH_STATUS_STEP_LIMIT)
+		{ // Search::cleanup: the batch in flight (waiting for its solver, or for larger arenas) is dropped, the root stands without its virtual losses
+			const int pending = gs.n_tasks;
+			for (int k = 0; k < pending; k++)
+			{
+				const DTask &t = E.tasks[static_cast<size_t>(g) * E.batch + k];
+				cancel_virtual_loss(nodes, edges, t, t.path_len, lane);
+				wave_sync();
+			}
+			__threadfence_block();
+			__syncthreads();
+		}
+		const AgxPositionSearchOutputs &o = J.out;
+		const bool have_root = status != AGX_POSSEARCH_STATUS_ENGINE_ERROR && gs.root >= 0; // (a tree that stopped on an error is not read)
+		if (!have_root)
+			position_write_empty(J, p, hw, status, gs.n_nodes, gs.n_edges, steps, error, lane, 64);
+		else
+		{
+			DNode root;
+			node_head(root, nodes[gs.root]);
+			const int n_edges = root.n_edges;
+			for (int i = lane; i < hw; i += 64)
+				cell_edge[i] = -1;
+			__syncthreads();
+			// ---- final selector: k_advance's rule — first strict maximum per lane, then the lowest index among the lanes' maxima ----
+			float best_value = -3.402823466e+38f;
+			int best = 0x7FFFFFFF;
+			for (int i = lane; i < n_edges; i += 64)
+			{ // (a root on an empty 20x20 board has 400 edges)
+				const DEdge e = edges[root.edge_begin + i];
+				cell_edge[((e.move >> 2) & 127) * n + ((e.move >> 9) & 127)] = static_cast<int16_t>(i);
+				const float value = final_selector_rating(E, e, root);
+				if (value > best_value)
+				{
+					best_value = value;
+					best = i;
+				}
+			}
+			wave_argmax(best_value, best);
+			__syncthreads();
+			const size_t row = static_cast<size_t>(p) * hw;
+			for (int i = lane; i < hw; i += 64)
+			{
+				const int ei = cell_edge[i];
+				DEdge e;
+				e.prior = e.win = e.draw = 0.0f;
+				e.visits = 0;
+				e.score = 0;
+				if (ei >= 0)
+					e = edges[root.edge_begin + ei];
+				if (o.visits != nullptr)
+					o.visits[row + i] = e.visits;
+				if (o.prior != nullptr)
+					o.prior[row + i] = e.prior;
+				if (o.q != nullptr)
+				{
+					o.q[2 * (row + i)] = e.win;
+					o.q[2 * (row + i) + 1] = e.draw;
+				}
+				if (o.score != nullptr)
+					o.score[row + i] = e.score;
+				if (o.edge_index != nullptr)
+					o.edge_index[row + i] = static_cast<int16_t>(ei);
+			}
+			if (lane == 0)
+			{
+				if (o.status != nullptr)
+					o.status[p] = status;
+				if (o.root != nullptr)
+				{
+					o.root[4 * p] = root.visits;
+					o.root[4 * p + 1] = root.score;
+					o.root[4 * p + 2] = (root.flags >> 3) & 7; // DNode flags 8 / 16 / 32, as AgxMoveRecord.root_flags
+					o.root[4 * p + 3] = n_edges;
+				}
+				if (o.root_value != nullptr)
+				{
+					o.root_value[2 * p] = root.win;
+					o.root_value[2 * p + 1] = root.draw;
+				}
+				if (o.best_move != nullptr)
+					o.best_move[p] = (best < n_edges) ? edges[root.edge_begin + best].move : static_cast<uint16_t>(0);
+				if (o.info != nullptr)
+				{
+					o.info[4 * p] = gs.n_nodes;
+					o.info[4 * p + 1] = gs.n_edges;
+					o.info[4 * p + 2] = steps;
+					o.info[4 * p + 3] = error;
+				}
+			}
+			// ---- the principal variation: k_principal_variation's walk from the root ----
+			const int *ht = ht_of(E, g);
+			QueryWalk q;
+			query_begin(E, gs, sh_cboard, q, lane);
+			int length = 0;
+			while (length < J.max_pv)
+			{
+				const int found = q.valid ? cache_seek(E, nodes, ht, q.hash, sh_cboard, q.sign, lane) : -1;
+				if (found < 0)
+					break;
+				DNode nd;
+				node_head(nd, nodes[found]);
+				if (nd.n_edges <= 0)
+					break;
+				float pv_value = -3.402823466e+38f;
+				int pv_best = 0x7FFFFFFF;
+				for (int i = lane; i < nd.n_edges; i += 64)
+				{
+					const float value = best_edge_rating(edges[nd.edge_begin + i], nd);
+					if (value > pv_value)
+					{
+						pv_value = value;
+						pv_best = i;
+					}
+				}
+				wave_argmax(pv_value, pv_best);
+				if (pv_best >= nd.n_edges)
+					break;
+				const uint16_t move = edges[nd.edge_begin + pv_best].move;
+				if (lane == 0 && o.pv != nullptr)
+					o.pv[static_cast<size_t>(p) * J.max_pv + length] = move;
+				query_place(E, sh_cboard, q, move, lane);
+				length++;
+			}
+			if (o.pv != nullptr)
+				for (int i = length + lane; i < J.max_pv; i += 64)
+					o.pv[static_cast<size_t>(p) * J.max_pv + i] = 0;
+			if (lane == 0 && o.pv_length != nullptr)
+				o.pv_length[p] = length;
+		}
+		__syncthreads();
+		if (lane == 0)
+		{ // a finished game: nothing in flight, waiting (restart_id -1) — k_arena_service takes a grown bundle back, k_load_positions the slot
+			gs.active = 0;
+			gs.need_move = 0;
+			gs.n_tasks = 0;
+			gs.solve_pos = 0;
+			gs.solve_pending = 0;
+			park_forget_game(E, g);
+			gs.grow_pending = 0;
+			gs.root = -1;
+			gs.restart_id = -1;
+			gs.games_done++;
+			J.slot_steps[g] = steps;
+			J.slot_position[g] = -1;
+			atomicAdd(J.finished, 1);
+		}
+	}
+
 	/* debug / test kernels --------------------------------------------------------------------------------------- */
 	__global__ __launch_bounds__(64) void k_debug_load_tasks(EngineDev E, const uint8_t *boards, const int *signs, int count)
 	{ // makes every game look as if one fresh leaf had been selected: task 0 = given position
@@ -5546,6 +5990,373 @@ int agx_position_solver_solve(AgxPositionSolver *ps, int n, const uint8_t *d_boa
 	ps->launched = true;
 	ps->last_stream = stream;
 	AGX_HIP_CHECK(launched);
+	return AGX_OK;
+}
+
+} /* extern "C" */
+
+/* ================================================================================================================ */
+/* agx_position_searcher_*: the whole search on boards (k_load_positions / k_harvest_positions around the engine's own stages) */
+struct AgxPositionSearcher
+{
+		AgxEngine *engine = nullptr;
+		int slots = 0, device = -1;
+		std::mutex mutex;
+		PositionJob job;      // the job in flight (device addresses); cursor / finished / slot_* are the searcher's own
+		int *state = nullptr;      // device: cursor, finished, slot_position[slots], slot_steps[slots]
+		int *poll_host = nullptr;  // pinned: two finished counts on their way back (search), then slot_position[slots] (slots)
+		hipEvent_t poll_event[2] = { nullptr, nullptr };
+		int job_n = 0;             // positions of the job in flight, 0 = none
+		int job_finished = 0;      // ... of which known to be finished
+		unsigned long long device_bytes = 0;
+		// the calls of one searcher share its pool: a call on another stream than the previous one is ordered behind it on the device
+		hipEvent_t done = nullptr;
+		hipStream_t last_stream = nullptr;
+		bool launched = false;
+};
+
+namespace
+{
+	int searcher_enter(AgxPositionSearcher *ps, hipStream_t stream, const char *what)
+	{ // (under the searcher's mutex) the calling thread's device, and the order behind the previous call's stream
+		int current = -1;
+		AGX_HIP_CHECK(hipGetDevice(&current));
+		AGX_REQUIRE(current == ps->device, AGX_ERR_STATE, "%s: the searcher lives on device %d, the calling thread's current device is %d", what, ps->device, current);
+		if (ps->launched && ps->last_stream != stream)
+			AGX_HIP_CHECK(hipStreamWaitEvent(stream, ps->done, 0));
+		return AGX_OK;
+	}
+	int searcher_leave(AgxPositionSearcher *ps, hipStream_t stream, int status)
+	{
+		const hipError_t launched = hipGetLastError();
+		AGX_HIP_CHECK(hipEventRecord(ps->done, stream));
+		ps->launched = true;
+		ps->last_stream = stream;
+		AGX_HIP_CHECK(launched);
+		return status;
+	}
+	EngineDev searcher_dev(const AgxPositionSearcher *ps)
+	{ // the pool as one group (agx_engine_*_group(e, 0, 1)); the engine's own record keeps what set_max_simulations / set_batch_size changed
+		EngineDev d = ps->engine->dev;
+		d.g0 = 0;
+		d.nn_counter = 16;
+		d.yield_counter = 32;
+		d.grp_first = 0;
+		d.grp_count = d.n_games;
+		return d;
+	}
+	int searcher_default_steps(const AgxPositionSearcher *ps)
+	{ // agx.h: agx_position_searcher_begin
+		const EngineDev &d = ps->engine->dev;
+		const long long steps = (static_cast<long long>(d.max_sims) + 2) * (2 * d.batch + 1) + ARENA_CLASSES;
+		return static_cast<int>(std::min<long long>(steps, 0x7FFFFFF0));
+	}
+	/* (under the mutex) is the job in flight finished?  Asks the device when the host does not know yet: waits for the previous call's stream only */
+	int searcher_job_open(AgxPositionSearcher *ps, bool *open)
+	{
+		*open = false;
+		if (ps->job_n == 0 || ps->job_finished >= ps->job_n)
+			return AGX_OK;
+		if (ps->launched)
+			AGX_HIP_CHECK(hipEventSynchronize(ps->done));
+		int finished = 0;
+		AGX_HIP_CHECK(hipMemcpy(&finished, ps->job.finished, sizeof(int), hipMemcpyDeviceToHost));
+		ps->job_finished = finished;
+		*open = finished < ps->job_n;
+		return AGX_OK;
+	}
+	int searcher_begin_locked(AgxPositionSearcher *ps, int n, const uint8_t *d_boards, const uint8_t *d_signs, const int32_t *d_serials,
+			const AgxPositionSearchOutputs *out, int max_pv, int max_steps, hipStream_t stream)
+	{
+		bool open = false;
+		const int st = searcher_job_open(ps, &open);
+		if (st != AGX_OK)
+			return st;
+		AGX_REQUIRE(!open, AGX_ERR_STATE, "agx_position_searcher_begin: the previous job has finished %d of its %d positions", ps->job_finished, ps->job_n);
+		const int entered = searcher_enter(ps, stream, "agx_position_searcher_begin");
+		if (entered != AGX_OK)
+			return entered;
+		ps->job.boards = d_boards;
+		ps->job.signs = d_signs;
+		ps->job.serials = d_serials;
+		ps->job.n = n;
+		ps->job.max_pv = max_pv;
+		ps->job.max_steps = (max_steps > 0) ? max_steps : searcher_default_steps(ps);
+		ps->job.out = *out;
+		ps->job_n = n;
+		ps->job_finished = 0;
+		const EngineDev d = searcher_dev(ps);
+		hipLaunchKernelGGL(k_positions_reset, dim3(1), dim3(1), 0, stream, ps->job);
+		hipLaunchKernelGGL(k_load_positions, dim3(ps->slots), dim3(256), 0, stream, d, ps->job);
+		return searcher_leave(ps, stream, AGX_OK);
+	}
+	int searcher_begin_checks(AgxPositionSearcher *ps, int n, const uint8_t *d_boards, const uint8_t *d_signs, const AgxPositionSearchOutputs *out, int max_pv, const char *what)
+	{
+		AGX_REQUIRE(ps != nullptr && out != nullptr, AGX_ERR_INVALID, "%s: null argument", what);
+		AGX_REQUIRE(n >= 0, AGX_ERR_INVALID, "%s: %d positions", what, n);
+		AGX_REQUIRE(max_pv >= 0 && max_pv <= MAXHW, AGX_ERR_INVALID, "%s: max_pv %d outside [0, %d]", what, max_pv, MAXHW);
+		AGX_REQUIRE(n == 0 || (d_boards != nullptr && d_signs != nullptr), AGX_ERR_INVALID, "%s: null boards or signs", what);
+		return AGX_OK;
+	}
+	int searcher_harvest_locked(AgxPositionSearcher *ps, hipStream_t stream)
+	{ // harvest -> arena service -> load: ordered by the launch order on one stream, as the stages behind k_advance are
+		const EngineDev d = searcher_dev(ps);
+		hipLaunchKernelGGL(k_harvest_positions, dim3(ps->slots), dim3(64), 0, stream, d, ps->job);
+		hipLaunchKernelGGL(k_arena_service, dim3(1), dim3(1024), 0, stream, d, ps->slots, 0);
+		hipLaunchKernelGGL(k_arena_copy, dim3(ps->slots * CLEAR_PARTS), dim3(256), 0, stream, d, CLEAR_PARTS); // (its last part per game commits)
+		hipLaunchKernelGGL(k_load_positions, dim3(ps->slots), dim3(256), 0, stream, d, ps->job);
+		return AGX_OK;
+	}
+}
+
+extern "C" {
+
+int agx_position_searcher_create(const AgxEngineConfig *cfg, AgxPositionSearcher **out)
+{
+	AGX_REQUIRE(cfg != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_position_searcher_create: null argument");
+	*out = nullptr;
+	AGX_REQUIRE(!cfg->match_mode, AGX_ERR_UNSUPPORTED, "agx_position_searcher_create: match_mode pools play matches, they search no positions");
+	AGX_REQUIRE(cfg->search_threads <= 1 && cfg->search_buffers <= 1, AGX_ERR_UNSUPPORTED,
+			"agx_position_searcher_create: search_threads > 1 / search_buffers > 1 make the pool one tree; the searcher needs a tree per slot");
+	AgxEngineConfig own = *cfg;
+	own.record_format = 0; // nothing is played: no move records, no samples, no finished games
+	own.record_capacity = 1;
+	own.record_edge_capacity = 1;
+	own.record_sample_capacity = 4;
+	own.game_end_capacity = 1;
+	AgxEngine *engine = nullptr;
+	const int created = agx_engine_create(&own, &engine);
+	if (created != AGX_OK)
+		return created;
+	AgxPositionSearcher *ps = new AgxPositionSearcher();
+	ps->engine = engine;
+	ps->slots = cfg->n_games;
+	std::memset(&ps->job, 0, sizeof(ps->job));
+	const size_t words = 2 + 2 * static_cast<size_t>(ps->slots);
+	int status = AGX_OK;
+	if (hipGetDevice(&ps->device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&ps->state), words * sizeof(int)) != hipSuccess
+			|| hipHostMalloc(reinterpret_cast<void**>(&ps->poll_host), (2 + static_cast<size_t>(ps->slots)) * sizeof(int)) != hipSuccess
+			|| hipEventCreateWithFlags(&ps->done, hipEventDisableTiming) != hipSuccess
+			|| hipEventCreateWithFlags(&ps->poll_event[0], hipEventDisableTiming) != hipSuccess
+			|| hipEventCreateWithFlags(&ps->poll_event[1], hipEventDisableTiming) != hipSuccess)
+	{
+		(void) hipGetLastError();
+		agx::set_error("agx_position_searcher_create: allocating the slot records failed");
+		status = AGX_ERR_HIP;
+	}
+	if (status == AGX_OK)
+	{
+		ps->job.cursor = ps->state;
+		ps->job.finished = ps->state + 1;
+		ps->job.slot_position = ps->state + 2;
+		ps->job.slot_steps = ps->state + 2 + ps->slots;
+		ps->device_bytes = engine->device_bytes + words * sizeof(int);
+		hipLaunchKernelGGL(k_positions_init, dim3(ps->slots), dim3(64), 0, nullptr, engine->dev, ps->job);
+		if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)
+		{
+			(void) hipGetLastError();
+			agx::set_error("agx_position_searcher_create: the launch that idles the slots failed");
+			status = AGX_ERR_HIP;
+		}
+		engine->begun = true; // (the staged calls are the engine's own; its slots take positions where a pool takes openings)
+	}
+	if (status != AGX_OK)
+	{
+		const std::string message = agx_last_error();
+		agx_position_searcher_destroy(ps);
+		agx::set_error("%s", message.c_str());
+		return status;
+	}
+	*out = ps;
+	return AGX_OK;
+}
+
+int agx_position_searcher_destroy(AgxPositionSearcher *ps)
+{
+	if (ps == nullptr)
+		return AGX_OK;
+	if (ps->launched)
+		(void) hipEventSynchronize(ps->done);
+	if (ps->state != nullptr)
+		(void) hipFree(ps->state);
+	if (ps->poll_host != nullptr)
+		(void) hipHostFree(ps->poll_host);
+	for (hipEvent_t ev : { ps->done, ps->poll_event[0], ps->poll_event[1] })
+		if (ev != nullptr)
+			(void) hipEventDestroy(ev);
+	(void) agx_engine_destroy(ps->engine);
+	delete ps;
+	return AGX_OK;
+}
+
+int agx_position_searcher_info(const AgxPositionSearcher *ps, int *slots, uint64_t *device_bytes)
+{
+	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "agx_position_searcher_info: null searcher");
+	if (slots != nullptr)
+		*slots = ps->slots;
+	if (device_bytes != nullptr)
+		*device_bytes = ps->device_bytes;
+	return AGX_OK;
+}
+
+int agx_position_searcher_engine(AgxPositionSearcher *ps, AgxEngine **out)
+{
+	AGX_REQUIRE(ps != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_position_searcher_engine: null argument");
+	*out = ps->engine;
+	return AGX_OK;
+}
+
+int agx_position_searcher_begin(AgxPositionSearcher *ps, int n, const uint8_t *d_boards, const uint8_t *d_signs, const int32_t *d_serials,
+		const AgxPositionSearchOutputs *out, int max_pv, int max_steps, void *stream)
+{
+	const int st = searcher_begin_checks(ps, n, d_boards, d_signs, out, max_pv, "agx_position_searcher_begin");
+	if (st != AGX_OK || n == 0)
+		return st;
+	std::lock_guard<std::mutex> lock(ps->mutex);
+	return searcher_begin_locked(ps, n, d_boards, d_signs, d_serials, out, max_pv, max_steps, static_cast<hipStream_t>(stream));
+}
+
+int agx_position_searcher_select_solve(AgxPositionSearcher *ps, void *stream)
+{
+	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "agx_position_searcher_select_solve: null searcher");
+	std::lock_guard<std::mutex> lock(ps->mutex);
+	const int st = searcher_enter(ps, static_cast<hipStream_t>(stream), "agx_position_searcher_select_solve");
+	if (st != AGX_OK)
+		return st;
+	return searcher_leave(ps, static_cast<hipStream_t>(stream), agx_engine_select_solve_group(ps->engine, 0, 1, stream));
+}
+
+int agx_position_searcher_buffers(AgxPositionSearcher *ps, AgxEngineBuffers *out)
+{
+	AGX_REQUIRE(ps != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_position_searcher_buffers: null argument");
+	return agx_engine_buffers(ps->engine, out);
+}
+
+int agx_position_searcher_evaluate(AgxPositionSearcher *ps, AgxNet *net, void *stream)
+{
+	AGX_REQUIRE(ps != nullptr && net != nullptr, AGX_ERR_INVALID, "agx_position_searcher_evaluate: null argument");
+	std::lock_guard<std::mutex> lock(ps->mutex);
+	const int st = searcher_enter(ps, static_cast<hipStream_t>(stream), "agx_position_searcher_evaluate");
+	if (st != AGX_OK)
+		return st;
+	return searcher_leave(ps, static_cast<hipStream_t>(stream), agx_engine_evaluate_group(ps->engine, net, 0, 1, stream));
+}
+
+int agx_position_searcher_expand(AgxPositionSearcher *ps, void *stream)
+{
+	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "agx_position_searcher_expand: null searcher");
+	std::lock_guard<std::mutex> lock(ps->mutex);
+	const int st = searcher_enter(ps, static_cast<hipStream_t>(stream), "agx_position_searcher_expand");
+	if (st != AGX_OK)
+		return st;
+	return searcher_leave(ps, static_cast<hipStream_t>(stream), expand_stage(ps->engine, 0, 1, stream, false)); // (the harvest stage services the arenas)
+}
+
+int agx_position_searcher_harvest(AgxPositionSearcher *ps, void *stream)
+{
+	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "agx_position_searcher_harvest: null searcher");
+	std::lock_guard<std::mutex> lock(ps->mutex);
+	const int st = searcher_enter(ps, static_cast<hipStream_t>(stream), "agx_position_searcher_harvest");
+	if (st != AGX_OK)
+		return st;
+	return searcher_leave(ps, static_cast<hipStream_t>(stream), searcher_harvest_locked(ps, static_cast<hipStream_t>(stream)));
+}
+
+int agx_position_searcher_slots(AgxPositionSearcher *ps, void *stream, int *h_position_of_slot)
+{
+	AGX_REQUIRE(ps != nullptr && h_position_of_slot != nullptr, AGX_ERR_INVALID, "agx_position_searcher_slots: null argument");
+	std::lock_guard<std::mutex> lock(ps->mutex);
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	const int st = searcher_enter(ps, s, "agx_position_searcher_slots");
+	if (st != AGX_OK)
+		return st;
+	AGX_HIP_CHECK(hipMemcpyAsync(ps->poll_host + 2, ps->job.slot_position, ps->slots * sizeof(int), hipMemcpyDeviceToHost, s));
+	AGX_HIP_CHECK(hipStreamSynchronize(s));
+	std::memcpy(h_position_of_slot, ps->poll_host + 2, ps->slots * sizeof(int));
+	return AGX_OK;
+}
+
+int agx_position_searcher_finished(AgxPositionSearcher *ps, void *stream, int *count)
+{
+	AGX_REQUIRE(ps != nullptr && count != nullptr, AGX_ERR_INVALID, "agx_position_searcher_finished: null argument");
+	std::lock_guard<std::mutex> lock(ps->mutex);
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	const int st = searcher_enter(ps, s, "agx_position_searcher_finished");
+	if (st != AGX_OK)
+		return st;
+	if (ps->job_n == 0)
+	{
+		*count = 0;
+		return AGX_OK;
+	}
+	AGX_HIP_CHECK(hipMemcpyAsync(ps->poll_host, ps->job.finished, sizeof(int), hipMemcpyDeviceToHost, s));
+	AGX_HIP_CHECK(hipStreamSynchronize(s));
+	ps->job_finished = ps->poll_host[0];
+	*count = ps->job_finished;
+	return AGX_OK;
+}
+
+int agx_position_searcher_search(AgxPositionSearcher *ps, AgxNet *net, int n, const uint8_t *d_boards, const uint8_t *d_signs, const int32_t *d_serials,
+		const AgxPositionSearchOutputs *out, int max_pv, int max_steps, void *stream_)
+{
+	const int checked = searcher_begin_checks(ps, n, d_boards, d_signs, out, max_pv, "agx_position_searcher_search");
+	if (checked != AGX_OK)
+		return checked;
+	AGX_REQUIRE(net != nullptr, AGX_ERR_INVALID, "agx_position_searcher_search: null network");
+	if (n == 0)
+		return AGX_OK;
+	hipStream_t stream = static_cast<hipStream_t>(stream_);
+	std::lock_guard<std::mutex> lock(ps->mutex);
+	int st = searcher_begin_locked(ps, n, d_boards, d_signs, d_serials, out, max_pv, max_steps, stream);
+	if (st != AGX_OK)
+		return st;
+	// every position finishes within max_steps steps of its load, a slot loads a new one in the step that finishes the old one: the slots work
+	// through the list in at most ceil(n / slots) rounds of max_steps steps
+	const long long rounds = (static_cast<long long>(n) + ps->slots - 1) / ps->slots;
+	const long long step_bound = rounds * ps->job.max_steps + 1;
+	constexpr int POLL_EVERY = 4; // steps between two reads of the finished counter; the read of the previous poll is awaited, so POLL_EVERY steps stay queued
+	int polls = 0;
+	bool all_finished = false;
+	for (long long step = 0; !all_finished && step < step_bound + 2 * POLL_EVERY; step++)
+	{
+		st = agx_engine_select_solve_group(ps->engine, 0, 1, stream_);
+		if (st == AGX_OK)
+			st = agx_engine_evaluate_group(ps->engine, net, 0, 1, stream_);
+		if (st == AGX_OK)
+			st = expand_stage(ps->engine, 0, 1, stream_, false);
+		if (st == AGX_OK)
+			st = searcher_harvest_locked(ps, stream);
+		if (st != AGX_OK)
+			break;
+		if ((step + 1) % POLL_EVERY != 0)
+			continue;
+		const int slot = polls & 1;
+		if (hipMemcpyAsync(ps->poll_host + slot, ps->job.finished, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess
+				|| hipEventRecord(ps->poll_event[slot], stream) != hipSuccess)
+		{
+			agx::set_error("agx_position_searcher_search: queuing a read of the finished counter failed: %s", hipGetErrorString(hipGetLastError()));
+			st = AGX_ERR_HIP;
+			break;
+		}
+		polls++;
+		if (polls >= 2)
+		{ // the poll before this one: its steps were queued POLL_EVERY steps ago
+			st = agx_event_synchronize(ps->poll_event[slot ^ 1]);
+			if (st != AGX_OK)
+				break;
+			ps->job_finished = ps->poll_host[slot ^ 1];
+			all_finished = ps->job_finished >= n;
+		}
+	}
+	(void) searcher_leave(ps, stream, AGX_OK);
+	const hipError_t drained = hipStreamSynchronize(stream);
+	if (st != AGX_OK)
+		return st;
+	AGX_HIP_CHECK(drained);
+	int finished = 0;
+	AGX_HIP_CHECK(hipMemcpy(&finished, ps->job.finished, sizeof(int), hipMemcpyDeviceToHost));
+	ps->job_finished = finished;
+	AGX_REQUIRE(finished >= n, AGX_ERR_STATE, "agx_position_searcher_search: %d of %d positions finished within the step bound", finished, n);
 	return AGX_OK;
 }
 

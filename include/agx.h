@@ -845,6 +845,93 @@ int agx_position_evaluator_evaluate_solved(AgxPositionEvaluator* pe, AgxPosition
 		const uint8_t* d_signs, int symmetry_mask, int flags, int top_k, const AgxPositionOutputs* out, const AgxSolvedPositions* solved_out,
 		void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Positions searched on the device: boards -> the root of a full search (PUCT, threat solver and network together, max_simulations
+ * playouts per position; k_load_positions / k_harvest_positions, csrc/engine.hip).  Re-searching old samples with a newer network, puzzle
+ * suites, opening checks, a move for a mid-game position at full search strength.
+ *
+ * Position i = (board[i], sign_to_move[i], serial[i], default 0) is searched exactly as a freshly created self-play GameGenerator would
+ * search for its first move after an opening that produced this board: empty tree, empty solver table, the solver's generation counting
+ * from 0 (the first search makes it 1), nn_queued 0, serial[i] as the noise / symmetry serial, move number = stones on the board, under the
+ * AgxEngineConfig of agx_position_searcher_create.  The search ends when the engine's own move rule fires (root proven, or more root visits
+ * than get_simulations_for_move allows); the result is the root at that moment — what the game's first AgxMoveRecord and root-edge snapshot
+ * would hold.  Nothing is played.  The result is a function of the position, its serial and the configuration alone: not of the batch, of
+ * the position's place in it, of the number of slots, of the slot that took it or of what that slot searched before.  One exception: the
+ * arena reserve is shared by the pool, so whether a tree that outgrows every arena ends with status 2 can depend on its neighbours.
+ * A position that is already decided (five in a row on the board) is NOT detected (Tree::setBoard does not detect it either): it is
+ * searched like any other.
+ *
+ * The pool has cfg.n_games slots.  A free slot takes the next position off a device-side cursor, a slot whose search has ended writes its
+ * outputs and is free again in the same step; the host only launches steps.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct AgxPositionSearcher AgxPositionSearcher;
+
+enum
+{ /* status words */
+	AGX_POSSEARCH_STATUS_BAD_INPUT = 1,    /* a cell value above 2 or a sign other than 1 / 2: zeroed outputs, no edge (edge_index -1), nothing was searched */
+	AGX_POSSEARCH_STATUS_ENGINE_ERROR = 2, /* the slot's engine error word was set (info[3]; e.g. the arena reserve ran out): zeroed outputs but info */
+	AGX_POSSEARCH_STATUS_STEP_LIMIT = 3    /* max_steps steps without the move rule firing: the root as it stands (leaves in flight dropped, their
+	                                          virtual losses taken back), or zeros with n_edges 0 when there is no root yet */
+};
+
+typedef struct AgxPositionSearchOutputs
+{ /* device addresses; any of them may be NULL.  `cells` = board_size^2; rows are always written whole */
+	int32_t* status;      /* [n] 0 searched, or AGX_POSSEARCH_STATUS_* */
+	int32_t* root;        /* [n][4] root visits, root Score raw bits, root flags as AgxMoveRecord.root_flags, number of root edges */
+	float* root_value;    /* [n][2] (win, draw) of the root node */
+	uint16_t* best_move;  /* [n] the pick of cfg.final_selector (Move::toShort; the engine's own code path and tie rule), 0 without edges */
+	int32_t* visits;      /* [n][cells] per cell: the root edge on that cell; 0 / 0.0f where the root has no edge */
+	float* prior;         /* [n][cells] */
+	float* q;             /* [n][cells][2] (win, draw) */
+	uint16_t* score;      /* [n][cells] Score raw bits */
+	int16_t* edge_index;  /* [n][cells] the cell's place in the root's edge order, -1 where the root has no edge */
+	uint16_t* pv;         /* [n][max_pv] the walk of agx_engine_principal_variation from the root, zeros behind it */
+	int32_t* pv_length;   /* [n] */
+	int32_t* info;        /* [n][4] nodes in the tree, edges in the tree, steps the slot spent on the position, engine error code */
+} AgxPositionSearchOutputs;
+
+/* cfg->n_games is the number of slots.  AGX_ERR_UNSUPPORTED: match_mode, search_threads > 1, search_buffers > 1; everything else as
+ * agx_engine_create refuses it.  The searcher owns an AgxEngine (its record pools are kept at their minimum: nothing is recorded). */
+int agx_position_searcher_create(const AgxEngineConfig* cfg, AgxPositionSearcher** out);
+int agx_position_searcher_destroy(AgxPositionSearcher* ps);
+/* slots and everything the searcher allocated on the device; either output may be NULL */
+int agx_position_searcher_info(const AgxPositionSearcher* ps, int* slots, uint64_t* device_bytes);
+/* The owned engine, for agx_engine_stats, agx_engine_set_max_simulations and agx_engine_set_batch_size ONLY (and the read-only queries
+ * agx_engine_game_info / agx_engine_principal_variation of a slot between two stages): stepping it, agx_engine_begin or agx_engine_set_board
+ * on it break the searcher. */
+int agx_position_searcher_engine(AgxPositionSearcher* ps, AgxEngine** out);
+/* Records the job — d_boards uint8[n][cells] (0 empty, 1 cross, 2 circle), d_signs uint8[n] (1 cross / 2 circle to move), d_serials
+ * int32[n] or NULL (all 0), the outputs, max_pv plies of principal variation per position — and loads the first positions into the slots.
+ * Launches on `stream`, nothing synchronised; the arrays must stay valid until the job has finished.  n == 0 is a valid no-op (nothing is
+ * launched, nothing written).  max_steps <= 0 selects the default
+ *     (max_simulations + 2) * (2 * max_batch_size + 1) + 6
+ * steps per position: a search adds a root visit in every step that expands a batch, the move rule fires after at most
+ * max_simulations + 2 of them, a batch reaches its expand stage after at most max_batch_size solver launches that yield (each solves at
+ * least one leaf) plus max_batch_size launches that park a solve (each solve is parked at most once) plus its own, and a tree changes its
+ * arena class at most 5 times at one step each (and one step to spare).  AGX_ERR_INVALID: a null searcher or `out`, n or max_pv negative, null boards or signs
+ * with n > 0; AGX_ERR_STATE: the previous job has not finished. */
+int agx_position_searcher_begin(AgxPositionSearcher* ps, int n, const uint8_t* d_boards, const uint8_t* d_signs, const int32_t* d_serials,
+		const AgxPositionSearchOutputs* out, int max_pv, int max_steps, void* stream);
+/* One step in stages, for callers with an evaluator of their own: select_solve (agx_engine_select_solve), then the positions listed in
+ * agx_position_searcher_buffers (the engine's AgxEngineBuffers) are evaluated — by the caller, or by _evaluate with a network —, then
+ * expand (agx_engine_expand_group without its arena service), then harvest: the slots whose search has ended write their outputs, grown
+ * arenas are serviced and free slots take the next positions.  All launches on `stream`, nothing synchronised. */
+int agx_position_searcher_select_solve(AgxPositionSearcher* ps, void* stream);
+int agx_position_searcher_buffers(AgxPositionSearcher* ps, AgxEngineBuffers* out);
+int agx_position_searcher_evaluate(AgxPositionSearcher* ps, AgxNet* net, void* stream);
+int agx_position_searcher_expand(AgxPositionSearcher* ps, void* stream);
+int agx_position_searcher_harvest(AgxPositionSearcher* ps, void* stream);
+/* the position every slot works on, -1 for a free slot: int[slots]; waits for `stream` only */
+int agx_position_searcher_slots(AgxPositionSearcher* ps, void* stream, int* h_position_of_slot);
+/* positions of the job whose outputs are written; waits for `stream` only */
+int agx_position_searcher_finished(AgxPositionSearcher* ps, void* stream, int* count);
+/* begin, then whole steps with `net` until all n positions are finished.  The finished counter is read behind the stream every few steps
+ * (the host sleeps between polls as agx_event_synchronize does, a few steps stay queued meanwhile); no device-wide synchronisation; the
+ * stream is drained on return.  The loop ends: every position finishes or reaches its step limit. */
+int agx_position_searcher_search(AgxPositionSearcher* ps, AgxNet* net, int n, const uint8_t* d_boards, const uint8_t* d_signs,
+		const int32_t* d_serials, const AgxPositionSearchOutputs* out, int max_pv, int max_steps, void* stream);
+/* Calls on one searcher share its pool: a call on another stream than the previous one is ordered behind it on the device. */
+
 /* Raw device-memory helpers so that non-HIP hosts (ctypes, cgo) can stage buffers. */
 int agx_malloc(void** d_ptr, size_t bytes);
 int agx_free(void* d_ptr);

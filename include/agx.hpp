@@ -704,6 +704,92 @@ namespace agx
 	{
 		check(agx_position_evaluator_evaluate_solved(m_evaluator, solver.handle(), net.handle(), n, d_boards, d_signs, symmetry_mask, flags, top_k, &out, solved, stream));
 	}
+
+	/* The whole search on boards (agx.h: agx_position_searcher_*): every position searched as a fresh self-play GameGenerator would search
+	 * for its first move, cfg.n_games slots that take positions off a device-side list.  All pointers are device addresses; search() returns
+	 * with the stream drained, the staged calls only enqueue on `stream`. */
+	class PositionSearcher
+	{
+			AgxPositionSearcher *m_searcher = nullptr;
+		public:
+			explicit PositionSearcher(const AgxEngineConfig &cfg)
+			{
+				check(agx_position_searcher_create(&cfg, &m_searcher));
+			}
+			PositionSearcher(const PositionSearcher&) = delete;
+			PositionSearcher& operator=(const PositionSearcher&) = delete;
+			~PositionSearcher()
+			{
+				agx_position_searcher_destroy(m_searcher);
+			}
+			/* any pointer of `out` may be null; d_serials may be null (all 0); max_steps <= 0: the default of agx.h */
+			void search(const AGNetwork &net, int n, const uint8_t *d_boards, const uint8_t *d_signs, const AgxPositionSearchOutputs &out, const int32_t *d_serials = nullptr,
+					int max_pv = 8, int max_steps = 0, void *stream = nullptr)
+			{
+				check(agx_position_searcher_search(m_searcher, net.handle(), n, d_boards, d_signs, d_serials, &out, max_pv, max_steps, stream));
+			}
+			void begin(int n, const uint8_t *d_boards, const uint8_t *d_signs, const AgxPositionSearchOutputs &out, const int32_t *d_serials = nullptr, int max_pv = 8,
+					int max_steps = 0, void *stream = nullptr)
+			{
+				check(agx_position_searcher_begin(m_searcher, n, d_boards, d_signs, d_serials, &out, max_pv, max_steps, stream));
+			}
+			void select_solve(void *stream = nullptr)
+			{
+				check(agx_position_searcher_select_solve(m_searcher, stream));
+			}
+			AgxEngineBuffers buffers() const
+			{
+				AgxEngineBuffers b;
+				check(agx_position_searcher_buffers(m_searcher, &b));
+				return b;
+			}
+			void evaluate(const AGNetwork &net, void *stream = nullptr)
+			{
+				check(agx_position_searcher_evaluate(m_searcher, net.handle(), stream));
+			}
+			void expand(void *stream = nullptr)
+			{
+				check(agx_position_searcher_expand(m_searcher, stream));
+			}
+			void harvest(void *stream = nullptr)
+			{
+				check(agx_position_searcher_harvest(m_searcher, stream));
+			}
+			/* the position every slot works on (-1: free), int[slots()]; waits for `stream` only */
+			void slot_positions(int *h_position_of_slot, void *stream = nullptr)
+			{
+				check(agx_position_searcher_slots(m_searcher, stream, h_position_of_slot));
+			}
+			int finished(void *stream = nullptr)
+			{
+				int count = 0;
+				check(agx_position_searcher_finished(m_searcher, stream, &count));
+				return count;
+			}
+			int slots() const
+			{
+				int s = 0;
+				check(agx_position_searcher_info(m_searcher, &s, nullptr));
+				return s;
+			}
+			uint64_t device_bytes() const
+			{
+				uint64_t bytes = 0;
+				check(agx_position_searcher_info(m_searcher, nullptr, &bytes));
+				return bytes;
+			}
+			/* the owned engine: agx_engine_stats, agx_engine_set_max_simulations and agx_engine_set_batch_size only */
+			AgxEngine* engine() const
+			{
+				AgxEngine *e = nullptr;
+				check(agx_position_searcher_engine(m_searcher, &e));
+				return e;
+			}
+			AgxPositionSearcher* handle() const noexcept
+			{
+				return m_searcher;
+			}
+	};
 }
 
 #endif /* AGX_HPP_ */
