@@ -289,7 +289,19 @@ class AgxTensorShape(ctypes.Structure):
     _fields_ = [("rank", ctypes.c_int), ("dim", ctypes.c_int * 4)]
 
 
-BATCH_INPUT_FP16, BATCH_POLICY_VISITS = 1, 2
+BATCH_INPUT_FP16, BATCH_POLICY_VISITS, BATCH_POLICY_VALUES = 1, 2, 4
+BATCH_POLICY_FLAGS = {"torch_api": 0, "visits": BATCH_POLICY_VISITS, "values": BATCH_POLICY_VALUES}
+
+
+class AgxBatchTensors(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ["input", "features", "policy", "value", "moves_left", "action_values", "action_values_weight"]]
+
+
+def batch_policy_flag(policy):
+    """the AGX_BATCH_POLICY_* flag of a policy= argument"""
+    if policy not in BATCH_POLICY_FLAGS:
+        raise ValueError("policy must be 'torch_api', 'visits' or 'values'")
+    return BATCH_POLICY_FLAGS[policy]
 
 _declare_engine = _declare
 
@@ -311,6 +323,8 @@ def _declare(c):  # noqa: F811
     c.agx_dataset_tensor_shapes.argtypes = [vp, ci] + [shape] * 6
     c.agx_dataset_load_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp]
     c.agx_dataset_load_batch_host.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, ci]
+    c.agx_dataset_load_batch_ex.argtypes = [vp, ci, vp, ctypes.POINTER(AgxBatchTensors), ci, vp]
+    c.agx_dataset_load_batch_host_ex.argtypes = [vp, ci, vp, ctypes.POINTER(AgxBatchTensors), ci]
 
 
 class AgxSampleScore(ctypes.Structure):
@@ -332,6 +346,8 @@ def _declare(c):  # noqa: F811
     c.agx_net_score_clear.argtypes = [vp, vp]
     c.agx_net_score_outputs.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     c.agx_net_score_dataset.argtypes = [vp, vp, ci, vp, ci, ctypes.POINTER(AgxNetScore), vp]
+    c.agx_net_score_outputs_weighted.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    c.agx_net_score_dataset_ex.argtypes = [vp, vp, ci, vp, ci, ci, ci, ctypes.POINTER(AgxNetScore), vp]
 
 
 class AgxPositionOutputs(ctypes.Structure):
@@ -362,6 +378,7 @@ def _declare(c):  # noqa: F811
     _declare_position(c)
     vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     c.agx_head_loss_grad.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, cf, cf, cf, vp, vp, vp, vp, vp, vp]
+    c.agx_head_loss_grad_weighted.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, cf, cf, cf, vp, vp, vp, vp, vp, vp]
 
 
 class AgxSolvedPositions(ctypes.Structure):

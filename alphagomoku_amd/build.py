@@ -25,6 +25,8 @@ SCORE_TEST = os.path.join(HERE, "agx_net_score_test")  # tests/cpp/net_score_mai
 SCORE_SRC = os.path.join(HERE, "..", "tests", "cpp", "net_score_main.cpp")
 POSITION_TEST = os.path.join(HERE, "agx_position_eval_test")  # tests/cpp/position_eval_main.cpp: ag::AGNetwork::packInputData(index, board, sign)
 POSITION_SRC = os.path.join(HERE, "..", "tests", "cpp", "position_eval_main.cpp")
+TARGETS_TEST = os.path.join(HERE, "agx_training_targets_test")  # tests/cpp/training_targets_main.cpp: the values targets and the weighted loss through agx.hpp
+TARGETS_SRC = os.path.join(HERE, "..", "tests", "cpp", "training_targets_main.cpp")
 HOST_ONLY = ("ag_classes.cpp", "selfplay_main.cpp")  # plain g++ sources in csrc/ (not part of libagx.so)
 
 
@@ -92,6 +94,8 @@ def _stale_host_targets():
         out.append(SCORE_TEST)
     if _mtime(POSITION_TEST) < max(_mtime(POSITION_SRC), headers, _mtime(AG_LIB)) or AG_LIB in out:
         out.append(POSITION_TEST)
+    if _mtime(TARGETS_TEST) < max(_mtime(TARGETS_SRC), headers, _mtime(LIB)):
+        out.append(TARGETS_TEST)
     return out
 
 
@@ -156,7 +160,7 @@ def build(force=False, verbose=True):
         relink = True
     if relink:
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + [BUILD_ID_OBJ, "-lz"])
-    stale = [DRIVER, AG_LIB, BOUNDARY_TEST, TRAINING_TEST, SCORE_TEST, POSITION_TEST] if force else _stale_host_targets()
+    stale = [DRIVER, AG_LIB, BOUNDARY_TEST, TRAINING_TEST, SCORE_TEST, POSITION_TEST, TARGETS_TEST] if force else _stale_host_targets()
     if DRIVER in stale:  # native C++ host driver over the C ABI (include/agx.hpp)
         run([cxx, "-std=c++17", "-O2", "-o", DRIVER, os.path.join(CSRC, "selfplay_main.cpp"), "-L" + HERE, "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     if AG_LIB in stale:  # the C++ boundary: plain host code (g++), no HIP types — a maintainer of the reference links it like any other library
@@ -170,6 +174,8 @@ def build(force=False, verbose=True):
         run([cxx, "-std=c++17", "-O2", "-Wall", "-o", SCORE_TEST, SCORE_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     if POSITION_TEST in stale:
         run([cxx, "-std=c++17", "-O2", "-Wall", "-o", POSITION_TEST, POSITION_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
+    if TARGETS_TEST in stale:
+        run([cxx, "-std=c++17", "-O2", "-Wall", "-o", TARGETS_TEST, TARGETS_SRC, "-L" + HERE, "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     return LIB
 
 

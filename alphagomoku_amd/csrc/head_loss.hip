@@ -32,6 +32,7 @@ namespace agx
 				float policy_scale, value_scale, q_scale;
 				float *policy_grad, *value_grad, *q_grad;             // like the logits; all null: losses only
 				AgxSampleScore *scores;                               // [n]
+				const float *q_weight;                                // [n][hw]: k_head_loss<true> only
 		};
 
 		__device__ __forceinline__ double wave_sum(double v)
@@ -79,6 +80,8 @@ namespace agx
 			}
 		}
 
+		/* WEIGHTED: the action-value cells that count are those with A.q_weight > 0 (agx.h: agx_head_loss_grad_weighted) */
+		template<bool WEIGHTED>
 		__global__ __launch_bounds__(64) void k_head_loss(HeadLossArgs A)
 		{
 			const int lane = threadIdx.x;
@@ -136,13 +139,23 @@ namespace agx
 						if (with_q)
 						{
 							const size_t at = (row + cell) * 3;
-							if (edge)
+							float w = 0.0f;
+							if constexpr (WEIGHTED)
+								w = A.q_weight[row + cell];
+							if (WEIGHTED ? (w > 0.0f) : edge)
 							{
-								three_way(A.q + at, A.q_target + at, A.q_scale, q_sum, with_grad ? A.q_grad + at : nullptr);
+								if constexpr (WEIGHTED)
+								{
+									double ce = 0.0;
+									three_way(A.q + at, A.q_target + at, A.q_scale * w, ce, with_grad ? A.q_grad + at : nullptr);
+									q_sum += static_cast<double>(w) * ce;
+								}
+								else
+									three_way(A.q + at, A.q_target + at, A.q_scale, q_sum, with_grad ? A.q_grad + at : nullptr);
 								cells++;
 							}
 							else if (with_grad)
-							{ // the cell had no edge: its action-value target is filler and is not even read
+							{ // the cell does not count (no edge; weighted: no weight): its action-value target is filler and is not even read
 								A.q_grad[at] = 0.0f;
 								A.q_grad[at + 1] = 0.0f;
 								A.q_grad[at + 2] = 0.0f;
@@ -182,11 +195,20 @@ int agx_head_loss_grad(int rows, int cols, int n, const float *d_policy_logits, 
 		const float *d_value_target, const float *d_q_target, float policy_scale, float value_scale, float q_scale, float *d_policy_grad, float *d_value_grad,
 		float *d_q_grad, AgxSampleScore *d_sample_scores, AgxNetScore *d_total, void *stream_)
 {
+	return agx_head_loss_grad_weighted(rows, cols, n, d_policy_logits, d_value_logits, d_q_logits, d_policy_target, d_value_target, d_q_target, nullptr, policy_scale,
+			value_scale, q_scale, d_policy_grad, d_value_grad, d_q_grad, d_sample_scores, d_total, stream_);
+}
+
+int agx_head_loss_grad_weighted(int rows, int cols, int n, const float *d_policy_logits, const float *d_value_logits, const float *d_q_logits,
+		const float *d_policy_target, const float *d_value_target, const float *d_q_target, const float *d_q_weight, float policy_scale, float value_scale, float q_scale,
+		float *d_policy_grad, float *d_value_grad, float *d_q_grad, AgxSampleScore *d_sample_scores, AgxNetScore *d_total, void *stream_)
+{
 	AGX_REQUIRE(rows >= 5 && rows <= 20 && cols >= 5 && cols <= 20, AGX_ERR_INVALID, "agx_head_loss_grad: boards from 5x5 to 20x20 (got %dx%d)", rows, cols);
 	AGX_REQUIRE(n > 0, AGX_ERR_INVALID, "agx_head_loss_grad: %d samples", n);
 	AGX_REQUIRE(d_policy_logits != nullptr && d_value_logits != nullptr && d_policy_target != nullptr && d_value_target != nullptr && d_sample_scores != nullptr
 			&& d_total != nullptr, AGX_ERR_INVALID, "agx_head_loss_grad: null argument (only the action-value tensors and the three gradients are optional)");
 	AGX_REQUIRE((d_q_logits == nullptr) == (d_q_target == nullptr), AGX_ERR_INVALID, "agx_head_loss_grad: action values need both the logits and the targets");
+	AGX_REQUIRE(d_q_weight == nullptr || d_q_logits != nullptr, AGX_ERR_INVALID, "agx_head_loss_grad_weighted: a weight without action values");
 	const bool with_grad = (d_policy_grad != nullptr || d_value_grad != nullptr || d_q_grad != nullptr);
 	AGX_REQUIRE(!with_grad || (d_policy_grad != nullptr && d_value_grad != nullptr && (d_q_grad != nullptr) == (d_q_logits != nullptr)), AGX_ERR_INVALID,
 			"agx_head_loss_grad: gradients are written for every head that has logits, or for none");
@@ -207,7 +229,11 @@ int agx_head_loss_grad(int rows, int cols, int n, const float *d_policy_logits, 
 	A.value_grad = d_value_grad;
 	A.q_grad = d_q_grad;
 	A.scores = d_sample_scores;
-	hipLaunchKernelGGL(agx::k_head_loss, dim3(std::min(n, agx::LOSS_MAX_WAVES)), dim3(64), 0, stream, A);
+	A.q_weight = d_q_weight;
+	if (d_q_weight != nullptr)
+		hipLaunchKernelGGL(agx::k_head_loss<true>, dim3(std::min(n, agx::LOSS_MAX_WAVES)), dim3(64), 0, stream, A);
+	else
+		hipLaunchKernelGGL(agx::k_head_loss<false>, dim3(std::min(n, agx::LOSS_MAX_WAVES)), dim3(64), 0, stream, A);
 	return agx::add_sample_scores(n, d_sample_scores, d_total, stream);
 }
 

@@ -33,6 +33,7 @@ namespace agx
 				const float *policy_target, *value_target, *action_values_target; // targets: [n][hw], [n][3], [n][hw][3] or null
 				AgxSampleScore *scores;                                           // [n] (null in the one-workgroup form)
 				AgxNetScore *total;
+				const float *q_weight;                                            // [n][hw] or null: agx_net_score_outputs_weighted
 		};
 
 		/* float32 term, as defined in agx.h: the product is rounded to float32 (the file is compiled with -ffp-contract=off) */
@@ -104,8 +105,25 @@ namespace agx
 					out[ch] = ordered(pv, cell);
 					target[ch] = ordered(tv, cell);
 					if (tv > 0.0f)
-					{
 						policy_sum += static_cast<double>(ce_term(tv, pv));
+					if (A.q_weight != nullptr)
+					{ // (needs action values: the host has checked)
+						const float w = A.q_weight[static_cast<size_t>(b) * hw + cell];
+						if (w > 0.0f)
+						{
+							const float *q = A.action_values + (static_cast<size_t>(b) * hw + cell) * 2;
+							const float *qt = A.action_values_target + (static_cast<size_t>(b) * hw + cell) * 3;
+							const float win = q[0], draw = q[1];
+							double ce = 0.0;
+							ce += static_cast<double>(ce_term(qt[0], win));
+							ce += static_cast<double>(ce_term(qt[1], draw));
+							ce += static_cast<double>(ce_term(qt[2], 1.0f - win - draw)); // Value::loss_rate
+							q_sum += static_cast<double>(w) * ce;
+							cells++;
+						}
+					}
+					else if (tv > 0.0f)
+					{
 						if (with_q)
 						{
 							const float *q = A.action_values + (static_cast<size_t>(b) * hw + cell) * 2;
@@ -256,6 +274,13 @@ int agx_net_score_clear(AgxNetScore *d_total, void *stream)
 int agx_net_score_outputs(int rows, int cols, int n, const float *d_policy, const float *d_value, const float *d_action_values, const float *d_policy_target,
 		const float *d_value_target, const float *d_action_values_target, AgxSampleScore *d_sample_scores, AgxNetScore *d_total, void *stream_)
 {
+	return agx_net_score_outputs_weighted(rows, cols, n, d_policy, d_value, d_action_values, d_policy_target, d_value_target, d_action_values_target, nullptr,
+			d_sample_scores, d_total, stream_);
+}
+
+int agx_net_score_outputs_weighted(int rows, int cols, int n, const float *d_policy, const float *d_value, const float *d_action_values, const float *d_policy_target,
+		const float *d_value_target, const float *d_action_values_target, const float *d_q_weight, AgxSampleScore *d_sample_scores, AgxNetScore *d_total, void *stream_)
+{
 	static_assert(sizeof(AgxSampleScore) == 48 && sizeof(AgxNetScore) == 72, "score record layouts");
 	AGX_REQUIRE(rows >= 5 && rows <= 20 && cols >= 5 && cols <= 20, AGX_ERR_INVALID, "agx_net_score_outputs: boards from 5x5 to 20x20 (got %dx%d)", rows, cols);
 	AGX_REQUIRE(n > 0, AGX_ERR_INVALID, "agx_net_score_outputs: %d samples", n);
@@ -263,6 +288,7 @@ int agx_net_score_outputs(int rows, int cols, int n, const float *d_policy, cons
 			"agx_net_score_outputs: null argument (only the two action-value tensors and d_sample_scores are optional)");
 	AGX_REQUIRE((d_action_values == nullptr) == (d_action_values_target == nullptr), AGX_ERR_INVALID,
 			"agx_net_score_outputs: action values need both the outputs and the targets");
+	AGX_REQUIRE(d_q_weight == nullptr || d_action_values != nullptr, AGX_ERR_INVALID, "agx_net_score_outputs_weighted: a weight without action values");
 	hipStream_t stream = static_cast<hipStream_t>(stream_);
 	agx::ScoreArgs A;
 	A.hw = rows * cols;
@@ -275,6 +301,7 @@ int agx_net_score_outputs(int rows, int cols, int n, const float *d_policy, cons
 	A.action_values_target = d_action_values_target;
 	A.scores = d_sample_scores;
 	A.total = d_total;
+	A.q_weight = d_q_weight;
 	if (d_sample_scores == nullptr)
 		hipLaunchKernelGGL(agx::k_score_batch_total, dim3(1), dim3(64 * agx::FUSED_WAVES), 0, stream, A);
 	else
@@ -288,8 +315,16 @@ int agx_net_score_outputs(int rows, int cols, int n, const float *d_policy, cons
 
 int agx_net_score_dataset(AgxNet *net, AgxDataset *dataset, int n, const AgxDatasetSample *h_samples, int chunk, AgxNetScore *h_out, void *stream_)
 {
+	return agx_net_score_dataset_ex(net, dataset, n, h_samples, chunk, 0, 0, h_out, stream_);
+}
+
+int agx_net_score_dataset_ex(AgxNet *net, AgxDataset *dataset, int n, const AgxDatasetSample *h_samples, int chunk, int batch_flags, int q_weighted, AgxNetScore *h_out,
+		void *stream_)
+{
 	AGX_REQUIRE(net != nullptr && dataset != nullptr && h_samples != nullptr && h_out != nullptr, AGX_ERR_INVALID, "agx_net_score_dataset: null argument");
 	AGX_REQUIRE(n > 0 && chunk >= 0, AGX_ERR_INVALID, "agx_net_score_dataset: %d samples in chunks of %d", n, chunk);
+	AGX_REQUIRE((batch_flags & ~(AGX_BATCH_POLICY_VISITS | AGX_BATCH_POLICY_VALUES)) == 0, AGX_ERR_INVALID,
+			"agx_net_score_dataset_ex: batch flags 0x%x (only the two policy flags: the path reads feature words)", batch_flags);
 	AgxNetDesc desc;
 	int st = agx_net_description(net, &desc);
 	if (st != AGX_OK)
@@ -302,12 +337,14 @@ int agx_net_score_dataset(AgxNet *net, AgxDataset *dataset, int n, const AgxData
 			board.dim[1], board.dim[2], desc.rows, desc.cols);
 	hipStream_t stream = static_cast<hipStream_t>(stream_);
 	const size_t hw = static_cast<size_t>(desc.rows) * desc.cols, C = static_cast<size_t>(std::min(chunk == 0 ? 1024 : chunk, n));
-	const bool with_q = (desc.action_values != 0);
-	// features, policy / value / moves-left / action-value targets, the network's policy / value / action values, the records, the total
-	const size_t bytes[10] = { C * hw * 4, C * hw * 4, C * 3 * 4, C * 4, C * hw * 3 * 4, C * hw * 4, C * 3 * 4, with_q ? C * hw * 2 * 4 : 0, C * sizeof(AgxSampleScore),
-			sizeof(AgxNetScore) };
-	size_t offset[10], total = 0;
-	for (int i = 0; i < 10; i++)
+	const bool with_q = (desc.action_values != 0), weighted = with_q && (q_weighted != 0);
+	// features, policy / value / moves-left / action-value targets, the network's policy / value / action values, the records, the total,
+	// the action-value weights
+	constexpr int AREAS = 11;
+	const size_t bytes[AREAS] = { C * hw * 4, C * hw * 4, C * 3 * 4, C * 4, C * hw * 3 * 4, C * hw * 4, C * 3 * 4, with_q ? C * hw * 2 * 4 : 0, C * sizeof(AgxSampleScore),
+			sizeof(AgxNetScore), weighted ? C * hw * 4 : 0 };
+	size_t offset[AREAS], total = 0;
+	for (int i = 0; i < AREAS; i++)
 	{
 		offset[i] = total;
 		total += (bytes[i] + 255) / 256 * 256;
@@ -321,13 +358,14 @@ int agx_net_score_dataset(AgxNet *net, AgxDataset *dataset, int n, const AgxData
 	for (int first = 0; first < n && st == AGX_OK; first += static_cast<int>(C))
 	{
 		const int count = std::min(static_cast<int>(C), n - first);
-		st = agx_dataset_load_batch(dataset, count, h_samples + first, nullptr, reinterpret_cast<uint32_t*>(at(0)), at(1), at(2), at(3), at(4), 0, stream);
+		const AgxBatchTensors tensors = { nullptr, reinterpret_cast<uint32_t*>(at(0)), at(1), at(2), at(3), at(4), weighted ? at(10) : nullptr };
+		st = agx_dataset_load_batch_ex(dataset, count, h_samples + first, &tensors, batch_flags, stream);
 		if (st == AGX_OK)
 			st = with_q ? agx_nn_forward_pvq(net, reinterpret_cast<const uint32_t*>(at(0)), count, at(5), at(6), at(7), stream) :
 					agx_nn_forward(net, reinterpret_cast<const uint32_t*>(at(0)), count, at(5), at(6), stream);
 		if (st == AGX_OK)
-			st = agx_net_score_outputs(desc.rows, desc.cols, count, at(5), at(6), with_q ? at(7) : nullptr, at(1), at(2), with_q ? at(4) : nullptr,
-					reinterpret_cast<AgxSampleScore*>(base + offset[8]), d_total, stream);
+			st = agx_net_score_outputs_weighted(desc.rows, desc.cols, count, at(5), at(6), with_q ? at(7) : nullptr, at(1), at(2), with_q ? at(4) : nullptr,
+					weighted ? at(10) : nullptr, reinterpret_cast<AgxSampleScore*>(base + offset[8]), d_total, stream);
 	}
 	if (st != AGX_OK)
 	{ // whatever was enqueued still uses the scratch

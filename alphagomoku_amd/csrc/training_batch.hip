@@ -28,6 +28,11 @@
  * The build uses -ffp-contract=off and correctly rounded float32 division: every output is bit-identical to a float32 restatement
  * on the CPU (tests/training_batch_ref.py).
  *
+ * Stage 3 has three compile-time variants (TARGETS_*): the two visit-count policies as they always were; the same plus
+ * action_values_weight (visits / sum of visits, the weight of the reference's action-value loss); and the targets of SamplerValues
+ * (dataset/Sampler.cpp:138-214, the reference's default sampler), which go through logf and expf: that policy is within 1 ulp-level
+ * differences of a float32 restatement (tests/training_targets_ref.py), everything else is bit-identical to it.
+ *
  * Differences from the reference, on purpose:
  *  - torch_api.cpp:274-277 never advances action_values_target inside its batch loop: it writes every sample's action values over
  *    sample 0's.  Here sample b's action values go to index b.
@@ -44,6 +49,7 @@
 #include <hip/hip_fp16.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -80,6 +86,17 @@ namespace agx
 				uint16_t *list_spill;   // [waves][20][SH::HW]
 				uint64_t *snap_spill;   // [waves][SNAP_LEVELS][64], null unless renju
 				int *error;             // pinned host word: batch index + 1 of a sample whose foul probe gave up (see the end of the sample loop)
+				float *weight;          // action_values_weight; null in TARGETS_PLAIN, may be null in TARGETS_VALUES
+		};
+
+		/* the compile-time variants of stage 3.  TARGETS_PLAIN is the kernel as it was before the other two existed: the two visit-count
+		 * policies, no weight output.  A launch picks the variant from the flags and the weight pointer, so a call that asks for neither
+		 * runs the code it always ran. */
+		enum
+		{
+			TARGETS_PLAIN = 0,    // visit-count policy (torch_api.cpp / SamplerVisits)
+			TARGETS_WEIGHTED = 1, // ... plus action_values_weight
+			TARGETS_VALUES = 2    // SamplerValues (Sampler.cpp:138-214), action_values_weight when its pointer is set
 		};
 
 		__device__ __forceinline__ uint32_t load_u16(const uint8_t *p) { return static_cast<uint32_t>(p[0]) | (static_cast<uint32_t>(p[1]) << 8); }
@@ -96,7 +113,241 @@ namespace agx
 			return v;
 		}
 
+		__device__ __forceinline__ int wave_sum_int(int v)
+		{
+#pragma unroll
+			for (int off = 1; off < 64; off <<= 1)
+				v += __shfl_xor(v, off, 64);
+			return v;
+		}
+		__device__ __forceinline__ float wave_max_float(float v)
+		{
+#pragma unroll
+			for (int off = 1; off < 64; off <<= 1)
+				v = fmaxf(v, __shfl_xor(v, off, 64));
+			return v;
+		}
+		/* the float of lane `src` (the same in every lane) */
+		__device__ __forceinline__ float lane_float(float v, int src)
+		{
+			return v201::bits_float(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v201::float_bits(v)), src)));
+		}
+		/* Value::getExpectation */
+		__device__ __forceinline__ float expectation(float win, float draw) { return win + 0.5f * draw; }
+		/* the count both samplers leave in TrainingDataPack::visit_count (Sampler.cpp:112,161): a proven move has at least one visit */
+		__device__ __forceinline__ int fixed_up_visits(bool empty, uint32_t score, int visits)
+		{
+			return (empty && dev::s_proven(score)) ? max(1, visits) : visits;
+		}
+		/* fill_action_values_mask (SupervisedLearning.cpp:55-61): count * (1 / sum of the counts); all zero when the sum is */
+		template<int CHUNKS>
+		__device__ __forceinline__ void write_weights(float *out, const int (&counts)[CHUNKS], int hw, int lane)
+		{
+			int total = 0;
+#pragma unroll
+			for (int ch = 0; ch < CHUNKS; ch++)
+				total += counts[ch];
+			total = __builtin_amdgcn_readfirstlane(wave_sum_int(total));
+			const float inv = (total == 0) ? 0.0f : 1.0f / static_cast<float>(total);
+#pragma unroll
+			for (int ch = 0; ch < CHUNKS; ch++)
+			{
+				const int cell = ch * 64 + lane;
+				if (cell < hw)
+					out[cell] = (total == 0) ? 0.0f : static_cast<float>(counts[ch]) * inv;
+			}
+		}
+
+		/* Stage 3 of TARGETS_VALUES: SamplerValues::prepare_training_data (Sampler.cpp:138-214) on sample b, in float32, one operation after
+		 * the other.  Every sequential float sum of the reference is formed one addend after the other (a ballot of the lanes that
+		 * contribute, then readlane in lane order), over the cells of the TRANSFORMED board where the reference, which samples before it
+		 * applies the symmetry, runs over the untransformed one: a difference of float32 rounding only.  The sums of storeTo run in entry
+		 * order, as there. */
 		template<int N>
+		struct ValuesTemp
+		{ // per cell of the transformed board, between the loops of values_targets (LDS of the TARGETS_VALUES variant only)
+				float prior[N * N];
+				float q[N * N];      // the cell's Q, then its logit, then its exponential
+				int count[N * N];    // fixed_up_visits
+				uint8_t flag[N * N]; // 1 empty, 2 visited or proven
+		};
+		template<int N>
+		__device__ __forceinline__ void values_targets(const BatchArgs &A, ValuesTemp<N> &T, int b, const uint8_t *sample, float value_scale, float visit_scale, int count,
+				int s, int n, int hw, const uint8_t *board, const uint16_t *entry_of, int lane)
+		{
+			using namespace dev;
+			const float policy_scale = v201::ScaleFormat::decode(load_u16(sample + 2));
+			const uint32_t minimax_score = load_u16(sample + 6);
+
+			// minimax value: storeTo's running sums over the entries (SearchDataStorage.cpp:377-406)
+			float win_rate = 0.0f, draw_rate = 0.0f;
+			int sum_visits = 0;
+			for (int base = 0; base < count; base += 64)
+			{
+				const int k = base + lane;
+				float v = 0.0f, wv = 0.0f, dv = 0.0f;
+				if (k < count)
+				{
+					const uint8_t *q = sample + v201::HEADER_BYTES + v201::ENTRY_BYTES * k;
+					v = v201::VisitFormat::decode(q[1]) * visit_scale + 0.5f;
+					float w = v201::PriorFormat::decode(q[4]) * value_scale;
+					float d = v201::PriorFormat::decode(q[5]) * value_scale;
+					const float total = w + d; // get_valid_value
+					if (total > 1.0f)
+					{
+						w /= total;
+						d /= total;
+					}
+					wv = w * v;
+					dv = d * v;
+				}
+				const int here = __builtin_amdgcn_readfirstlane(min(64, count - base));
+				for (int j = 0; j < here; j++)
+				{
+					const int src = __builtin_amdgcn_readfirstlane(j);
+					sum_visits = static_cast<int>(static_cast<float>(sum_visits) + lane_float(v, src)); // int sum_visits += float visits
+					win_rate += lane_float(wv, src);
+					draw_rate += lane_float(dv, src);
+				}
+			}
+			float mm_win, mm_draw;
+			if (sum_visits == 0)
+				s_to_value(minimax_score, mm_win, mm_draw);
+			else
+			{
+				mm_win = win_rate / static_cast<float>(sum_visits);
+				mm_draw = draw_rate / static_cast<float>(sum_visits);
+				const float total = mm_win + mm_draw;
+				if (total > 1.0f)
+				{
+					mm_win /= total;
+					mm_draw /= total;
+				}
+			}
+			if (s_proven(minimax_score)) // get_value(minimax_value, minimax_score)
+				s_to_value(minimax_score, mm_win, mm_draw);
+			const float minimax_V = expectation(mm_win, mm_draw);
+
+			// first loop (:152-165): the cells that have a visit or a proven score.  What the later loops need of a cell waits in LDS; a lane
+			// reads back only what it wrote itself (cells lane, lane + 64, ...), so nothing has to be synchronised
+			float sum_PxQ = 0.0f, sum_P = 0.0f;
+			int unvisited = 0, count_sum = 0;
+			for (int base = 0; base < hw; base += 64)
+			{
+				const int cell = base + lane;
+				const bool inside = cell < hw;
+				int visits = 0;
+				float win = 0.0f, draw = 0.0f, p = 0.0f;
+				uint32_t score = s_unknown(0); // SearchDataPack::clear
+				if (inside)
+				{
+					int sr, sc;
+					symmetry_source(s, n, cell / n, cell % n, sr, sc);
+					const int e = entry_of[sr * n + sc];
+					if (e != 0)
+					{ // storeTo
+						const uint8_t *q = sample + v201::HEADER_BYTES + v201::ENTRY_BYTES * (e - 1);
+						visits = static_cast<int>(v201::VisitFormat::decode(q[1]) * visit_scale + 0.5f);
+						p = v201::PriorFormat::decode(q[2]) * policy_scale;
+						win = v201::PriorFormat::decode(q[4]) * value_scale;
+						draw = v201::PriorFormat::decode(q[5]) * value_scale;
+						const float total = win + draw;
+						if (total > 1.0f)
+						{
+							win /= total;
+							draw /= total;
+						}
+						score = v201::score_from_code(q[3]);
+					}
+				}
+				const bool empty = inside && board[cell] == 0;
+				const bool counted = empty && (visits > 0 || s_proven(score));
+				const float distance = static_cast<float>(s_distance(score));
+				float Q;
+				switch (s_pv(score))
+				{ // the Q of the second loop (:180-195); the raw action value where nothing is proven
+					case 0: Q = -1.0f / (1.0f + distance); break;
+					case 1: Q = 0.5f; break; // Value::draw().getExpectation()
+					case 3: Q = 1.0f + 2.0f / (1.0f + distance); break;
+					default: Q = expectation(win, draw); break;
+				}
+				if (s_proven(score)) // get_value(action_value, score)
+					s_to_value(score, win, draw);
+				const int fixed = inside ? fixed_up_visits(empty, score, visits) : 0;
+				count_sum += fixed;
+				if (inside)
+				{
+					T.prior[cell] = p;
+					T.q[cell] = Q;
+					T.count[cell] = fixed;
+					T.flag[cell] = static_cast<uint8_t>((empty ? 1 : 0) | (counted ? 2 : 0));
+					// the cleared pack (0, 0) wherever the second loop writes nothing
+					const float w = counted ? win : 0.0f, d = counted ? draw : 0.0f;
+					float *av = A.action_values + (static_cast<size_t>(b) * hw + cell) * 3;
+					av[0] = w;
+					av[1] = d;
+					av[2] = 1.0f - (w + d); // Value::loss_rate
+				}
+				const float pxq = p * expectation(win, draw);
+				u64 todo = __ballot(counted);
+				unvisited += __popcll(__ballot(empty && !counted));
+				while (todo != 0ull)
+				{
+					const int src = __builtin_amdgcn_readfirstlane(__ffsll(static_cast<long long>(todo)) - 1);
+					todo &= todo - 1ull;
+					sum_PxQ += lane_float(pxq, src);
+					sum_P += lane_float(p, src);
+				}
+			}
+			sum_PxQ = sum_P * sum_PxQ + (1.0f - sum_P) * minimax_V;
+
+			// second loop (:170-201): the logits and their maximum.  Without an unvisited cell the default P is never used (and not formed)
+			const float spread = (unvisited > 0) ? (1.0f - sum_P) / static_cast<float>(unvisited) : 0.0f;
+			const float default_P = (0.0f < spread) ? spread : 0.0f; // std::max(0.0f, ...)
+			float max_value = -FLT_MAX;
+			for (int cell = lane; cell < hw; cell += 64)
+				if (T.flag[cell] & 1)
+				{
+					const bool counted = (T.flag[cell] & 2) != 0;
+					const float logit = 50.0f * (counted ? T.q[cell] : sum_PxQ) + logf(FLT_EPSILON + (counted ? T.prior[cell] : default_P));
+					T.q[cell] = logit;
+					max_value = fmaxf(max_value, logit);
+				}
+			max_value = wave_max_float(max_value);
+
+			// normalisation (:203-213)
+			float sum_policy = 0.0f;
+			for (int base = 0; base < hw; base += 64)
+			{
+				const int cell = base + lane;
+				const bool empty = cell < hw && (T.flag[cell] & 1) != 0;
+				float e = 0.0f;
+				if (empty)
+				{
+					const float shifted = T.q[cell] - max_value;
+					e = expf((-20.0f < shifted) ? shifted : -20.0f); // std::max(-20.0f, ...)
+					T.q[cell] = e;
+				}
+				u64 todo = __ballot(empty);
+				while (todo != 0ull)
+				{
+					const int src = __builtin_amdgcn_readfirstlane(__ffsll(static_cast<long long>(todo)) - 1);
+					todo &= todo - 1ull;
+					sum_policy += lane_float(e, src);
+				}
+			}
+			for (int cell = lane; cell < hw; cell += 64)
+				A.policy[static_cast<size_t>(b) * hw + cell] = (T.flag[cell] & 1) ? T.q[cell] / sum_policy : 0.0f;
+			if (A.weight != nullptr)
+			{ // fill_action_values_mask, as write_weights forms it
+				const int total = __builtin_amdgcn_readfirstlane(wave_sum_int(count_sum));
+				const float inv = (total == 0) ? 0.0f : 1.0f / static_cast<float>(total);
+				for (int cell = lane; cell < hw; cell += 64)
+					A.weight[static_cast<size_t>(b) * hw + cell] = (total == 0) ? 0.0f : static_cast<float>(T.count[cell]) * inv;
+			}
+		}
+
+		template<int N, int TARGETS>
 		__global__ __launch_bounds__(64) void k_training_batch(EngineDev E, BatchArgs A)
 		{
 			using namespace dev;
@@ -177,70 +428,83 @@ namespace agx
 				wave_sync();
 
 				// ---- 3. targets, cell by cell of the transformed board ----
-				float addend[CHUNKS];
-				float sum = 0.0f;
-#pragma unroll
-				for (int ch = 0; ch < CHUNKS; ch++)
+				if constexpr (TARGETS == TARGETS_VALUES)
 				{
-					const int cell = ch * 64 + lane;
-					const bool inside = cell < hw;
-					int visits = 0;
-					float win = 0.0f, draw = 0.0f;
-					uint32_t score = s_unknown(0); // SearchDataPack::clear
-					if (inside)
+					__shared__ ValuesTemp<N> temp;
+					values_targets<N>(A, temp, b, sample, value_scale, visit_scale, count, s, n, hw, board, entry_of, lane);
+				}
+				else
+				{
+					float addend[CHUNKS];
+					int counts[CHUNKS]; // (TARGETS_WEIGHTED only)
+					float sum = 0.0f;
+#pragma unroll
+					for (int ch = 0; ch < CHUNKS; ch++)
 					{
-						int sr, sc;
-						symmetry_source(s, n, cell / n, cell % n, sr, sc);
-						const int e = entry_of[sr * n + sc];
-						if (e != 0)
-						{ // storeTo (SearchDataStorage.cpp:375-409)
-							const uint8_t *q = sample + v201::HEADER_BYTES + v201::ENTRY_BYTES * (e - 1);
-							visits = static_cast<int>(v201::VisitFormat::decode(q[1]) * visit_scale + 0.5f);
-							win = v201::PriorFormat::decode(q[4]) * value_scale;
-							draw = v201::PriorFormat::decode(q[5]) * value_scale;
-							const float total = win + draw; // get_valid_value (:52-61)
-							if (total > 1.0f)
-							{
-								win /= total;
-								draw /= total;
+						const int cell = ch * 64 + lane;
+						const bool inside = cell < hw;
+						int visits = 0;
+						float win = 0.0f, draw = 0.0f;
+						uint32_t score = s_unknown(0); // SearchDataPack::clear
+						if (inside)
+						{
+							int sr, sc;
+							symmetry_source(s, n, cell / n, cell % n, sr, sc);
+							const int e = entry_of[sr * n + sc];
+							if (e != 0)
+							{ // storeTo (SearchDataStorage.cpp:375-409)
+								const uint8_t *q = sample + v201::HEADER_BYTES + v201::ENTRY_BYTES * (e - 1);
+								visits = static_cast<int>(v201::VisitFormat::decode(q[1]) * visit_scale + 0.5f);
+								win = v201::PriorFormat::decode(q[4]) * value_scale;
+								draw = v201::PriorFormat::decode(q[5]) * value_scale;
+								const float total = win + draw; // get_valid_value (:52-61)
+								if (total > 1.0f)
+								{
+									win /= total;
+									draw /= total;
+								}
+								score = v201::score_from_code(q[3]);
 							}
-							score = v201::score_from_code(q[3]);
+						}
+						if constexpr (TARGETS == TARGETS_WEIGHTED)
+							counts[ch] = inside ? fixed_up_visits(board[cell] == 0, score, visits) : 0;
+						if (s_proven(score))
+							s_to_value(score, win, draw);
+						float p;
+						switch (s_pv(score))
+						{ // torch_api.cpp:252-267 / Sampler.cpp:117-130
+							case 0: p = 1.0e-6f; break;
+							case 1: p = static_cast<float>(A.visits_mode ? visits : max(1, visits)); break;
+							case 3: p = 1.0e+6f; break;
+							default: p = static_cast<float>(visits); break;
+						}
+						p = inside ? p : 0.0f;
+						addend[ch] = p;
+						if (inside)
+						{
+							float *av = A.action_values + (static_cast<size_t>(b) * hw + cell) * 3;
+							av[0] = win;
+							av[1] = draw;
+							av[2] = 1.0f - (win + draw); // Value::loss_rate
+						}
+						u64 nonzero = __ballot(p != 0.0f); // policy_sum += policy_target[i], in cell order; + 0.0f changes nothing
+						while (nonzero != 0ull)
+						{
+							const int src = __builtin_amdgcn_readfirstlane(__ffsll(static_cast<long long>(nonzero)) - 1);
+							nonzero &= nonzero - 1ull;
+							sum += v201::bits_float(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v201::float_bits(p)), src)));
 						}
 					}
-					if (s_proven(score))
-						s_to_value(score, win, draw);
-					float p;
-					switch (s_pv(score))
-					{ // torch_api.cpp:252-267 / Sampler.cpp:117-130
-						case 0: p = 1.0e-6f; break;
-						case 1: p = static_cast<float>(A.visits_mode ? visits : max(1, visits)); break;
-						case 3: p = 1.0e+6f; break;
-						default: p = static_cast<float>(visits); break;
-					}
-					p = inside ? p : 0.0f;
-					addend[ch] = p;
-					if (inside)
-					{
-						float *av = A.action_values + (static_cast<size_t>(b) * hw + cell) * 3;
-						av[0] = win;
-						av[1] = draw;
-						av[2] = 1.0f - (win + draw); // Value::loss_rate
-					}
-					u64 nonzero = __ballot(p != 0.0f); // policy_sum += policy_target[i], in cell order; + 0.0f changes nothing
-					while (nonzero != 0ull)
-					{
-						const int src = __builtin_amdgcn_readfirstlane(__ffsll(static_cast<long long>(nonzero)) - 1);
-						nonzero &= nonzero - 1ull;
-						sum += v201::bits_float(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v201::float_bits(p)), src)));
-					}
-				}
-				const float scale = 1.0f / sum;
+					const float scale = 1.0f / sum;
 #pragma unroll
-				for (int ch = 0; ch < CHUNKS; ch++)
-				{
-					const int cell = ch * 64 + lane;
-					if (cell < hw)
-						A.policy[static_cast<size_t>(b) * hw + cell] = addend[ch] * scale;
+					for (int ch = 0; ch < CHUNKS; ch++)
+					{
+						const int cell = ch * 64 + lane;
+						if (cell < hw)
+							A.policy[static_cast<size_t>(b) * hw + cell] = addend[ch] * scale;
+					}
+					if constexpr (TARGETS == TARGETS_WEIGHTED)
+						write_weights<CHUNKS>(A.weight + static_cast<size_t>(b) * hw, counts, hw, lane);
 				}
 				if (lane == 0)
 				{ // convertOutcome(game_outcome, sign to move) (Value.cpp:16-29), moves_left (GameDataStorage.cpp:141)
@@ -678,10 +942,18 @@ int agx_dataset_tensor_shapes(const AgxDataset *d, int n, AgxTensorShape *input,
 int agx_dataset_load_batch(AgxDataset *d, int n, const AgxDatasetSample *h_samples, void *d_input, uint32_t *d_features, float *d_policy, float *d_value,
 		float *d_moves_left, float *d_action_values, int flags, void *stream_)
 {
-	AGX_REQUIRE(d != nullptr && n >= 0 && (h_samples != nullptr || n == 0), AGX_ERR_INVALID, "agx_dataset_load_batch: null argument or negative batch");
-	AGX_REQUIRE(d_policy != nullptr && d_value != nullptr && d_moves_left != nullptr && d_action_values != nullptr, AGX_ERR_INVALID,
-			"agx_dataset_load_batch: a target tensor is null (only d_input and d_features are optional)");
-	AGX_REQUIRE((flags & ~(AGX_BATCH_INPUT_FP16 | AGX_BATCH_POLICY_VISITS)) == 0, AGX_ERR_INVALID, "agx_dataset_load_batch: unknown flags 0x%x", flags);
+	const AgxBatchTensors tensors = { d_input, d_features, d_policy, d_value, d_moves_left, d_action_values, nullptr };
+	return agx_dataset_load_batch_ex(d, n, h_samples, &tensors, flags, stream_);
+}
+
+int agx_dataset_load_batch_ex(AgxDataset *d, int n, const AgxDatasetSample *h_samples, const AgxBatchTensors *tensors, int flags, void *stream_)
+{
+	AGX_REQUIRE(d != nullptr && tensors != nullptr && n >= 0 && (h_samples != nullptr || n == 0), AGX_ERR_INVALID, "agx_dataset_load_batch: null argument or negative batch");
+	AGX_REQUIRE(tensors->policy != nullptr && tensors->value != nullptr && tensors->moves_left != nullptr && tensors->action_values != nullptr, AGX_ERR_INVALID,
+			"agx_dataset_load_batch: a target tensor is null (only input, features and action_values_weight are optional)");
+	AGX_REQUIRE((flags & ~(AGX_BATCH_INPUT_FP16 | AGX_BATCH_POLICY_VISITS | AGX_BATCH_POLICY_VALUES)) == 0, AGX_ERR_INVALID, "agx_dataset_load_batch: unknown flags 0x%x", flags);
+	AGX_REQUIRE((flags & AGX_BATCH_POLICY_VISITS) == 0 || (flags & AGX_BATCH_POLICY_VALUES) == 0, AGX_ERR_INVALID,
+			"agx_dataset_load_batch: AGX_BATCH_POLICY_VISITS and AGX_BATCH_POLICY_VALUES name two different policy targets");
 	std::lock_guard<std::mutex> lock(d->mutex);
 	std::vector<Fragment*> used;
 	int st = resolve(d, n, h_samples, &used);
@@ -756,20 +1028,40 @@ int agx_dataset_load_batch(AgxDataset *d, int n, const AgxDatasetSample *h_sampl
 	A.n = n;
 	A.fp16 = (flags & AGX_BATCH_INPUT_FP16) ? 1 : 0;
 	A.visits_mode = (flags & AGX_BATCH_POLICY_VISITS) ? 1 : 0;
-	A.input = d_input;
-	A.features = d_features;
-	A.policy = d_policy;
-	A.value = d_value;
-	A.moves_left = d_moves_left;
-	A.action_values = d_action_values;
+	A.input = tensors->input;
+	A.features = tensors->features;
+	A.policy = tensors->policy;
+	A.value = tensors->value;
+	A.moves_left = tensors->moves_left;
+	A.action_values = tensors->action_values;
+	A.weight = tensors->action_values_weight;
 	A.list_spill = d->d_list_spill;
 	A.snap_spill = d->d_snap_spill;
 	AGX_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&A.error), d->h_error, 0));
 	const int waves = std::min(n, MAX_WAVES);
-	if (d->rows <= 15)
-		hipLaunchKernelGGL(agx::k_training_batch<15>, dim3(waves), dim3(64), 0, stream, E, A);
-	else
-		hipLaunchKernelGGL(agx::k_training_batch<agx::MAXN>, dim3(waves), dim3(64), 0, stream, E, A);
+	const int targets = (flags & AGX_BATCH_POLICY_VALUES) ? agx::TARGETS_VALUES : (A.weight != nullptr ? agx::TARGETS_WEIGHTED : agx::TARGETS_PLAIN);
+	const bool small = (d->rows <= 15);
+	switch (targets)
+	{
+		case agx::TARGETS_VALUES:
+			if (small)
+				hipLaunchKernelGGL((agx::k_training_batch<15, agx::TARGETS_VALUES>), dim3(waves), dim3(64), 0, stream, E, A);
+			else
+				hipLaunchKernelGGL((agx::k_training_batch<agx::MAXN, agx::TARGETS_VALUES>), dim3(waves), dim3(64), 0, stream, E, A);
+			break;
+		case agx::TARGETS_WEIGHTED:
+			if (small)
+				hipLaunchKernelGGL((agx::k_training_batch<15, agx::TARGETS_WEIGHTED>), dim3(waves), dim3(64), 0, stream, E, A);
+			else
+				hipLaunchKernelGGL((agx::k_training_batch<agx::MAXN, agx::TARGETS_WEIGHTED>), dim3(waves), dim3(64), 0, stream, E, A);
+			break;
+		default:
+			if (small)
+				hipLaunchKernelGGL((agx::k_training_batch<15, agx::TARGETS_PLAIN>), dim3(waves), dim3(64), 0, stream, E, A);
+			else
+				hipLaunchKernelGGL((agx::k_training_batch<agx::MAXN, agx::TARGETS_PLAIN>), dim3(waves), dim3(64), 0, stream, E, A);
+			break;
+	}
 	AGX_HIP_CHECK(hipGetLastError());
 	AGX_HIP_CHECK(hipEventRecord(slot.done, stream));
 	slot.in_flight = true;
@@ -782,16 +1074,30 @@ int agx_dataset_load_batch(AgxDataset *d, int n, const AgxDatasetSample *h_sampl
 int agx_dataset_load_batch_host(AgxDataset *d, int n, const AgxDatasetSample *h_samples, void *h_input, uint32_t *h_features, float *h_policy, float *h_value,
 		float *h_moves_left, float *h_action_values, int flags)
 {
-	AGX_REQUIRE(d != nullptr && n >= 0 && (h_samples != nullptr || n == 0), AGX_ERR_INVALID, "agx_dataset_load_batch_host: null argument or negative batch");
-	AGX_REQUIRE(h_policy != nullptr && h_value != nullptr && h_moves_left != nullptr && h_action_values != nullptr, AGX_ERR_INVALID,
-			"agx_dataset_load_batch_host: a target tensor is null (only h_input and h_features are optional)");
+	const AgxBatchTensors tensors = { h_input, h_features, h_policy, h_value, h_moves_left, h_action_values, nullptr };
+	return agx_dataset_load_batch_host_ex(d, n, h_samples, &tensors, flags);
+}
+
+int agx_dataset_load_batch_host_ex(AgxDataset *d, int n, const AgxDatasetSample *h_samples, const AgxBatchTensors *tensors, int flags)
+{
+	AGX_REQUIRE(d != nullptr && tensors != nullptr && n >= 0 && (h_samples != nullptr || n == 0), AGX_ERR_INVALID, "agx_dataset_load_batch_host: null argument or negative batch");
+	void *h_input = tensors->input;
+	uint32_t *h_features = tensors->features;
+	float *h_weight = tensors->action_values_weight;
+	AGX_REQUIRE(tensors->policy != nullptr && tensors->value != nullptr && tensors->moves_left != nullptr && tensors->action_values != nullptr, AGX_ERR_INVALID,
+			"agx_dataset_load_batch_host: a target tensor is null (only input, features and action_values_weight are optional)");
+	AGX_REQUIRE((flags & ~(AGX_BATCH_INPUT_FP16 | AGX_BATCH_POLICY_VISITS | AGX_BATCH_POLICY_VALUES)) == 0, AGX_ERR_INVALID, "agx_dataset_load_batch_host: unknown flags 0x%x", flags);
+	AGX_REQUIRE((flags & AGX_BATCH_POLICY_VISITS) == 0 || (flags & AGX_BATCH_POLICY_VALUES) == 0, AGX_ERR_INVALID,
+			"agx_dataset_load_batch_host: AGX_BATCH_POLICY_VISITS and AGX_BATCH_POLICY_VALUES name two different policy targets");
 	if (n == 0)
 		return AGX_OK;
+	constexpr int OUTPUTS = 7;
 	const size_t hw = static_cast<size_t>(d->rows) * d->cols, N = static_cast<size_t>(n);
-	const size_t bytes[6] = { h_input ? N * hw * 32 * ((flags & AGX_BATCH_INPUT_FP16) ? 2 : 4) : 0, h_features ? N * hw * 4 : 0, N * hw * 4, N * 3 * 4, N * 4, N * hw * 3 * 4 };
-	void *host[6] = { h_input, h_features, h_policy, h_value, h_moves_left, h_action_values };
-	size_t offset[6], total = 0;
-	for (int i = 0; i < 6; i++)
+	const size_t bytes[OUTPUTS] = { h_input ? N * hw * 32 * ((flags & AGX_BATCH_INPUT_FP16) ? 2 : 4) : 0, h_features ? N * hw * 4 : 0, N * hw * 4, N * 3 * 4, N * 4,
+			N * hw * 3 * 4, h_weight ? N * hw * 4 : 0 };
+	void *host[OUTPUTS] = { h_input, h_features, tensors->policy, tensors->value, tensors->moves_left, tensors->action_values, h_weight };
+	size_t offset[OUTPUTS], total = 0;
+	for (int i = 0; i < OUTPUTS; i++)
 	{
 		offset[i] = total;
 		total += (bytes[i] + 255) / 256 * 256;
@@ -819,12 +1125,13 @@ int agx_dataset_load_batch_host(AgxDataset *d, int n, const AgxDatasetSample *h_
 		stage = static_cast<uint8_t*>(d->d_stage);
 		stream = d->host_stream;
 	}
-	const int st = agx_dataset_load_batch(d, n, h_samples, h_input ? stage + offset[0] : nullptr, h_features ? reinterpret_cast<uint32_t*>(stage + offset[1]) : nullptr,
+	const AgxBatchTensors staged = { h_input ? stage + offset[0] : nullptr, h_features ? reinterpret_cast<uint32_t*>(stage + offset[1]) : nullptr,
 			reinterpret_cast<float*>(stage + offset[2]), reinterpret_cast<float*>(stage + offset[3]), reinterpret_cast<float*>(stage + offset[4]),
-			reinterpret_cast<float*>(stage + offset[5]), flags, stream);
+			reinterpret_cast<float*>(stage + offset[5]), h_weight ? reinterpret_cast<float*>(stage + offset[6]) : nullptr };
+	const int st = agx_dataset_load_batch_ex(d, n, h_samples, &staged, flags, stream);
 	if (st != AGX_OK)
 		return st;
-	for (int i = 0; i < 6; i++)
+	for (int i = 0; i < OUTPUTS; i++)
 		if (bytes[i] != 0)
 			AGX_HIP_CHECK(hipMemcpyAsync(host[i], stage + offset[i], bytes[i], hipMemcpyDeviceToHost, stream));
 	AGX_HIP_CHECK(hipStreamSynchronize(stream));

@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import lib, check, AgxError, AgxDatasetSample, AgxGameBufferStats, AgxTensorShape, BATCH_INPUT_FP16, BATCH_POLICY_VISITS
+from ._lib import lib, check, AgxError, AgxBatchTensors, AgxDatasetSample, AgxGameBufferStats, AgxTensorShape, BATCH_INPUT_FP16, batch_policy_flag
 
 SYMMETRIES = 8   # number_of_available_symmetries of a square board
 
@@ -60,12 +60,21 @@ class TrainingDataset:
         check(lib.agx_dataset_stats(self._h, ctypes.byref(s)))
         return {name: getattr(s, name) for name, _ in s._fields_}
 
-    def tensor_shapes(self, batch_size):
-        """get_tensor_shapes, plus the packed feature words"""
+    def tensor_shapes(self, batch_size, q_weights=False):
+        """get_tensor_shapes, plus the packed feature words and, with q_weights, action_values_weight [n, rows, cols]"""
         shapes = [AgxTensorShape() for _ in range(6)]
         check(lib.agx_dataset_tensor_shapes(self._h, batch_size, *[ctypes.byref(s) for s in shapes]))
         names = ["input", "features", "policy_target", "value_target", "moves_left_target", "action_values_target"]
-        return {k: tuple(s.dim[:s.rank]) for k, s in zip(names, shapes)}
+        out = {k: tuple(s.dim[:s.rank]) for k, s in zip(names, shapes)}
+        if q_weights:
+            out["action_values_weight"] = out["policy_target"]
+        return out
+
+    @staticmethod
+    def _tensors(address):
+        """AgxBatchTensors from a function name -> address or None"""
+        names = ["input", "features", "policy_target", "value_target", "moves_left_target", "action_values_target", "action_values_weight"]
+        return AgxBatchTensors(*[address(k) for k in names])
 
     @staticmethod
     def _records(samples):
@@ -73,15 +82,19 @@ class TrainingDataset:
         assert ctypes.sizeof(AgxDatasetSample) == 16
         return a
 
-    def load_batch(self, samples, *, dtype=None, out=None, features=True, policy="torch_api"):
+    def load_batch(self, samples, *, dtype=None, out=None, features=True, policy="torch_api", q_weights=False):
         """samples: [n, 4] (fragment, game, sample, augmentation).  Returns a dict of torch tensors on the current ROCm device:
         input [n, rows, cols, 32] (dtype torch.float32 or torch.float16), features [n, rows * cols] (the uint32 feature words agx_nn_forward
         takes, as int32), policy_target [n, rows, cols], value_target [n, 3], moves_left_target [n, 1], action_values_target
         [n, rows, cols, 3].  The launch is enqueued on torch.cuda.current_stream(); nothing is synchronised.  features=False leaves the
         feature words out.  out: a dict of tensors to write into, e.g. from an earlier call of the same batch size: it must hold the four
         targets, and exactly what it holds of "input" and "features" is written (dtype and features are then taken from it).
-        policy: "torch_api" (proven draw: max(1, visits)) or "visits" (SamplerVisits).  The dataset lives on the device of its first
-        batch; a call with another device current is refused."""
+        policy: "torch_api" (proven draw: max(1, visits)), "visits" (SamplerVisits) or "values" (SamplerValues, the reference's default
+        sampler: a softmax over 50 * Q + log(eps + P) on the empty cells; action values only on the visited or proven cells).
+        q_weights=True adds action_values_weight [n, rows, cols]: visits / sum of visits per cell, the weight training.head_loss gives the
+        cell's action-value loss (out= must then hold it, and may hold it only then).  policy="values" with q_weights=True is what the
+        reference's default configuration trains on.  The dataset lives on the device of its first batch; a call with another device
+        current is refused."""
         if not _lib.torch_shares_hip_runtime():
             raise AgxError("this torch carries a HIP runtime of its own: call alphagomoku_amd._lib.share_torch_hip_runtime() before the library is first "
                            "used in this process, or use load_batch_pointers / load_batch_host")
@@ -95,9 +108,8 @@ class TrainingDataset:
         dtype = dtype or torch.float32
         if dtype not in (torch.float32, torch.float16):
             raise ValueError("input dtype must be torch.float32 or torch.float16")
-        if policy not in ("torch_api", "visits"):
-            raise ValueError("policy must be 'torch_api' or 'visits'")
-        shapes = self.tensor_shapes(n)
+        policy_flag = batch_policy_flag(policy)
+        shapes = self.tensor_shapes(n, q_weights)
         if out is None:
             dev = torch.device("cuda", torch.cuda.current_device())
             out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in shapes if k not in ("input", "features")}
@@ -105,53 +117,58 @@ class TrainingDataset:
             if features:
                 out["features"] = torch.empty(shapes["features"], dtype=torch.int32, device=dev)
         else:
-            missing = [k for k in ("policy_target", "value_target", "moves_left_target", "action_values_target") if k not in out]
+            required = ("policy_target", "value_target", "moves_left_target", "action_values_target") + (("action_values_weight",) if q_weights else ())
+            missing = [k for k in required if k not in out]
             if missing or any(k not in shapes for k in out):
-                raise ValueError("out must hold the four targets and at most 'input' and 'features' besides (missing %s)" % missing)
+                raise ValueError("out must hold the four targets (with q_weights also 'action_values_weight', and only then) and at most 'input' and "
+                                 "'features' besides (missing %s)" % missing)
             for k, t in out.items():
                 want = dtype if k == "input" else (torch.int32 if k == "features" else torch.float32)
                 if tuple(t.shape) != shapes[k] or t.dtype != want or not t.is_contiguous() or not t.is_cuda:
                     raise ValueError("out[%r] must be a contiguous %s device tensor of shape %s" % (k, want, shapes[k]))
-        flags = (BATCH_INPUT_FP16 if dtype == torch.float16 else 0) | (BATCH_POLICY_VISITS if policy == "visits" else 0)
-        ptr = lambda k: ctypes.c_void_p(out[k].data_ptr()) if k in out else None  # noqa: E731
+        flags = (BATCH_INPUT_FP16 if dtype == torch.float16 else 0) | policy_flag
+        tensors = self._tensors(lambda k: out[k].data_ptr() if k in out else None)
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        check(lib.agx_dataset_load_batch(self._h, n, rec.ctypes.data_as(ctypes.c_void_p), ptr("input"), ptr("features"), ptr("policy_target"),
-                                         ptr("value_target"), ptr("moves_left_target"), ptr("action_values_target"), flags, stream))
+        check(lib.agx_dataset_load_batch_ex(self._h, n, rec.ctypes.data_as(ctypes.c_void_p), ctypes.byref(tensors), flags, stream))
         return out
 
-    def load_batch_pointers(self, samples, pointers, *, half=False, policy="torch_api", stream=None):
-        """agx_dataset_load_batch on raw device addresses: pointers maps the output names of tensor_shapes() to integers ("input" and
-        "features" may be missing), stream is a hipStream_t as an integer / c_void_p or None"""
+    def load_batch_pointers(self, samples, pointers, *, half=False, policy="torch_api", q_weights=False, stream=None):
+        """agx_dataset_load_batch_ex on raw device addresses: pointers maps the output names of tensor_shapes() to integers ("input" and
+        "features" may be missing; "action_values_weight" is needed, and allowed, exactly with q_weights), stream is a hipStream_t as an
+        integer / c_void_p or None"""
         rec = self._records(samples)
-        flags = (BATCH_INPUT_FP16 if half else 0) | (BATCH_POLICY_VISITS if policy == "visits" else 0)
-        ptr = lambda k: ctypes.c_void_p(pointers[k]) if pointers.get(k) else None  # noqa: E731
-        check(lib.agx_dataset_load_batch(self._h, rec.shape[0], rec.ctypes.data_as(ctypes.c_void_p), ptr("input"), ptr("features"), ptr("policy_target"),
-                                         ptr("value_target"), ptr("moves_left_target"), ptr("action_values_target"), flags, stream))
+        flags = (BATCH_INPUT_FP16 if half else 0) | batch_policy_flag(policy)
+        if bool(pointers.get("action_values_weight")) != bool(q_weights):
+            raise ValueError("pointers must name 'action_values_weight' with q_weights, and only then")
+        tensors = self._tensors(lambda k: pointers.get(k) or None)
+        check(lib.agx_dataset_load_batch_ex(self._h, rec.shape[0], rec.ctypes.data_as(ctypes.c_void_p), ctypes.byref(tensors), flags, stream))
 
-    def load_batch_host(self, samples, *, half=False, features=True, policy="torch_api"):
+    def load_batch_host(self, samples, *, half=False, features=True, policy="torch_api", q_weights=False):
         """the same through the C ABI's host-pointer form (what ag::load_batch forwards to): numpy arrays, no torch"""
         rec = self._records(samples)
         n = rec.shape[0]
-        shapes = self.tensor_shapes(n)
+        shapes = self.tensor_shapes(n, q_weights)
         out = {k: np.zeros(shapes[k], np.float32) for k in shapes if k not in ("input", "features")}
         out["input"] = np.zeros(shapes["input"], np.float16 if half else np.float32)
         if features:
             out["features"] = np.zeros(shapes["features"], np.uint32)
-        flags = (BATCH_INPUT_FP16 if half else 0) | (BATCH_POLICY_VISITS if policy == "visits" else 0)
-        ptr = lambda k: out[k].ctypes.data_as(ctypes.c_void_p) if k in out else None  # noqa: E731
-        check(lib.agx_dataset_load_batch_host(self._h, n, rec.ctypes.data_as(ctypes.c_void_p), ptr("input"), ptr("features"), ptr("policy_target"),
-                                              ptr("value_target"), ptr("moves_left_target"), ptr("action_values_target"), flags))
+        flags = (BATCH_INPUT_FP16 if half else 0) | batch_policy_flag(policy)
+        tensors = self._tensors(lambda k: out[k].ctypes.data if k in out else None)
+        check(lib.agx_dataset_load_batch_host_ex(self._h, n, rec.ctypes.data_as(ctypes.c_void_p), ctypes.byref(tensors), flags))
         return out
 
-    def score(self, net, samples, chunk=0, stream=None):
+    def score(self, net, samples, chunk=0, stream=None, policy="torch_api", q_weights=False):
         """How well `net` (networks.AGNetwork) fits these samples ([n, 4] as for load_batch): batch, network and reductions run on the
         device, `chunk` samples at a time (0 = 1024), on `stream`; the call waits for the 72-byte result.  Returns networks.score_dict():
         the sums (policy_ce, value_ce, q_ce, q_cells, topk_hit[4], samples) and their means (policy_loss, value_loss, q_loss,
-        accuracy[4]).  The total does not depend on chunk."""
+        accuracy[4]).  The total does not depend on chunk.  policy: the targets to score against, as for load_batch.  q_weights=True
+        weights every cell's action-value term by visits / sum of visits: q_ce / samples is then the weighted mean per sample (q_loss stays
+        q_ce / q_cells, q_cells counting the cells with a weight)."""
         from .networks import score_dict
         rec = self._records(samples)
         out = _lib.AgxNetScore()
-        check(lib.agx_net_score_dataset(net._net, self._h, rec.shape[0], rec.ctypes.data_as(ctypes.c_void_p), chunk, ctypes.byref(out), stream))
+        check(lib.agx_net_score_dataset_ex(net._net, self._h, rec.shape[0], rec.ctypes.data_as(ctypes.c_void_p), chunk, batch_policy_flag(policy),
+                                           1 if q_weights else 0, ctypes.byref(out), stream))
         return score_dict(out)
 
     def sample(self, batch_size, generator):

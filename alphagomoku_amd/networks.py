@@ -212,16 +212,18 @@ def _address(x):
 
 
 def score_outputs(rows, cols, n, policy, value, policy_target, value_target, action_values=None, action_values_target=None, *,
-                  sample_scores=None, total=None, stream=None):
+                  sample_scores=None, total=None, stream=None, action_values_weight=None):
     """agx_net_score_outputs: losses and top-4 hits of n samples from a network's outputs (the layout agx_nn_forward[_pvq] writes: policy
     [n, rows * cols], value [n, 3], action_values [n, rows * cols, 2]) and the targets (the layout load_batch writes: [n, rows, cols],
     [n, 3], [n, rows, cols, 3]), all float32 on the device: torch tensors, DeviceBuffers or raw addresses.  With torch tensors the
     launches go on torch.cuda.current_stream() unless `stream` names one (the library must share torch's HIP runtime, as for
     TrainingDataset.load_batch).  sample_scores: room for n AgxSampleScore records (48 bytes each) or None.
     total: a 72-byte device AgxNetScore the samples are ADDED to (clear it with score_clear; read it with score_total) — the call
-    then only enqueues and returns None.  Without it the call scores into a total of its own, waits and returns score_dict()."""
+    then only enqueues and returns None.  Without it the call scores into a total of its own, waits and returns score_dict().
+    action_values_weight: [n, rows, cols] (load_batch's q_weights=True) — the action-value cells that count are then those with a weight
+    > 0, each term multiplied by its weight (agx_net_score_outputs_weighted)."""
     from . import _lib
-    tensors = [policy, value, policy_target, value_target, action_values, action_values_target, sample_scores, total]
+    tensors = [policy, value, policy_target, value_target, action_values, action_values_target, sample_scores, total, action_values_weight]
     if any(hasattr(t, "data_ptr") for t in tensors):
         if not _lib.torch_shares_hip_runtime():
             raise _lib.AgxError("this torch carries a HIP runtime of its own: call alphagomoku_amd._lib.share_torch_hip_runtime() before the "
@@ -233,9 +235,9 @@ def score_outputs(rows, cols, n, policy, value, policy_target, value_target, act
     try:
         if own is not None:
             check(lib.agx_net_score_clear(own.ptr, stream))
-        check(lib.agx_net_score_outputs(rows, cols, n, _address(policy), _address(value), _address(action_values), _address(policy_target),
-                                        _address(value_target), _address(action_values_target), _address(sample_scores),
-                                        own.ptr if own is not None else _address(total), stream))
+        check(lib.agx_net_score_outputs_weighted(rows, cols, n, _address(policy), _address(value), _address(action_values), _address(policy_target),
+                                                 _address(value_target), _address(action_values_target), _address(action_values_weight),
+                                                 _address(sample_scores), own.ptr if own is not None else _address(total), stream))
         if own is None:
             return None
         check(lib.agx_stream_synchronize(stream))

@@ -39,8 +39,9 @@ def head_loss_reference(policy_logits, value_logits, q_logits, targets, weights=
     """The loss of head_loss as a plain torch composite, in the dtype of the logits: the CPU path and the yardstick of the tests.
     Per sample and head: sum over the entries with target t > 0 of t * (logsumexp(z) - z); the action values per cell over its 3 classes, on
     the cells whose POLICY target is > 0 only.  Targets that do not count are replaced by 0 BEFORE anything is multiplied, so a NaN among the
-    filler reaches neither the loss nor, through autograd, a gradient.  Returns (loss, components): loss = (w_p * policy_ce + w_v * value_ce +
-    w_q * q_ce) / n, components = the three sums / n."""
+    filler reaches neither the loss nor, through autograd, a gradient.  When targets holds "action_values_weight" (load_batch's q_weights=True)
+    the action-value cells that count are those with a weight > 0, and a cell's cross-entropy enters q_ce multiplied by its weight (w * ce).
+    Returns (loss, components): loss = (w_p * policy_ce + w_v * value_ce + w_q * q_ce) / n, components = the three sums / n."""
     n = policy_logits.shape[0]
     dtype = policy_logits.dtype
     pt, vt, qt = _targets(targets, n)
@@ -50,7 +51,13 @@ def head_loss_reference(policy_logits, value_logits, q_logits, targets, weights=
     vt = torch.where(vt > 0, vt.to(dtype), zero)
     policy_ce = -(pt * F.log_softmax(policy_logits.reshape(n, -1), dim=1)).sum()
     value_ce = -(vt * F.log_softmax(value_logits, dim=1)).sum()
-    if q_logits is not None:
+    if q_logits is not None and "action_values_weight" in targets:
+        w = targets["action_values_weight"].reshape(n, -1)
+        counts = w > 0
+        w = torch.where(counts, w.to(dtype), zero)
+        qt = torch.where(counts.unsqueeze(2) & (qt > 0), qt.to(dtype), zero)
+        q_ce = -(w * (qt * F.log_softmax(q_logits.reshape(n, -1, 3), dim=2)).sum(dim=2)).sum()
+    elif q_logits is not None:
         qt = torch.where(edge.unsqueeze(2) & (qt > 0), qt.to(dtype), zero)
         q_ce = -(qt * F.log_softmax(q_logits.reshape(n, -1, 3), dim=2)).sum()
     else:
@@ -64,16 +71,17 @@ class _HeadLoss(torch.autograd.Function):
     """forward runs csrc/head_loss.hip once and keeps dL/dlogits; backward multiplies them by grad_output"""
 
     @staticmethod
-    def forward(ctx, policy_logits, value_logits, q_logits, policy_target, value_target, q_target, weights):
+    def forward(ctx, policy_logits, value_logits, q_logits, policy_target, value_target, q_target, weights, q_weight=None):
         n, hw = policy_logits.shape
         rows, cols = policy_target.shape[1:3]
         with_q = q_logits is not None
         dev = policy_logits.device
-        tensors = [policy_logits, value_logits, q_logits if with_q else None, policy_target, value_target, q_target if with_q else None]
+        tensors = [policy_logits, value_logits, q_logits if with_q else None, policy_target, value_target, q_target if with_q else None,
+                   q_weight if with_q else None]
         for t in tensors:
             if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.device == dev):
                 raise ValueError("head_loss takes float32 tensors of one ROCm device")
-        shapes = [(n, rows * cols), (n, 3), (n, rows * cols, 3), (n, rows, cols), (n, 3), (n, rows, cols, 3)]
+        shapes = [(n, rows * cols), (n, 3), (n, rows * cols, 3), (n, rows, cols), (n, 3), (n, rows, cols, 3), (n, rows, cols)]
         for t, shape in zip(tensors, shapes):   # the kernel trusts the shapes
             if t is not None and tuple(t.shape) != shape:
                 raise ValueError("head_loss: a tensor of shape %s where %s is expected" % (tuple(t.shape), shape))
@@ -85,8 +93,8 @@ class _HeadLoss(torch.autograd.Function):
         ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            check(lib.agx_head_loss_grad(rows, cols, n, *[ptr(t) for t in tensors], weights[0] / n, weights[1] / n, weights[2] / n,
-                                         *[ptr(g) for g in grads], ptr(records), ptr(total), stream))
+            check(lib.agx_head_loss_grad_weighted(rows, cols, n, *[ptr(t) for t in tensors], weights[0] / n, weights[1] / n, weights[2] / n,
+                                                  *[ptr(g) for g in grads], ptr(records), ptr(total), stream))
         ctx.grads = grads
         components = total[1:4] / n
         loss = (weights[0] * components[0] + weights[1] * components[1] + weights[2] * components[2]).to(torch.float32)
@@ -95,7 +103,7 @@ class _HeadLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss, _grad_components, _grad_total):
-        return tuple(None if (g is None or not need) else g * grad_loss for g, need in zip(ctx.grads, ctx.needs_input_grad[:3])) + (None,) * 4
+        return tuple(None if (g is None or not need) else g * grad_loss for g, need in zip(ctx.grads, ctx.needs_input_grad[:3])) + (None,) * 5
 
 
 def _head_loss_total(policy_logits, value_logits, q_logits, targets, weights):
@@ -104,12 +112,14 @@ def _head_loss_total(policy_logits, value_logits, q_logits, targets, weights):
                        "used in this process")
     n = policy_logits.shape[0]
     return _HeadLoss.apply(policy_logits.reshape(n, -1), value_logits, None if q_logits is None else q_logits.reshape(n, -1, 3),
-                           targets["policy_target"], targets["value_target"], targets["action_values_target"], tuple(float(w) for w in weights))
+                           targets["policy_target"], targets["value_target"], targets["action_values_target"], tuple(float(w) for w in weights),
+                           targets.get("action_values_weight"))
 
 
 def head_loss(policy_logits, value_logits, q_logits, targets, weights=LOSS_WEIGHTS):
     """The training loss on the device: policy_logits [n, rows * cols], value_logits [n, 3], q_logits [n, rows, cols, 3] or None (float32,
-    pre-softmax), targets a load_batch dict (policy_target, value_target, action_values_target).  One call of agx_head_loss_grad on torch's
+    pre-softmax), targets a load_batch dict (policy_target, value_target, action_values_target, and action_values_weight when the batch was
+    loaded with q_weights=True: the action-value loss is then the weighted form of agx_head_loss_grad_weighted).  One call on torch's
     current stream computes the losses AND the gradients of the logits (scales weight / n); autograd's backward only multiplies them by
     grad_output.  Returns (loss, components): loss a float32 device scalar (w_p * policy_ce + w_v * value_ce + w_q * q_ce) / n, components a
     float64 device tensor of the three sums / n (not differentiable).  Nothing is synchronised with the host."""
@@ -260,19 +270,32 @@ def import_blob(module, blob):
 class Trainer:
     """RAdam over the trainable parameters of `module` on batches of `dataset`: a TrainingDataset, or anything with its load_batch(samples, out=,
     features=) and sample(batch_size, generator).  A module on a ROCm device trains through head_loss (the HIP kernel), a module on the CPU
-    through head_loss_reference."""
+    through head_loss_reference.  policy and q_weights choose the targets, as TrainingDataset.load_batch names them (they are passed to
+    load_batch only when they differ from its defaults); reference_targets() is the pair the reference's default configuration trains on."""
 
-    def __init__(self, module, dataset, lr=1e-3, weights=LOSS_WEIGHTS):
+    def __init__(self, module, dataset, lr=1e-3, weights=LOSS_WEIGHTS, policy="torch_api", q_weights=False):
         self.module, self.dataset, self.weights = module, dataset, tuple(float(w) for w in weights)
+        self.target_options = {}
+        if policy != "torch_api":
+            self.target_options["policy"] = policy
+        if q_weights:
+            self.target_options["q_weights"] = True
         self.optimizer = torch.optim.RAdam([p for p in module.parameters() if p.requires_grad], lr=lr)
         self._buffers = {}   # batch size -> the tensors load_batch writes into, reused
+
+    @staticmethod
+    def reference_targets():
+        """Trainer(module, dataset, **Trainer.reference_targets()): what the reference's default configuration trains on — the policy target of
+        SamplerValues (TrainingConfig::sampler_type = "values") and the action-value loss weighted per cell by visits / sum of visits
+        (fill_action_values_mask), for which its loss weight 0.05 was chosen"""
+        return dict(policy="values", q_weights=True)
 
     def _on_device(self):
         return next(self.module.parameters()).is_cuda
 
     def _forward(self, samples, reuse):
         n = len(samples)
-        batch = self.dataset.load_batch(samples, out=self._buffers.get(n) if reuse else None, features=False)
+        batch = self.dataset.load_batch(samples, out=self._buffers.get(n) if reuse else None, features=False, **self.target_options)
         if reuse:
             self._buffers[n] = batch
         return batch, self.module(batch["input"])
@@ -295,7 +318,9 @@ class Trainer:
 
     def evaluate(self, samples, chunk=256):
         """the eval-mode losses (running batch-norm statistics: what export_blob folds) over samples [n, 4], as TrainingDataset.score names them:
-        policy_loss and value_loss per sample, q_loss per cell that had an edge, plus the sums.  Waits for the result."""
+        policy_loss and value_loss per sample, q_loss per cell that had an edge, plus the sums.  With q_weights every cell's term carries its
+        weight (they sum to 1 per sample): q_loss is then q_ce / samples, the weighted mean per sample, and q_cells counts the cells with a
+        weight.  Waits for the result."""
         samples = np.asarray(samples, dtype=np.int32).reshape(-1, 4)
         was_training = self.module.training
         self.module.eval()
@@ -308,13 +333,14 @@ class Trainer:
                     _, components = (head_loss if self._on_device() else head_loss_reference)(policy, value, q, batch, self.weights)
                     sums += components.double().cpu() * len(part)
                     if q is not None:
-                        cells += int((batch["policy_target"] > 0).sum())
+                        cells += int((batch["action_values_weight" if "action_values_weight" in batch else "policy_target"] > 0).sum())
         finally:
             self.module.train(was_training)
         n = len(samples)
         policy_ce, value_ce, q_ce = (float(s) for s in sums)
+        q_loss = (q_ce / n if n else 0.0) if self.target_options.get("q_weights") else (q_ce / cells if cells else 0.0)
         return dict(samples=n, policy_ce=policy_ce, value_ce=value_ce, q_ce=q_ce, q_cells=cells, policy_loss=policy_ce / n if n else 0.0,
-                    value_loss=value_ce / n if n else 0.0, q_loss=q_ce / cells if cells else 0.0)
+                    value_loss=value_ce / n if n else 0.0, q_loss=q_loss)
 
     def export_to(self, net):
         """loads the module, batch norms folded, into an AGNetwork"""

@@ -585,7 +585,8 @@ typedef struct AgxTensorShape
 enum
 {
 	AGX_BATCH_INPUT_FP16 = 1,    /* d_input holds IEEE half values instead of float32 */
-	AGX_BATCH_POLICY_VISITS = 2  /* policy target of SamplerVisits (dataset/Sampler.cpp:96-133): a proven draw keeps its visit count; default: torch_api.cpp's max(1, visits) */
+	AGX_BATCH_POLICY_VISITS = 2, /* policy target of SamplerVisits (dataset/Sampler.cpp:96-133): a proven draw keeps its visit count; default: torch_api.cpp's max(1, visits) */
+	AGX_BATCH_POLICY_VALUES = 4  /* policy and action-value targets of SamplerValues (dataset/Sampler.cpp:138-214), the reference's default sampler; not together with AGX_BATCH_POLICY_VISITS */
 };
 
 int agx_dataset_create(int rules, int rows, int cols, AgxDataset** out);
@@ -626,6 +627,41 @@ int agx_dataset_load_batch(AgxDataset* dataset, int n, const AgxDatasetSample* h
  * when the data is there).  Calls from several threads run one after the other. */
 int agx_dataset_load_batch_host(AgxDataset* dataset, int n, const AgxDatasetSample* h_samples, void* h_input, uint32_t* h_features, float* h_policy,
 		float* h_value, float* h_moves_left, float* h_action_values, int flags);
+/* The extended form: the same launch with one more output, and the form new outputs will be added to.  The two calls above forward to it
+ * with action_values_weight = NULL and write exactly what they wrote before it existed.
+ *   action_values_weight [n][rows][cols] float32, may be NULL: the weight of the cell in the action-value loss, visits / sum of visits as
+ *                    the reference's fill_action_values_mask forms it (selfplay/SupervisedLearning.cpp:55-61): w = float(c) * (1.0f /
+ *                    float(sum of c)), with c = max(1, visits) on an empty cell with a proven score and c = visits on every other cell — the
+ *                    count both of the reference's samplers leave in TrainingDataPack::visit_count.  The same in every policy mode.  When
+ *                    the sum is 0 every weight is 0.0f (this project's rule: the reference would divide by zero).
+ * AGX_BATCH_POLICY_VALUES (not together with AGX_BATCH_POLICY_VISITS: AGX_ERR_INVALID before anything is launched) writes what
+ * SamplerValues::prepare_training_data (dataset/Sampler.cpp:138-214) writes, in float32, one operation after the other, unfused.  With
+ * board = the transformed board, prior = PriorFormat::decode * policy_scale, q(cell) = the expectation win + 0.5f * draw of the proven
+ * score's value or else of the stored action value, V = the same of the sample's minimax value and score (storeTo's rule, its sums taken
+ * in entry order), and `counted` = an empty cell with visits > 0 or a proven score:
+ *   sum_P, sum_PxQ   prior and prior * q added over the counted cells in cell order, from 0.0f; u = the number of the other empty cells
+ *   base             = sum_P * sum_PxQ + (1.0f - sum_P) * V
+ *   logit            = 50.0f * Q + logf(FLT_EPSILON + P) on every empty cell: Q = base, P = max(0.0f, (1.0f - sum_P) / u) on a cell that is
+ *                      not counted (u == 0: there is no such cell, nothing is divided); on a counted cell P = prior and Q = -1.0f / (1.0f +
+ *                      distance) for a proven loss, 0.5f for a proven draw, 1.0f + 2.0f / (1.0f + distance) for a proven win, the stored
+ *                      action value's expectation otherwise
+ *   policy           = e / sum on the empty cells (a true division), e = expf(max(-20.0f, logit - the largest logit)), sum = the e added
+ *                      in cell order from 0.0f; exactly 0.0f on occupied cells
+ *   action values    as in the other modes on the counted cells, (0, 0, 1) on every other cell
+ * All sums run in cell order of the TRANSFORMED board (the reference samples first and applies the symmetry afterwards: its sums run in
+ * the untransformed order; the two differ by float32 rounding only).  logf and expf are the device's: within 1 ulp of a host libm. */
+typedef struct AgxBatchTensors
+{ /* device addresses for agx_dataset_load_batch_ex, host addresses for agx_dataset_load_batch_host_ex */
+	void* input;                 /* may be NULL */
+	uint32_t* features;          /* may be NULL */
+	float* policy;
+	float* value;
+	float* moves_left;
+	float* action_values;
+	float* action_values_weight; /* may be NULL */
+} AgxBatchTensors;
+int agx_dataset_load_batch_ex(AgxDataset* dataset, int n, const AgxDatasetSample* h_samples, const AgxBatchTensors* tensors, int flags, void* stream);
+int agx_dataset_load_batch_host_ex(AgxDataset* dataset, int n, const AgxDatasetSample* h_samples, const AgxBatchTensors* tensors, int flags);
 
 /* ----------------------------------------------------------------------------------------------
  * Scoring a network against saved games: losses and top-k accuracy, on the device (csrc/net_score.hip).
@@ -680,6 +716,20 @@ int agx_net_score_outputs(int rows, int cols, int n, const float* d_policy, cons
  * it).  The total does not depend on `chunk`.  AGX_ERR_INVALID: null arguments, n <= 0, negative chunk, a dataset whose board is not the
  * network's; the dataset's and the network's own errors pass through. */
 int agx_net_score_dataset(AgxNet* net, AgxDataset* dataset, int n, const AgxDatasetSample* h_samples, int chunk, AgxNetScore* h_out, void* stream);
+/* agx_net_score_outputs with a weight per cell for the action-value term: d_q_weight float[n][rows*cols], the action_values_weight of
+ * agx_dataset_load_batch_ex (needs the two action-value tensors).  A cell then counts when its weight is > 0, not when its policy target
+ * is: its three float32 terms are added in class order in float64 from 0.0, the sum is multiplied by (double) w and added to q_ce;
+ * q_cells counts the cells with w > 0.  A cell whose weight is not > 0 (zero, negative, NaN) is not read: a NaN among its outputs or
+ * targets reaches nothing.  q_ce / samples is then the mean of the per-sample weighted means, the loss the reference's weight 0.05 of the
+ * action-value output was chosen for.  d_q_weight == NULL gives the bits of agx_net_score_outputs.  Chaining and determinism as above. */
+int agx_net_score_outputs_weighted(int rows, int cols, int n, const float* d_policy, const float* d_value, const float* d_action_values,
+		const float* d_policy_target, const float* d_value_target, const float* d_action_values_target, const float* d_q_weight,
+		AgxSampleScore* d_sample_scores, AgxNetScore* d_total, void* stream);
+/* agx_net_score_dataset with the loader's flags (AGX_BATCH_POLICY_VISITS or AGX_BATCH_POLICY_VALUES; AGX_BATCH_INPUT_FP16 is refused: the
+ * path reads feature words, no input planes) and, with q_weighted != 0, the weighted action-value term on the loader's
+ * action_values_weight.  agx_net_score_dataset is this call with 0, 0. */
+int agx_net_score_dataset_ex(AgxNet* net, AgxDataset* dataset, int n, const AgxDatasetSample* h_samples, int chunk, int batch_flags, int q_weighted,
+		AgxNetScore* h_out, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Training: the loss of the three heads and its gradients with respect to the LOGITS, on the device (csrc/head_loss.hip).
@@ -712,6 +762,19 @@ int agx_head_loss_grad(int rows, int cols, int n,
 		AgxSampleScore* d_sample_scores, /* [n], required */
 		AgxNetScore* d_total,            /* added to, like agx_net_score_outputs */
 		void* stream);
+/* agx_head_loss_grad with a weight per cell for the action-value head: d_q_weight float[n][rows*cols], the action_values_weight of
+ * agx_dataset_load_batch_ex (needs the action-value tensors).  A cell then counts when its weight w is > 0, not when its policy target is:
+ *   q_ce       the cell's cross-entropy is formed as above (its float32 terms added in class order in float64, from 0.0), multiplied by
+ *              (double) w and added to the sample's sum; q_cells counts the cells with w > 0
+ *   gradient_i = (q_scale * w) * (p_i * T - t_i): the float32 product q_scale * w first, then its float32 product with the float32
+ *              difference; with w == 1.0f these are the bits of the unweighted form
+ * A cell whose weight is not > 0 (zero, negative, NaN) gets the gradient exactly 0.0f; neither its logits nor its targets are read, a NaN
+ * among them or in the weight itself reaches nothing.  d_q_weight == NULL gives the bits of agx_head_loss_grad.  Chaining and determinism
+ * as above: totals are bit-identical however a set of samples is split into calls. */
+int agx_head_loss_grad_weighted(int rows, int cols, int n, const float* d_policy_logits, const float* d_value_logits, const float* d_q_logits,
+		const float* d_policy_target, const float* d_value_target, const float* d_q_target, const float* d_q_weight, float policy_scale,
+		float value_scale, float q_scale, float* d_policy_grad, float* d_value_grad, float* d_q_grad, AgxSampleScore* d_sample_scores,
+		AgxNetScore* d_total, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Positions evaluated on the device: boards -> policy, value, best moves (csrc/position_eval.hip).

@@ -541,6 +541,16 @@ namespace agx
 				value_scale, q_scale, d_policy_grad, d_value_grad, d_q_grad, d_sample_scores, d_total, stream));
 	}
 
+	/* ... with a weight per cell for the action-value head (agx.h: agx_head_loss_grad_weighted): d_q_weight is the action_values_weight of
+	 * TrainingDataset::loadBatch(samples, tensors, ...); null gives the unweighted form */
+	inline void head_loss_grad(int rows, int cols, int n, const float *d_policy_logits, const float *d_value_logits, const float *d_q_logits,
+			const float *d_policy_target, const float *d_value_target, const float *d_q_target, const float *d_q_weight, float policy_scale, float value_scale,
+			float q_scale, float *d_policy_grad, float *d_value_grad, float *d_q_grad, AgxSampleScore *d_sample_scores, AgxNetScore *d_total, void *stream = nullptr)
+	{
+		check(agx_head_loss_grad_weighted(rows, cols, n, d_policy_logits, d_value_logits, d_q_logits, d_policy_target, d_value_target, d_q_target, d_q_weight,
+				policy_scale, value_scale, q_scale, d_policy_grad, d_value_grad, d_q_grad, d_sample_scores, d_total, stream));
+	}
+
 	/* The consumer of the record sink: format-201 games -> training tensors on the device (agx.h: agx_dataset_*; what the reference's
 	 * dataset/torch_api.h reader does on one host thread).  Fragments are numbered like Dataset::load(i, path). */
 	class TrainingDataset
@@ -596,12 +606,26 @@ namespace agx
 				check(agx_dataset_load_batch(m_dataset, static_cast<int>(samples.size()), samples.data(), d_input, d_features, d_policy, d_value, d_moves_left,
 						d_action_values, flags, stream));
 			}
+			/* the extended form: every output in one struct, action_values_weight among them (may be null); flags may name the policy
+			 * target (AGX_BATCH_POLICY_VISITS or AGX_BATCH_POLICY_VALUES) */
+			void loadBatch(const std::vector<AgxDatasetSample> &samples, const AgxBatchTensors &tensors, int flags = 0, void *stream = nullptr)
+			{
+				check(agx_dataset_load_batch_ex(m_dataset, static_cast<int>(samples.size()), samples.data(), &tensors, flags, stream));
+			}
 			/* losses and top-k accuracy of `net` on these samples: batch, network and reductions on the device, `chunk` samples at a time
 			 * (0 = 1024); waits for the result */
 			NetScore score(const AGNetwork &net, const std::vector<AgxDatasetSample> &samples, int chunk = 0, void *stream = nullptr)
 			{
 				NetScore result;
 				check(agx_net_score_dataset(net.handle(), m_dataset, static_cast<int>(samples.size()), samples.data(), chunk, &result, stream));
+				return result;
+			}
+			/* ... against the targets of a policy flag, the action-value term weighted per cell by visits / sum of visits when q_weighted */
+			NetScore score(const AGNetwork &net, const std::vector<AgxDatasetSample> &samples, int chunk, int batch_flags, bool q_weighted, void *stream = nullptr)
+			{
+				NetScore result;
+				check(agx_net_score_dataset_ex(net.handle(), m_dataset, static_cast<int>(samples.size()), samples.data(), chunk, batch_flags, q_weighted ? 1 : 0, &result,
+						stream));
 				return result;
 			}
 			AgxDataset* handle() const noexcept
