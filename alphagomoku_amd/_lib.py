@@ -94,6 +94,12 @@ def _declare(c):
     c.agx_nn_forward_pvq.argtypes = [vp, vp, ci, vp, vp, vp, vp]
     c.agx_nn_forward_indirect_pvq.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp]
     c.agx_net_destroy.argtypes = [vp]
+    c.agx_net_blob_floats_ex.restype = sz
+    c.agx_net_blob_floats_ex.argtypes = [ctypes.POINTER(AgxNetDesc), ci, ci]
+    c.agx_net_create_ex.argtypes = [ctypes.POINTER(AgxNetDesc), ci, ci, ctypes.POINTER(vp)]
+    c.agx_net_architecture.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    c.agx_nn_forward_pvqm.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp]
+    c.agx_nn_forward_indirect_pvqm.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]
     c.agx_malloc.argtypes = [ctypes.POINTER(vp), sz]
     c.agx_free.argtypes = [vp]
     c.agx_memcpy_h2d.argtypes = [vp, vp, sz]
@@ -354,6 +360,8 @@ class AgxPositionOutputs(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ["policy", "value", "action_values", "top_cells", "top_probs", "status"]]
 
 
+ARCH_RESNET, ARCH_CONVNEXT = 0, 1   # AgxNetArchitecture
+ARCHITECTURES = {"resnet": ARCH_RESNET, "convnext": ARCH_CONVNEXT}
 POSEVAL_MASK_FORBIDDEN, POSEVAL_RENORMALISE = 1, 2
 POSEVAL_STATUS_BAD_INPUT, POSEVAL_STATUS_FOUL_PROBE = 1, 2
 

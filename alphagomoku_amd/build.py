@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libagx.so")
 
 INCLUDE = os.path.join(HERE, "..", "include")
-SOURCES = ["agx_api.hip", "nn_forward.hip", "nn_any_board.hip", "engine.hip", "training_batch.hip", "net_score.hip", "head_loss.hip", "position_eval.hip", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
+SOURCES = ["agx_api.hip", "nn_forward.hip", "nn_any_board.hip", "nn_convnext.hip", "engine.hip", "training_batch.hip", "net_score.hip", "head_loss.hip", "position_eval.hip", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
 DRIVER = os.path.join(HERE, "agx_selfplay")
 AG_LIB = os.path.join(HERE, "libagx_ag.so")               # the reference-named C++ classes (include/alphagomoku_agx/) over the C ABI
 BOUNDARY_TEST = os.path.join(HERE, "agx_boundary_test")  # tests/cpp/boundary_main.cpp: the reference's call chain on those classes
@@ -27,6 +27,8 @@ POSITION_TEST = os.path.join(HERE, "agx_position_eval_test")  # tests/cpp/positi
 POSITION_SRC = os.path.join(HERE, "..", "tests", "cpp", "position_eval_main.cpp")
 TARGETS_TEST = os.path.join(HERE, "agx_training_targets_test")  # tests/cpp/training_targets_main.cpp: the values targets and the weighted loss through agx.hpp
 TARGETS_SRC = os.path.join(HERE, "..", "tests", "cpp", "training_targets_main.cpp")
+CONVNEXT_TEST = os.path.join(HERE, "agx_convnext_test")  # tests/cpp/convnext_main.cpp: the ConvNeXt architectures through ag::AGNetwork, container included
+CONVNEXT_SRC = os.path.join(HERE, "..", "tests", "cpp", "convnext_main.cpp")
 HOST_ONLY = ("ag_classes.cpp", "selfplay_main.cpp")  # plain g++ sources in csrc/ (not part of libagx.so)
 
 
@@ -96,6 +98,8 @@ def _stale_host_targets():
         out.append(POSITION_TEST)
     if _mtime(TARGETS_TEST) < max(_mtime(TARGETS_SRC), headers, _mtime(LIB)):
         out.append(TARGETS_TEST)
+    if _mtime(CONVNEXT_TEST) < max(_mtime(CONVNEXT_SRC), headers, _mtime(AG_LIB)) or AG_LIB in out:
+        out.append(CONVNEXT_TEST)
     return out
 
 
@@ -160,7 +164,7 @@ def build(force=False, verbose=True):
         relink = True
     if relink:
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + [BUILD_ID_OBJ, "-lz"])
-    stale = [DRIVER, AG_LIB, BOUNDARY_TEST, TRAINING_TEST, SCORE_TEST, POSITION_TEST, TARGETS_TEST] if force else _stale_host_targets()
+    stale = [DRIVER, AG_LIB, BOUNDARY_TEST, TRAINING_TEST, SCORE_TEST, POSITION_TEST, TARGETS_TEST, CONVNEXT_TEST] if force else _stale_host_targets()
     if DRIVER in stale:  # native C++ host driver over the C ABI (include/agx.hpp)
         run([cxx, "-std=c++17", "-O2", "-o", DRIVER, os.path.join(CSRC, "selfplay_main.cpp"), "-L" + HERE, "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     if AG_LIB in stale:  # the C++ boundary: plain host code (g++), no HIP types — a maintainer of the reference links it like any other library
@@ -176,6 +180,8 @@ def build(force=False, verbose=True):
         run([cxx, "-std=c++17", "-O2", "-Wall", "-o", POSITION_TEST, POSITION_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     if TARGETS_TEST in stale:
         run([cxx, "-std=c++17", "-O2", "-Wall", "-o", TARGETS_TEST, TARGETS_SRC, "-L" + HERE, "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
+    if CONVNEXT_TEST in stale:
+        run([cxx, "-std=c++17", "-O2", "-Wall", "-o", CONVNEXT_TEST, CONVNEXT_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     return LIB
 
 

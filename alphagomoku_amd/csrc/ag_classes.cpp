@@ -88,15 +88,19 @@ namespace ag
 	AGNetwork::AGNetwork(const GameConfig &gameOptions, const std::string &architecture, int blocks, int filters) :
 			game_config(gameOptions)
 	{
-		if (architecture != "ResnetPV" && architecture != "ResnetPVQ" && architecture != "ResnetPVraw")
-			throw std::logic_error("AGNetwork: unknown architecture '" + architecture + "' (the device tower implements ResnetPV, ResnetPVraw and ResnetPVQ)");
+		const bool convnext = (architecture == "ConvNextPVQraw" || architecture == "ConvNextPVQMraw");
+		if (architecture != "ResnetPV" && architecture != "ResnetPVQ" && architecture != "ResnetPVraw" && !convnext)
+			throw std::logic_error("AGNetwork: unknown architecture '" + architecture
+					+ "' (the device towers implement ResnetPV, ResnetPVraw, ResnetPVQ, ConvNextPVQraw and ConvNextPVQMraw)");
+		this->architecture = convnext ? AGX_ARCH_CONVNEXT : AGX_ARCH_RESNET;
+		moves_left = (architecture == "ConvNextPVQMraw") ? 1 : 0;
 		desc.rows = gameOptions.rows;
 		desc.cols = gameOptions.cols;
 		desc.blocks = blocks;
 		desc.filters = filters;
-		desc.in_channels = (architecture == "ResnetPVraw") ? 8 : 32; // networks.cpp:107-129: the raw network sees the 8 low bits of a feature word
-		desc.value_hidden = std::min(256, 2 * filters);
-		desc.action_values = (architecture == "ResnetPVQ") ? 1 : 0;
+		desc.in_channels = (architecture == "ResnetPVraw" || convnext) ? 8 : 32; // networks.cpp:107-129: the raw networks see the 8 low bits of a feature word
+		desc.value_hidden = convnext ? 256 : std::min(256, 2 * filters);
+		desc.action_values = (architecture == "ResnetPVQ" || convnext) ? 1 : 0;
 		create();
 	}
 	AGNetwork::~AGNetwork()
@@ -105,13 +109,13 @@ namespace ag
 	}
 	void AGNetwork::create()
 	{
-		check(agx_net_create(&desc, &net));
+		check(agx_net_create_ex(&desc, architecture, moves_left, &net));
 		if (!blob_copy.empty())
 			check(agx_net_load_weights(net, blob_copy.data(), blob_copy.size()));
 	}
 	void AGNetwork::release()
 	{
-		void **buffers[] = { &d_input, &d_policy, &d_value, &d_action_values, &d_boards, &d_signs, &d_board_status };
+		void **buffers[] = { &d_input, &d_policy, &d_value, &d_action_values, &d_moves_left, &d_boards, &d_signs, &d_board_status };
 		for (void **p : buffers)
 		{
 			if (*p != nullptr)
@@ -127,15 +131,17 @@ namespace ag
 	}
 	std::string AGNetwork::getOutputConfig() const
 	{
-		return desc.action_values ? "pvq" : "pv";
+		return moves_left ? "pvqm" : (desc.action_values ? "pvq" : "pv");
 	}
 	std::string AGNetwork::name() const
 	{
+		if (architecture == AGX_ARCH_CONVNEXT)
+			return moves_left ? "ConvNextPVQMraw" : "ConvNextPVQraw";
 		return desc.action_values ? "ResnetPVQ" : (desc.in_channels == 8 ? "ResnetPVraw" : "ResnetPV");
 	}
 	size_t AGNetwork::numberOfWeights() const
 	{
-		return agx_net_blob_floats(&desc);
+		return agx_net_blob_floats_ex(&desc, architecture, moves_left);
 	}
 	void AGNetwork::loadWeights(const std::vector<float> &blob)
 	{
@@ -185,6 +191,12 @@ namespace ag
 				actionValues[i] = Value(action_values[(static_cast<size_t>(index) * hw + i) * 2], action_values[(static_cast<size_t>(index) * hw + i) * 2 + 1]);
 		out_value = Value(value[3 * index], value[3 * index + 1]); // (win, draw) of the softmax over (win, draw, loss)
 		movesLeft = 0.0f;                                            // 'pv' / 'pvq' networks have no moves-left output
+		if (moves_left)
+		{ // NetworkDataPack::unpackMovesLeft (NetworkDataPack.cpp:224-235)
+			const float *m = moves_left_out.data() + static_cast<size_t>(index) * hw;
+			for (int i = 0; i < hw; i++)
+				movesLeft += m[i] * i;
+		}
 	}
 	void AGNetwork::asyncForwardLaunch(int batch)
 	{
@@ -210,7 +222,10 @@ namespace ag
 				encoded = last + 1;
 				first = last;
 			}
-		if (desc.action_values)
+		if (moves_left)
+			check(agx_nn_forward_pvqm(net, static_cast<const uint32_t*>(d_input), batch, static_cast<float*>(d_policy), static_cast<float*>(d_value),
+					static_cast<float*>(d_action_values), static_cast<float*>(d_moves_left), nullptr));
+		else if (desc.action_values)
 			check(agx_nn_forward_pvq(net, static_cast<const uint32_t*>(d_input), batch, static_cast<float*>(d_policy), static_cast<float*>(d_value),
 					static_cast<float*>(d_action_values), nullptr));
 		else
@@ -225,6 +240,8 @@ namespace ag
 		check(agx_memcpy_d2h(value.data(), d_value, sizeof(float) * 3 * launched));
 		if (desc.action_values)
 			check(agx_memcpy_d2h(action_values.data(), d_action_values, sizeof(float) * 2 * hw * launched));
+		if (moves_left)
+			check(agx_memcpy_d2h(moves_left_out.data(), d_moves_left, sizeof(float) * hw * launched));
 		launched = 0;
 		if (encoded > 0)
 		{
@@ -257,8 +274,13 @@ namespace ag
 		if (!f.good())
 			throw std::runtime_error("AGNetwork::saveToFile() : cannot open '" + path + "'");
 		const uint64_t count = blob_copy.size();
-		f.write("AGXW", 4);
+		f.write((architecture == AGX_ARCH_RESNET) ? "AGXW" : "AGXC", 4);
 		f.write(reinterpret_cast<const char*>(&desc), sizeof(desc));
+		if (architecture != AGX_ARCH_RESNET)
+		{ // the ConvNeXt container: two more ints behind the description
+			const int32_t extra[2] = { architecture, moves_left };
+			f.write(reinterpret_cast<const char*>(extra), sizeof(extra));
+		}
 		f.write(reinterpret_cast<const char*>(&count), sizeof(count));
 		f.write(reinterpret_cast<const char*>(blob_copy.data()), sizeof(float) * count);
 	}
@@ -272,8 +294,12 @@ namespace ag
 		AgxNetDesc d;
 		f.read(magic, 4);
 		f.read(reinterpret_cast<char*>(&d), sizeof(d));
+		int32_t extra[2] = { AGX_ARCH_RESNET, 0 };
+		const bool convnext_container = f.good() && std::memcmp(magic, "AGXC", 4) == 0;
+		if (convnext_container)
+			f.read(reinterpret_cast<char*>(extra), sizeof(extra));
 		f.read(reinterpret_cast<char*>(&count), sizeof(count));
-		if (!f.good() || std::memcmp(magic, "AGXW", 4) != 0)
+		if (!f.good() || (std::memcmp(magic, "AGXW", 4) != 0 && !convnext_container))
 			throw std::runtime_error("'" + path + "' is not a weight file of this library (MinML checkpoints cannot be imported: their format is not in the reference tree)");
 		std::vector<float> blob(count);
 		f.read(reinterpret_cast<char*>(blob.data()), sizeof(float) * count);
@@ -281,6 +307,8 @@ namespace ag
 			throw std::runtime_error("'" + path + "' is truncated");
 		release();
 		desc = d;
+		architecture = extra[0];
+		moves_left = extra[1];
 		game_config.rows = d.rows;
 		game_config.cols = d.cols;
 		if (game_config.draw_after <= 0)
@@ -329,7 +357,7 @@ namespace ag
 			throw std::logic_error("AGNetwork::setBatchSize() : batch size must be positive");
 		if (batchSize == batch_size && d_input != nullptr)
 			return;
-		void **buffers[] = { &d_input, &d_policy, &d_value, &d_action_values, &d_boards, &d_signs, &d_board_status };
+		void **buffers[] = { &d_input, &d_policy, &d_value, &d_action_values, &d_moves_left, &d_boards, &d_signs, &d_board_status };
 		for (void **p : buffers)
 		{
 			if (*p != nullptr)
@@ -354,6 +382,9 @@ namespace ag
 		check(agx_malloc(&d_value, sizeof(float) * n * 3));
 		if (desc.action_values)
 			check(agx_malloc(&d_action_values, sizeof(float) * n * hw * 2));
+		moves_left_out.assign(moves_left ? n * hw : 0, 0.0f);
+		if (moves_left)
+			check(agx_malloc(&d_moves_left, sizeof(float) * n * hw));
 	}
 	GameConfig AGNetwork::getGameConfig() const noexcept
 	{

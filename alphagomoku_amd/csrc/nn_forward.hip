@@ -40,6 +40,7 @@
 #include "agx_internal.hpp"
 #include "nn_device.hpp"
 #include "nn_any_board.hpp"
+#include "nn_convnext.hpp"
 
 #include <vector>
 #include <mutex>
@@ -1875,6 +1876,10 @@ struct AgxNet
 		int num_cus = 256;
 		int launch_width = 0; // 0 = every CU
 		int kpad() const { return (desc.rows * desc.cols * 4 + 31) / 32 * 32; } // value-head dense input length: 4 HW padded to whole MFMA k-steps
+		// AGX_ARCH_CONVNEXT: the network lives in nn_convnext.hip; of the members above only desc, loaded, num_cus and launch_width are used
+		int architecture = AGX_ARCH_RESNET;
+		int moves_left = 0;
+		agx_cnx::Net *convnext = nullptr;
 };
 
 namespace
@@ -1929,6 +1934,45 @@ size_t agx_net_blob_floats(const AgxNetDesc *d)
 	return n;
 }
 
+size_t agx_net_blob_floats_ex(const AgxNetDesc *d, int architecture, int moves_left)
+{
+	if (d == nullptr)
+		return 0;
+	if (architecture == AGX_ARCH_CONVNEXT)
+		return agx_cnx::blob_floats(*d, moves_left);
+	return (architecture == AGX_ARCH_RESNET && moves_left == 0) ? agx_net_blob_floats(d) : 0;
+}
+
+int agx_net_create_ex(const AgxNetDesc *desc, int architecture, int moves_left, AgxNet **out)
+{
+	AGX_REQUIRE(desc != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_net_create_ex: null argument");
+	if (architecture == AGX_ARCH_RESNET && moves_left == 0)
+		return agx_net_create(desc, out);
+	AGX_REQUIRE(architecture == AGX_ARCH_CONVNEXT, AGX_ERR_UNSUPPORTED, "agx_net_create_ex: unsupported architecture %d with moves_left=%d (the residual networks have no moves-left head)",
+			architecture, moves_left);
+	AGX_REQUIRE(agx_cnx::supported(*desc, moves_left), AGX_ERR_UNSUPPORTED,
+			"agx_net_create_ex: unsupported ConvNeXt network %dx%d blocks=%d filters=%d cin=%d hidden=%d action_values=%d moves_left=%d (supported: 5..20 rows and cols, F in {64,128}, cin 8, hidden 256, with the action-values head)",
+			desc->rows, desc->cols, desc->blocks, desc->filters, desc->in_channels, desc->value_hidden, desc->action_values, moves_left);
+	AgxNet *net = new AgxNet();
+	net->desc = *desc;
+	net->architecture = architecture;
+	net->moves_left = moves_left;
+	int dev = 0;
+	hipDeviceProp_t prop;
+	if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+		net->num_cus = prop.multiProcessorCount;
+	*out = net;
+	return AGX_OK;
+}
+
+int agx_net_architecture(const AgxNet *net, int *architecture, int *moves_left)
+{
+	AGX_REQUIRE(net != nullptr && architecture != nullptr && moves_left != nullptr, AGX_ERR_INVALID, "agx_net_architecture: null argument");
+	*architecture = net->architecture;
+	*moves_left = net->moves_left;
+	return AGX_OK;
+}
+
 int agx_net_create(const AgxNetDesc *desc, AgxNet **out)
 {
 	AGX_REQUIRE(desc != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_net_create: null argument");
@@ -1948,6 +1992,23 @@ int agx_net_create(const AgxNetDesc *desc, AgxNet **out)
 int agx_net_load_weights(AgxNet *net, const float *h_blob, size_t n_floats)
 {
 	AGX_REQUIRE(net != nullptr && h_blob != nullptr, AGX_ERR_INVALID, "agx_net_load_weights: null argument");
+	if (net->architecture == AGX_ARCH_CONVNEXT)
+	{
+		const size_t expected = agx_cnx::blob_floats(net->desc, net->moves_left);
+		AGX_REQUIRE(n_floats == expected, AGX_ERR_INVALID, "agx_net_load_weights: blob has %zu floats, expected %zu", n_floats, expected);
+		agx_cnx::Net *fresh = nullptr;
+		const int status = agx_cnx::load(net->desc, net->moves_left, h_blob, &fresh);
+		if (status != AGX_OK)
+			return status;
+		if (net->convnext != nullptr)
+		{ // (launches of the old weights may be in flight)
+			AGX_HIP_CHECK(hipDeviceSynchronize());
+			agx_cnx::destroy(net->convnext);
+		}
+		net->convnext = fresh;
+		net->loaded = true;
+		return AGX_OK;
+	}
 	AGX_REQUIRE(n_floats == agx_net_blob_floats(&net->desc), AGX_ERR_INVALID, "agx_net_load_weights: blob has %zu floats, expected %zu", n_floats,
 			agx_net_blob_floats(&net->desc));
 	free_net_buffers(net);
@@ -2061,7 +2122,7 @@ int agx_net_load_weights(AgxNet *net, const float *h_blob, size_t n_floats)
 }
 
 static int launch_forward(AgxNet *net, const uint32_t *d_features, const int *d_slot_list, const int *d_count, int batch, float *d_policy, float *d_value,
-		float *d_action_values, void *stream)
+		float *d_action_values, void *stream, float *d_moves_left = nullptr)
 {
 	AGX_REQUIRE(net != nullptr, AGX_ERR_INVALID, "agx_nn_forward: null network");
 	AGX_REQUIRE(net->loaded, AGX_ERR_STATE, "agx_nn_forward: weights not loaded");
@@ -2069,6 +2130,13 @@ static int launch_forward(AgxNet *net, const uint32_t *d_features, const int *d_
 	if (batch == 0)
 		return AGX_OK;
 	AGX_REQUIRE(d_features != nullptr && d_policy != nullptr && d_value != nullptr, AGX_ERR_INVALID, "agx_nn_forward: null buffer");
+	AGX_REQUIRE(d_moves_left == nullptr || net->moves_left, AGX_ERR_INVALID, "agx_nn_forward: the network has no moves-left head");
+	if (net->architecture == AGX_ARCH_CONVNEXT)
+	{ // the same persistent grid and launch-width cap as below; the ConvNeXt tower needs no scratch
+		const int cnx_width = (net->launch_width > 0 && net->launch_width < net->num_cus) ? net->launch_width : net->num_cus;
+		return agx_cnx::launch(net->convnext, (batch < cnx_width) ? batch : cnx_width, d_features, d_slot_list, d_count, batch, d_policy, d_value, d_action_values,
+				d_moves_left, static_cast<hipStream_t>(stream));
+	}
 
 	NetParams p;
 	p.w_in = static_cast<const half8*>(net->d_w_in);
@@ -2194,6 +2262,18 @@ int agx_nn_forward_indirect_pvq(AgxNet *net, const uint32_t *d_features, const i
 	return launch_forward(net, d_features, d_slot_list, d_count, max_batch, d_policy, d_value, d_action_values, stream);
 }
 
+int agx_nn_forward_pvqm(AgxNet *net, const uint32_t *d_features, int batch, float *d_policy, float *d_value, float *d_action_values, float *d_moves_left,
+		void *stream)
+{
+	return launch_forward(net, d_features, nullptr, nullptr, batch, d_policy, d_value, d_action_values, stream, d_moves_left);
+}
+int agx_nn_forward_indirect_pvqm(AgxNet *net, const uint32_t *d_features, const int *d_slot_list, const int *d_count, int max_batch, float *d_policy,
+		float *d_value, float *d_action_values, float *d_moves_left, void *stream)
+{
+	AGX_REQUIRE(d_slot_list != nullptr && d_count != nullptr, AGX_ERR_INVALID, "agx_nn_forward_indirect_pvqm: null list");
+	return launch_forward(net, d_features, d_slot_list, d_count, max_batch, d_policy, d_value, d_action_values, stream, d_moves_left);
+}
+
 #ifdef AGX_NN_PROFILE
 /* profile builds only: shader cycles per phase summed over the workgroups (waves 0 and 4), then reset.  out[2][16] */
 int agx_debug_nn_profile(unsigned long long *out)
@@ -2225,6 +2305,7 @@ int agx_net_destroy(AgxNet *net)
 	if (net == nullptr)
 		return AGX_OK;
 	free_net_buffers(net);
+	agx_cnx::destroy(net->convnext);
 	delete net;
 	return AGX_OK;
 }

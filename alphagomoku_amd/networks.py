@@ -4,7 +4,7 @@ All arithmetic happens in libagx.so (HIP); this class only owns handles and devi
 import ctypes
 import numpy as np
 
-from ._lib import lib, check, AgxNetDesc
+from ._lib import lib, check, AgxNetDesc, ARCHITECTURES
 
 
 class DeviceBuffer:
@@ -31,7 +31,8 @@ class DeviceBuffer:
 
 
 class AGNetwork:
-    """ResnetPV on the device.  `desc` is a dict as made by synthetic.net_desc()."""
+    """A network on the device.  `desc` is a dict as made by synthetic.net_desc() (ResnetPV / PVraw / PVQ) or synthetic.convnext_desc()
+    (ConvNextPVQraw / PVQMraw: desc["architecture"] == "convnext", desc["moves_left"] 0 or 1)."""
 
     def __init__(self, desc):
         self.desc = dict(desc)
@@ -40,32 +41,41 @@ class AGNetwork:
         self._net = ctypes.c_void_p()
         self._evaluators = {}          # rules -> (AgxPositionEvaluator, capacity), made by evaluate_positions
         self._retired_evaluators = []  # replaced by larger ones; destroyed in close() (destroying one waits for its last launch)
-        check(lib.agx_net_create(ctypes.byref(self._cdesc), ctypes.byref(self._net)))
+        name = desc.get("architecture", "resnet")
+        if name not in ARCHITECTURES:
+            raise ValueError("AGNetwork: unknown architecture %r (known: %s)" % (name, ", ".join(sorted(ARCHITECTURES))))
+        self._architecture, self._moves_left = ARCHITECTURES[name], int(desc.get("moves_left", 0))
+        check(lib.agx_net_create_ex(ctypes.byref(self._cdesc), self._architecture, self._moves_left, ctypes.byref(self._net)))
 
     def blobFloats(self):
-        return int(lib.agx_net_blob_floats(ctypes.byref(self._cdesc)))
+        return int(lib.agx_net_blob_floats_ex(ctypes.byref(self._cdesc), self._architecture, self._moves_left))
 
     def loadWeights(self, blob):
         blob = np.ascontiguousarray(blob, dtype=np.float32)
         check(lib.agx_net_load_weights(self._net, blob.ctypes.data_as(ctypes.c_void_p), blob.size))
 
     def load_module(self, module):
-        """loadWeights(training.export_blob(module)): a training.TowerModule of this network's description, its batch norms folded with their
-        running statistics"""
+        """loadWeights(training.export_blob(module)): a training.TowerModule or ConvNextModule of this network's description, its batch norms
+        folded with their running statistics"""
         from .training import export_blob
-        if {k: module.desc.get(k, 0) for k in self.desc} != {k: self.desc.get(k, 0) for k in self.desc}:
+        keys = set(self.desc) | set(module.desc)
+        defaults = dict(architecture="resnet")
+        if {k: module.desc.get(k, defaults.get(k, 0)) for k in keys} != {k: self.desc.get(k, defaults.get(k, 0)) for k in keys}:
             raise ValueError("load_module: the module's description %s is not the network's %s" % (module.desc, self.desc))
         self.loadWeights(export_blob(module))
 
-    def forwardDevice(self, d_features, batch, d_policy, d_value, stream=None, d_action_values=None):
-        if d_action_values is None:
+    def forwardDevice(self, d_features, batch, d_policy, d_value, stream=None, d_action_values=None, d_moves_left=None):
+        if d_moves_left is not None:
+            check(lib.agx_nn_forward_pvqm(self._net, d_features, batch, d_policy, d_value, d_action_values, d_moves_left, stream))
+        elif d_action_values is None:
             check(lib.agx_nn_forward(self._net, d_features, batch, d_policy, d_value, stream))
         else:
             check(lib.agx_nn_forward_pvq(self._net, d_features, batch, d_policy, d_value, d_action_values, stream))
 
     def forward(self, features):
         """Convenience host round trip (tests): features uint32 [B, HW] -> (policy [B, HW], value [B, 3]) and, for a network
-        with the action-values head, additionally q [B, HW, 2] = (win, draw) per cell."""
+        with the action-values head, additionally q [B, HW, 2] = (win, draw) per cell; for one with the moves-left head, moves_left [B, HW]
+        (the softmax of the 'm' output: moves_left_mean) is appended."""
         features = np.ascontiguousarray(features, dtype=np.uint32)
         batch, hw = features.shape
         with_q = bool(self.desc.get("action_values", 0))
@@ -73,18 +83,23 @@ class AGNetwork:
         p = DeviceBuffer(batch * hw * 4)
         v = DeviceBuffer(batch * 3 * 4)
         q = DeviceBuffer(batch * hw * 2 * 4) if with_q else None
+        m = DeviceBuffer(batch * hw * 4) if self._moves_left else None
         try:
             f.upload(features)
-            self.forwardDevice(f.ptr, batch, p.ptr, v.ptr, None, q.ptr if with_q else None)
+            self.forwardDevice(f.ptr, batch, p.ptr, v.ptr, None, q.ptr if with_q else None, m.ptr if m is not None else None)
             check(lib.agx_device_synchronize())
             out = (p.download((batch, hw), np.float32), v.download((batch, 3), np.float32))
             if with_q:
                 out = out + (q.download((batch, hw, 2), np.float32),)
+            if m is not None:
+                out = out + (m.download((batch, hw), np.float32),)
             return out
         finally:
             f.free(); p.free(); v.free()
             if q is not None:
                 q.free()
+            if m is not None:
+                m.free()
 
     def _position_evaluator(self, rules, n):
         """the network's AgxPositionEvaluator for `rules`, with room for n positions.  A larger batch than any before gets a new one (device
@@ -189,6 +204,16 @@ class AGNetwork:
         if self._net:
             lib.agx_net_destroy(self._net)
             self._net = ctypes.c_void_p()
+
+
+def moves_left_mean(m):
+    """the expected number of moves left from the 'm' output [..., HW] (NetworkDataPack::unpackMovesLeft, NetworkDataPack.cpp:224-235):
+    sum_i i * p_i, added in index order in fp32 like the reference's loop"""
+    m = np.asarray(m, dtype=np.float32)
+    out = np.zeros(m.shape[:-1], dtype=np.float32)
+    for i in range(m.shape[-1]):
+        out = out + np.float32(i) * m[..., i]
+    return out
 
 
 def score_dict(score):

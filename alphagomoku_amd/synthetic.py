@@ -43,6 +43,47 @@ def make_weights(desc, seed=1234, residual_gain=1.0, policy_gain=1.0):
     return blob, parts
 
 
+def convnext_desc(rows=15, cols=15, blocks=6, filters=128, moves_left=0):
+    """ConvNextPVQraw (moves_left=0) / ConvNextPVQMraw (moves_left=1), networks.cpp:1078-1219: the 8 low bits of the feature word in, 'pvq' out"""
+    return dict(rows=rows, cols=cols, blocks=blocks, filters=filters, in_channels=8, value_hidden=256, action_values=1,
+                architecture="convnext", moves_left=moves_left)
+
+
+def make_convnext_weights(desc, seed=1234, residual_gain=0.5):
+    """Returns (blob, parts) for a convnext_desc(): the canonical fp32 blob of include/agx.h (batch norms folded: scale 1, shift = small normal
+    bias) and the named arrays in blob order.  He-normal, fixed seed.
+    The residual stream x = (W2 . y + b2 + x) * gate has no ReLU and no normalisation: residual_gain scales W2, and the gates' biases bs2 are
+    2 + a small shift (gates near 0.88: with gates near 0.5 the stream of a deep tower dies away, near 1 it grows by the residual every
+    block).  Measured with tests/nn_convnext_ref.py in float64 on random_features boards, seed 1234, residual_gain 0.5: the largest |x|
+    anywhere in a 10 x 128 stream is 12.8 on 15x15 and 14.9 on 20x20 (6 x 128: 8.5 / 8.7), the largest stored activation of all 21.8; logit
+    spans of a 10 x 128 network are 7 (policy), 10 (q), 18 (m).  fp16 overflows at 65504."""
+    rng = np.random.default_rng(seed)
+    F, HW = desc["filters"], desc["rows"] * desc["cols"]
+
+    def he(shape, fan_in):
+        return (rng.standard_normal(shape) * np.sqrt(2.0 / fan_in)).astype(np.float32)
+
+    def shift(n):
+        return (0.01 * rng.standard_normal(n)).astype(np.float32)
+
+    parts = [("conv_in.w", he((5, 5, 8, F), 25 * 8)), ("conv_in.b", shift(F))]
+    for i in range(desc["blocks"]):
+        parts += [("block%d.wd" % i, he((7, 7, F), 49)), ("block%d.bd" % i, shift(F)),
+                  ("block%d.w1" % i, he((F, F), F)), ("block%d.b1" % i, shift(F)),
+                  ("block%d.w2" % i, he((F, F), F) * np.float32(residual_gain)), ("block%d.b2" % i, shift(F)),
+                  ("block%d.ws1" % i, he((F, F), F)), ("block%d.bs1" % i, shift(F)),
+                  ("block%d.ws2" % i, he((F, F), F)), ("block%d.bs2" % i, np.float32(2.0) + shift(F))]
+    parts += [("policy.w1", he((F, F), F)), ("policy.b1", shift(F)), ("policy.w2", he((F,), F)), ("policy.b2", shift(1))]
+    parts += [("value.w1", he((F, F), F)), ("value.b1", shift(F)), ("value.w2", he((F, 256), F)), ("value.b2", shift(256)),
+              ("value.w3", he((256, 3), 256)), ("value.b3", shift(3))]
+    parts += [("q.w1", he((F, F), F)), ("q.b1", shift(F)), ("q.w2", he((F, 3), F)), ("q.b2", shift(3))]
+    if desc.get("moves_left", 0):
+        parts += [("m.w1", he((F, 32), F)), ("m.b1", shift(32)), ("m.w2", he((32, 128), 32)), ("m.b2", shift(128)),
+                  ("m.w3", he((128, HW), 128)), ("m.b3", shift(HW))]
+    blob = np.concatenate([p[1].reshape(-1) for p in parts]).astype(np.float32)
+    return blob, parts
+
+
 def random_features(batch, rows, cols, seed=0):
     """Random bit-packed feature words with plausible sparsity (stones/legal bits dense, threat bits sparse)."""
     rng = np.random.default_rng(seed)
@@ -75,11 +116,17 @@ def make_openings(n, count, seed0=0, rules=0):
 
 
 def save_weights(path, desc, blob):
-    """the weight container ag::AGNetwork::loadFromFile reads (include/alphagomoku_agx/networks.hpp): "AGXW", AgxNetDesc (7 ints), u64 count, fp32 blob"""
+    """the weight container ag::AGNetwork::loadFromFile reads (include/alphagomoku_agx/networks.hpp): "AGXW", AgxNetDesc (7 ints), u64 count, fp32 blob.
+    A ConvNeXt description (convnext_desc) is written under a second magic, "AGXC", with two more ints behind the seven: AgxNetArchitecture
+    and moves_left."""
     import struct
+    from ._lib import ARCHITECTURES
+    architecture = ARCHITECTURES[desc.get("architecture", "resnet")]
     with open(path, "wb") as f:
-        f.write(b"AGXW")
+        f.write(b"AGXC" if architecture else b"AGXW")
         f.write(struct.pack("<7i", desc["rows"], desc["cols"], desc["blocks"], desc["filters"], desc["in_channels"], desc["value_hidden"],
                             desc.get("action_values", 0)))
+        if architecture:
+            f.write(struct.pack("<2i", architecture, desc.get("moves_left", 0)))
         f.write(struct.pack("<Q", blob.size))
         f.write(np.ascontiguousarray(blob, dtype=np.float32).tobytes())

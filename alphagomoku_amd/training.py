@@ -7,7 +7,9 @@ convolutions forward and backward and the optimiser; the project adds
   TowerModule      ResnetPV / ResnetPVraw / ResnetPVQ as the reference builds them (src/networks/blocks.cpp:32-55,99-127,
                    src/networks/networks.cpp:71-168): no bias and a batch norm WITHOUT a learnable scale but with a shift behind every conv
                    and the hidden dense layer, a bias on the last 1x1 convs and the last dense layer,
-  export_blob / import_blob   the exact bridge between such a module and the BN-folded weight blob of agx.h:70-78,
+  ConvNextModule   ConvNextPVQraw / ConvNextPVQMraw (networks.cpp:1090-1140 / 1154-1219): depthwise 7x7 blocks with squeeze-and-excitation,
+                   1x1 heads over global average pooling, the moves-left output 'm' with the loss weight 0.25 (networks.cpp:1214),
+  export_blob / import_blob   the exact bridge between such a module and the BN-folded weight blob of agx.h,
   Trainer          RAdam (networks.cpp:89: graph.setOptimizer(ml::RAdam())) over the module on batches of a TrainingDataset.
 The architecture, the optimiser and the weight 0.05 of the action-values output (networks.cpp:161) follow reference text; the loss formulas
 are the project's own (MinML's are not in the reference tree).  The module runs in fp32; an fp16 `input` tensor is widened.
@@ -24,6 +26,7 @@ from . import _lib
 from ._lib import lib, check, AgxError, AgxNetDesc
 
 LOSS_WEIGHTS = (1.0, 1.0, 0.05)   # policy, value, action values (networks.cpp:161: graph.addOutput(q, ml::CrossEntropyLoss(), 0.05f))
+MOVES_LEFT_WEIGHT = 0.25          # networks.cpp:1214: graph.addOutput(mlh, ml::CrossEntropyLoss(), 0.25f)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------------
@@ -144,6 +147,18 @@ class _Normed(nn.Module):
         return self.norm(self.layer(x)) + self.shift.view(self._shape)
 
 
+class _NormedGamma(nn.Module):
+    """a conv or dense layer without bias + BatchNormalization(...): normalisation WITH a learnable scale (gamma) and a shift"""
+
+    def __init__(self, layer, channels, spatial):
+        super().__init__()
+        self.layer = layer
+        self.norm = (nn.BatchNorm2d if spatial else nn.BatchNorm1d)(channels, affine=True)
+
+    def forward(self, x):
+        return self.norm(self.layer(x))
+
+
 def _conv(cin, cout, k, bias=False):
     return nn.Conv2d(cin, cout, k, padding=k // 2, bias=bias)
 
@@ -198,9 +213,81 @@ class TowerModule(nn.Module):
         return out
 
 
+class _ConvNextBlock(nn.Module):
+    """networks.cpp:1102-1111: depthwise 7x7 + batch norm, 1x1 + ReLU, 1x1 + residual (no activation), squeeze-and-excitation"""
+
+    def __init__(self, f):
+        super().__init__()
+        self.depthwise = _NormedGamma(nn.Conv2d(f, f, 7, padding=3, groups=f, bias=False), f, True)
+        self.conv1 = _conv(f, f, 1, bias=True)
+        self.conv2 = _conv(f, f, 1, bias=True)
+        self.se1 = nn.Linear(f, f)
+        self.se2 = nn.Linear(f, f)
+
+    def forward(self, x):
+        x = self.conv2(F.relu(self.conv1(self.depthwise(x)))) + x
+        gate = torch.sigmoid(self.se2(F.relu(self.se1(x.mean(dim=(2, 3))))))
+        return x * gate[:, :, None, None]
+
+    def _layers(self):
+        return [("gamma", self.depthwise), ("biased", self.conv1), ("biased", self.conv2), ("biased", self.se1), ("biased", self.se2)]
+
+
+class ConvNextModule(nn.Module):
+    """ConvNextPVQraw (desc moves_left 0) or ConvNextPVQMraw (moves_left 1); desc as synthetic.convnext_desc() makes it.
+    forward(input): load_batch's `input` [n, rows, cols, 32] (planes 0..7 are read: bit c of the feature word = channel c).  Returns the
+    LOGITS: policy [n, rows * cols], value [n, 3], q [n, rows, cols, 3] contiguous, m [n, rows * cols] (None without the head)."""
+
+    def __init__(self, desc):
+        super().__init__()
+        self.desc = dict(desc)
+        f, hw = desc["filters"], desc["rows"] * desc["cols"]
+        if desc.get("architecture") != "convnext" or desc["in_channels"] != 8 or desc["value_hidden"] != 256 or not desc.get("action_values", 0):
+            raise ValueError("ConvNextModule takes a synthetic.convnext_desc()")
+        self.conv_in = _NormedGamma(_conv(8, f, 5), f, True)
+        self.blocks = nn.ModuleList(_ConvNextBlock(f) for _ in range(desc["blocks"]))
+        self.policy1 = _Normed(_conv(f, f, 1), f, True)
+        self.policy2 = _conv(f, 1, 1, bias=True)
+        self.value1 = _conv(f, f, 1, bias=True)
+        self.value2 = _NormedGamma(nn.Linear(f, 256, bias=False), 256, False)
+        self.value3 = nn.Linear(256, 3)
+        self.q1 = _Normed(_conv(f, f, 1), f, True)
+        self.q2 = _conv(f, 3, 1, bias=True)
+        if desc.get("moves_left", 0):
+            self.m1 = _conv(f, 32, 1, bias=True)
+            self.m2 = _NormedGamma(nn.Linear(32, 128, bias=False), 128, False)
+            self.m3 = nn.Linear(128, hw)
+        else:
+            self.m1 = self.m2 = self.m3 = None
+
+    def forward(self, x):
+        n = x.shape[0]
+        x = x[..., :8].to(self.policy2.weight.dtype).permute(0, 3, 1, 2)   # NHWC planes -> NCHW
+        x = F.relu(self.conv_in(x))
+        for block in self.blocks:
+            x = block(x)
+        policy = self.policy2(F.relu(self.policy1(x))).reshape(n, -1)
+        value = self.value3(F.relu(self.value2(F.relu(self.value1(x)).mean(dim=(2, 3)))))
+        q = self.q2(F.relu(self.q1(x))).permute(0, 2, 3, 1).contiguous()
+        m = None
+        if self.m1 is not None:
+            m = self.m3(F.relu(self.m2(F.relu(self.m1(x)).mean(dim=(2, 3)))))
+        return policy, value, q, m
+
+    def _layers(self):
+        out = [("gamma", self.conv_in)]
+        for block in self.blocks:
+            out += block._layers()
+        out += [("normed", self.policy1), ("biased", self.policy2), ("biased", self.value1), ("gamma", self.value2), ("biased", self.value3),
+                ("normed", self.q1), ("biased", self.q2)]
+        if self.m1 is not None:
+            out += [("biased", self.m1), ("gamma", self.m2), ("biased", self.m3)]
+        return out
+
+
 def blob_floats(desc):
     cdesc = AgxNetDesc(desc["rows"], desc["cols"], desc["blocks"], desc["filters"], desc["in_channels"], desc["value_hidden"], desc.get("action_values", 0))
-    return int(lib.agx_net_blob_floats(ctypes.byref(cdesc)))
+    return int(lib.agx_net_blob_floats_ex(ctypes.byref(cdesc), _lib.ARCHITECTURES[desc.get("architecture", "resnet")], desc.get("moves_left", 0)))
 
 
 def _to_blob_order(w):
@@ -213,9 +300,9 @@ def _from_blob_order(w, like):
 
 
 def export_blob(module):
-    """The module as the canonical weight blob of agx.h:70-78 (what AGNetwork.loadWeights takes): every batch norm is folded into its layer with
-    its RUNNING statistics — w * s, shift - mean * s, s = 1 / sqrt(var + eps) — in float64, rounded once to float32, transposed to the blob's
-    order.  Returns a numpy float32 array of agx_net_blob_floats(desc) values (the call waits for the copy from the device)."""
+    """The module as the canonical weight blob of agx.h (what AGNetwork.loadWeights takes): every batch norm is folded into its layer with
+    its RUNNING statistics — w * s, shift - mean * s, s = 1 / sqrt(var + eps), with a learnable scale ('gamma' layers) s = gamma / sqrt(var +
+    eps) and shift = beta — in float64, rounded once to float32, transposed to the blob's order.  Returns a numpy float32 array of agx_net_blob_floats(desc) values (the call waits for the copy from the device)."""
     parts = []
     with torch.no_grad():
         for kind, m in module._layers():
@@ -223,6 +310,10 @@ def export_blob(module):
                 w = m.layer.weight.double()
                 s = 1.0 / torch.sqrt(m.norm.running_var.double() + m.norm.eps)
                 parts += [_to_blob_order(w * s.view([-1] + [1] * (w.dim() - 1))), m.shift.double() - m.norm.running_mean.double() * s]
+            elif kind == "gamma":
+                w = m.layer.weight.double()
+                s = m.norm.weight.double() / torch.sqrt(m.norm.running_var.double() + m.norm.eps)
+                parts += [_to_blob_order(w * s.view([-1] + [1] * (w.dim() - 1))), m.norm.bias.double() - m.norm.running_mean.double() * s]
             else:
                 parts += [_to_blob_order(m.weight.double()), m.bias.double()]
         blob = torch.cat([p.reshape(-1) for p in parts]).to(torch.float32).cpu().numpy()
@@ -250,11 +341,17 @@ def import_blob(module, blob):
 
     with torch.no_grad():
         for kind, m in module._layers():
-            layer = m.layer if kind == "normed" else m
+            layer = m if kind == "biased" else m.layer
             w = _from_blob_order(take(_to_blob_order(layer.weight).shape), layer.weight)
             if kind == "normed":
                 layer.weight.copy_(w * math.sqrt(1.0 + m.norm.eps))
                 m.shift.copy_(take(m.shift.shape))
+                m.norm.running_mean.zero_()
+                m.norm.running_var.fill_(1.0)
+            elif kind == "gamma":   # (the learnable scale becomes 1)
+                layer.weight.copy_(w * math.sqrt(1.0 + m.norm.eps))
+                m.norm.weight.fill_(1.0)
+                m.norm.bias.copy_(take(m.norm.bias.shape))
                 m.norm.running_mean.zero_()
                 m.norm.running_var.fill_(1.0)
             else:
@@ -302,10 +399,20 @@ class Trainer:
 
     def step(self, samples):
         """one training step on samples [n, 4] (fragment, game, sample, augmentation): load_batch into reused buffers -> module -> loss ->
-        backward -> optimiser.  Returns the three loss components (sums / n) as a device tensor; on a ROCm device nothing waits for the host."""
+        backward -> optimiser.  Returns the three loss components (sums / n) as a device tensor — four for a module with the moves-left output
+        (ConvNextModule with moves_left: the mean cross-entropy of 'm' last) —; on a ROCm device nothing waits for the host."""
         self.module.train()
-        batch, (policy, value, q) = self._forward(samples, True)
+        batch, outputs = self._forward(samples, True)
+        policy, value, q = outputs[:3]
         loss, components = (head_loss if self._on_device() else head_loss_reference)(policy, value, q, batch, self.weights)
+        if len(outputs) > 3 and outputs[3] is not None:
+            # the moves-left output 'm' (ConvNextPVQMraw): cross-entropy against the class clamp(int(moves left), 0, HW - 1), weight 0.25, with
+            # torch ops; its mean per sample is appended to the components
+            m = outputs[3]
+            target = batch["moves_left_target"].reshape(-1).to(torch.int64).clamp(0, m.shape[1] - 1)
+            m_ce = F.cross_entropy(m, target)
+            loss = loss + MOVES_LEFT_WEIGHT * m_ce
+            components = torch.cat([components, m_ce.detach().to(components.dtype).reshape(1)])
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.optimizer.step()
@@ -329,7 +436,8 @@ class Trainer:
             with torch.no_grad():
                 for first in range(0, len(samples), chunk):
                     part = samples[first:first + chunk]
-                    batch, (policy, value, q) = self._forward(part, False)
+                    batch, outputs = self._forward(part, False)
+                    policy, value, q = outputs[:3]
                     _, components = (head_loss if self._on_device() else head_loss_reference)(policy, value, q, batch, self.weights)
                     sums += components.double().cpu() * len(part)
                     if q is not None:

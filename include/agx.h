@@ -101,6 +101,41 @@ int agx_nn_forward_indirect(AgxNet* net, const uint32_t* d_features, const int* 
 int agx_nn_forward_indirect_pvq(AgxNet* net, const uint32_t* d_features, const int* d_slot_list, const int* d_count, int max_batch,
 		float* d_policy, float* d_value, float* d_action_values, void* stream);
 
+/* ConvNeXt networks: ConvNextPVQraw (networks.cpp:1078-1140) and ConvNextPVQMraw (:1142-1219, with the moves-left output 'm').  AgxNetDesc
+ * keeps its seven ints; the architecture and the moves-left head are named next to it.  For AGX_ARCH_CONVNEXT the description must have
+ * in_channels 8 (the 8 low bits of the feature word), action_values 1, value_hidden 256 and filters 64 or 128, on boards 5..20 x 5..20.
+ * The network after the batch norms are folded (F = filters, HW = rows * cols):
+ *   conv_in  5x5, 8 -> F, + b, relu
+ *   blocks x y = depthwise 7x7 (x) + bd ; y = relu(W1 . y + b1) ; x = W2 . y + b2 + x (no activation) ;
+ *            x = x * sigmoid(Ws2 . relu(Ws1 . mean_hw(x) + bs1) + bs2) per channel
+ *   policy   relu(Wp1 . x + bp1) ; Wp2 . + bp2 (F -> 1) ; softmax over the board
+ *   value    relu(Wv1 . x + bv1) ; mean_hw ; relu(Wv2 . + bv2) (F -> 256) ; Wv3 . + bv3 (256 -> 3) ; softmax
+ *   q        relu(Wq1 . x + bq1) ; Wq2 . + bq2 (F -> 3) ; softmax per cell
+ *   m        relu(Wm1 . x + bm1) (F -> 32) ; mean_hw ; relu(Wm2 . + bm2) (32 -> 128) ; Wm3 . + bm3 (128 -> HW) ; softmax
+ * The canonical fp32 blob holds, in this order:
+ *   conv_in  W[5][5][8][F] b[F]
+ *   blocks x { Wd[7][7][F] bd[F]  W1[F][F] b1[F]  W2[F][F] b2[F]  Ws1[F][F] bs1[F]  Ws2[F][F] bs2[F] }
+ *   policy   Wp1[F][F] bp1[F]  Wp2[F] bp2[1]
+ *   value    Wv1[F][F] bv1[F]  Wv2[F][256] bv2[256]  Wv3[256][3] bv3[3]
+ *   q        Wq1[F][F] bq1[F]  Wq2[F][3] bq2[3]
+ *   m (only with moves_left)  Wm1[F][32] bm1[32]  Wm2[32][128] bm2[128]  Wm3[128][HW] bm3[HW]
+ * 1x1 convolutions and dense layers are [in][out]; the depthwise convolution is a cross-correlation with "same" zero padding. */
+enum AgxNetArchitecture { AGX_ARCH_RESNET = 0, AGX_ARCH_CONVNEXT = 1 };
+size_t agx_net_blob_floats_ex(const AgxNetDesc* desc, int architecture, int moves_left); /* 0 for a combination that does not exist */
+/* architecture AGX_ARCH_RESNET with moves_left 0 is agx_net_create.  What the kernels do not cover is AGX_ERR_UNSUPPORTED with a message.
+ * Every entry point that takes an AgxNet takes the result: agx_net_load_weights (the blob above), agx_nn_forward[_indirect][_pvq],
+ * agx_net_set_launch_width, agx_net_description, agx_net_destroy, and with them the pool, the position evaluators and searchers and
+ * agx_net_score_dataset*. */
+int agx_net_create_ex(const AgxNetDesc* desc, int architecture, int moves_left, AgxNet** out);
+int agx_net_architecture(const AgxNet* net, int* architecture, int* moves_left);
+/* agx_nn_forward[_indirect]_pvq with the moves-left output: d_moves_left float[batch or slots][rows*cols], the softmax of the 'm' head (index i
+ * = i moves left, NetworkDataPack.cpp:224-235).  d_action_values and d_moves_left may each be NULL (head skipped); a d_moves_left on a
+ * network without the head is AGX_ERR_INVALID. */
+int agx_nn_forward_pvqm(AgxNet* net, const uint32_t* d_features, int batch, float* d_policy, float* d_value, float* d_action_values,
+		float* d_moves_left, void* stream);
+int agx_nn_forward_indirect_pvqm(AgxNet* net, const uint32_t* d_features, const int* d_slot_list, const int* d_count, int max_batch,
+		float* d_policy, float* d_value, float* d_action_values, float* d_moves_left, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Device-resident self-play engine: a pool of independent games, each with its own search tree, solver transposition
  * table and task buffer in HBM.  Replaces, for one GeneratorThread (src/selfplay/GeneratorManager.cpp:124-141), the

@@ -84,20 +84,25 @@ namespace agx
 	{
 			AgxNet *m_net = nullptr;
 			AgxNetDesc m_desc { };
+			int m_architecture = AGX_ARCH_RESNET, m_moves_left = 0;
 		public:
-			/* architecture "ResnetPV" (networks.cpp:71-93) or "ResnetPVQ" (:143-168, adds the action-values head) */
+			/* architecture "ResnetPV" (networks.cpp:71-93), "ResnetPVQ" (:143-168, adds the action-values head), "ConvNextPVQraw" (:1078-1140) or
+			 * "ConvNextPVQMraw" (:1142-1219, adds the moves-left output) */
 			AGNetwork(const GameConfig &cfg, int blocks, int filters, const std::string &architecture = "ResnetPV")
 			{
-				if (architecture != "ResnetPV" && architecture != "ResnetPVQ")
+				const bool convnext = (architecture == "ConvNextPVQraw" || architecture == "ConvNextPVQMraw");
+				if (architecture != "ResnetPV" && architecture != "ResnetPVQ" && !convnext)
 					throw std::logic_error("AGNetwork: unknown architecture '" + architecture + "'");
-				m_desc.action_values = (architecture == "ResnetPVQ") ? 1 : 0;
+				m_architecture = convnext ? AGX_ARCH_CONVNEXT : AGX_ARCH_RESNET;
+				m_moves_left = (architecture == "ConvNextPVQMraw") ? 1 : 0;
+				m_desc.action_values = (architecture == "ResnetPVQ" || convnext) ? 1 : 0;
 				m_desc.rows = cfg.rows;
 				m_desc.cols = cfg.cols;
 				m_desc.blocks = blocks;
 				m_desc.filters = filters;
-				m_desc.in_channels = 32;
-				m_desc.value_hidden = (2 * filters < 256) ? 2 * filters : 256;
-				check(agx_net_create(&m_desc, &m_net));
+				m_desc.in_channels = convnext ? 8 : 32;
+				m_desc.value_hidden = convnext ? 256 : ((2 * filters < 256) ? 2 * filters : 256);
+				check(agx_net_create_ex(&m_desc, m_architecture, m_moves_left, &m_net));
 			}
 			AGNetwork(const AGNetwork&) = delete;
 			AGNetwork& operator=(const AGNetwork&) = delete;
@@ -107,7 +112,7 @@ namespace agx
 			}
 			size_t numberOfWeights() const
 			{
-				return agx_net_blob_floats(&m_desc);
+				return agx_net_blob_floats_ex(&m_desc, m_architecture, m_moves_left);
 			}
 			void loadWeights(const std::vector<float> &blob)
 			{
@@ -123,9 +128,14 @@ namespace agx
 			{
 				check(agx_nn_forward_pvq(m_net, d_features, batch, d_policy, d_value, d_action_values, stream));
 			}
+			/* 'pvqm' networks: additionally moves left float[batch][rows*cols], the softmax of the 'm' output */
+			void forward(const uint32_t *d_features, int batch, float *d_policy, float *d_value, float *d_action_values, float *d_moves_left, void *stream)
+			{
+				check(agx_nn_forward_pvqm(m_net, d_features, batch, d_policy, d_value, d_action_values, d_moves_left, stream));
+			}
 			std::string getOutputConfig() const
 			{ // AGNetwork::getOutputConfig
-				return m_desc.action_values ? "pvq" : "pv";
+				return m_moves_left ? "pvqm" : (m_desc.action_values ? "pvq" : "pv");
 			}
 			AgxNet* handle() const noexcept
 			{

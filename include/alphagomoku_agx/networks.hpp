@@ -49,12 +49,14 @@ namespace ag
 	{
 			GameConfig game_config;
 			AgxNetDesc desc { };
+			int architecture = AGX_ARCH_RESNET; // AgxNetArchitecture
+			int moves_left = 0;                 // 1: the network has the moves-left output 'm' (ConvNextPVQMraw)
 			AgxNet *net = nullptr;
 			int batch_size = 0;
 			// host staging of the reference's NetworkDataPack + the device tensors behind it
 			std::vector<uint32_t> input;
-			std::vector<float> policy, value, action_values;
-			void *d_input = nullptr, *d_policy = nullptr, *d_value = nullptr, *d_action_values = nullptr;
+			std::vector<float> policy, value, action_values, moves_left_out;
+			void *d_input = nullptr, *d_policy = nullptr, *d_value = nullptr, *d_action_values = nullptr, *d_moves_left = nullptr;
 			int launched = 0;
 			// the indices packed as boards: encoded on the device by forward (agx_position_evaluator_encode), in front of the tower
 			std::vector<uint8_t> boards, signs, packed_as_board;
@@ -64,7 +66,10 @@ namespace ag
 			int encoded = 0;
 		public:
 			AGNetwork() noexcept = default;
-			/* architecture "ResnetPV" / "ResnetPVraw" (outputs "pv"; the raw network reads the 8 low bits of a feature word) or "ResnetPVQ" ("pvq") */
+			/* architecture "ResnetPV" / "ResnetPVraw" (outputs "pv"; the raw network reads the 8 low bits of a feature word), "ResnetPVQ" ("pvq"),
+			 * "ConvNextPVQraw" ("pvq", raw input) or "ConvNextPVQMraw" ("pvqm": unpackOutput's movesLeft is the mean of the 'm' output).  The weight
+			 * container of saveToFile / loadFromFile is "AGXW" + AgxNetDesc + u64 count + fp32 blob for the residual networks and "AGXC" + AgxNetDesc
+			 * + two ints (AgxNetArchitecture, moves_left) + u64 count + fp32 blob for the ConvNeXt ones. */
 			AGNetwork(const GameConfig &gameOptions, const std::string &architecture, int blocks, int filters);
 			AGNetwork(const AGNetwork &other) = delete;
 			AGNetwork& operator=(const AGNetwork &other) = delete;
