@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libagx.so")
 
 INCLUDE = os.path.join(HERE, "..", "include")
-SOURCES = ["agx_api.hip", "nn_forward.hip", "nn_any_board.hip", "nn_convnext.hip", "engine.hip", "training_batch.hip", "net_score.hip", "head_loss.hip", "position_eval.hip", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
+SOURCES = ["agx_api.hip", "nn_forward.hip", "nn_any_board.hip", "nn_convnext.hip", "engine.hip", "training_batch.hip", "net_score.hip", "head_loss.hip", "position_eval.hip", "nn_net.cpp", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
 DRIVER = os.path.join(HERE, "agx_selfplay")
 AG_LIB = os.path.join(HERE, "libagx_ag.so")               # the reference-named C++ classes (include/alphagomoku_agx/) over the C ABI
 BOUNDARY_TEST = os.path.join(HERE, "agx_boundary_test")  # tests/cpp/boundary_main.cpp: the reference's call chain on those classes
@@ -29,6 +29,15 @@ TARGETS_TEST = os.path.join(HERE, "agx_training_targets_test")  # tests/cpp/trai
 TARGETS_SRC = os.path.join(HERE, "..", "tests", "cpp", "training_targets_main.cpp")
 CONVNEXT_TEST = os.path.join(HERE, "agx_convnext_test")  # tests/cpp/convnext_main.cpp: the ConvNeXt architectures through ag::AGNetwork, container included
 CONVNEXT_SRC = os.path.join(HERE, "..", "tests", "cpp", "convnext_main.cpp")
+# the host test programs: (target, source, libraries, depends on libagx_ag.so); one without the reference-named classes is relinked with libagx.so
+HOST_TESTS = [
+    (BOUNDARY_TEST, BOUNDARY_SRC, ["-lagx_ag", "-lagx"], True),
+    (TRAINING_TEST, TRAINING_SRC, ["-lagx_ag", "-lagx"], True),
+    (SCORE_TEST, SCORE_SRC, ["-lagx_ag", "-lagx"], True),
+    (POSITION_TEST, POSITION_SRC, ["-lagx_ag", "-lagx"], True),
+    (TARGETS_TEST, TARGETS_SRC, ["-lagx"], False),
+    (CONVNEXT_TEST, CONVNEXT_SRC, ["-lagx_ag", "-lagx"], True),
+]
 HOST_ONLY = ("ag_classes.cpp", "selfplay_main.cpp")  # plain g++ sources in csrc/ (not part of libagx.so)
 
 
@@ -88,18 +97,9 @@ def _stale_host_targets():
         out.append(DRIVER)
     if _mtime(AG_LIB) < max(_mtime(os.path.join(CSRC, "ag_classes.cpp")), headers):
         out.append(AG_LIB)
-    if _mtime(BOUNDARY_TEST) < max(_mtime(BOUNDARY_SRC), headers, _mtime(AG_LIB)) or AG_LIB in out:
-        out.append(BOUNDARY_TEST)
-    if _mtime(TRAINING_TEST) < max(_mtime(TRAINING_SRC), headers, _mtime(AG_LIB)) or AG_LIB in out:
-        out.append(TRAINING_TEST)
-    if _mtime(SCORE_TEST) < max(_mtime(SCORE_SRC), headers, _mtime(AG_LIB)) or AG_LIB in out:
-        out.append(SCORE_TEST)
-    if _mtime(POSITION_TEST) < max(_mtime(POSITION_SRC), headers, _mtime(AG_LIB)) or AG_LIB in out:
-        out.append(POSITION_TEST)
-    if _mtime(TARGETS_TEST) < max(_mtime(TARGETS_SRC), headers, _mtime(LIB)):
-        out.append(TARGETS_TEST)
-    if _mtime(CONVNEXT_TEST) < max(_mtime(CONVNEXT_SRC), headers, _mtime(AG_LIB)) or AG_LIB in out:
-        out.append(CONVNEXT_TEST)
+    for target, src, _, on_ag_lib in HOST_TESTS:
+        if _mtime(target) < max(_mtime(src), headers, _mtime(AG_LIB if on_ag_lib else LIB)) or (on_ag_lib and AG_LIB in out):
+            out.append(target)
     return out
 
 
@@ -164,24 +164,15 @@ def build(force=False, verbose=True):
         relink = True
     if relink:
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + [BUILD_ID_OBJ, "-lz"])
-    stale = [DRIVER, AG_LIB, BOUNDARY_TEST, TRAINING_TEST, SCORE_TEST, POSITION_TEST, TARGETS_TEST, CONVNEXT_TEST] if force else _stale_host_targets()
+    stale = ([DRIVER, AG_LIB] + [t[0] for t in HOST_TESTS]) if force else _stale_host_targets()
     if DRIVER in stale:  # native C++ host driver over the C ABI (include/agx.hpp)
         run([cxx, "-std=c++17", "-O2", "-o", DRIVER, os.path.join(CSRC, "selfplay_main.cpp"), "-L" + HERE, "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
     if AG_LIB in stale:  # the C++ boundary: plain host code (g++), no HIP types — a maintainer of the reference links it like any other library
         run([cxx, "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-o", AG_LIB, os.path.join(CSRC, "ag_classes.cpp"), "-L" + HERE, "-lagx",
              "-Wl,-rpath," + HERE, "-lpthread"])
-    if BOUNDARY_TEST in stale:
-        run([cxx, "-std=c++17", "-O2", "-Wall", "-o", BOUNDARY_TEST, BOUNDARY_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
-    if TRAINING_TEST in stale:
-        run([cxx, "-std=c++17", "-O2", "-Wall", "-o", TRAINING_TEST, TRAINING_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
-    if SCORE_TEST in stale:
-        run([cxx, "-std=c++17", "-O2", "-Wall", "-o", SCORE_TEST, SCORE_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
-    if POSITION_TEST in stale:
-        run([cxx, "-std=c++17", "-O2", "-Wall", "-o", POSITION_TEST, POSITION_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
-    if TARGETS_TEST in stale:
-        run([cxx, "-std=c++17", "-O2", "-Wall", "-o", TARGETS_TEST, TARGETS_SRC, "-L" + HERE, "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
-    if CONVNEXT_TEST in stale:
-        run([cxx, "-std=c++17", "-O2", "-Wall", "-o", CONVNEXT_TEST, CONVNEXT_SRC, "-L" + HERE, "-lagx_ag", "-lagx", "-Wl,-rpath," + HERE, "-lpthread"])
+    for target, src, libraries, _ in HOST_TESTS:
+        if target in stale:
+            run([cxx, "-std=c++17", "-O2", "-Wall", "-o", target, src, "-L" + HERE] + libraries + ["-Wl,-rpath," + HERE, "-lpthread"])
     return LIB
 
 

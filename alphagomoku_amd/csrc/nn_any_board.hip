@@ -17,8 +17,8 @@
  *     the loop divides: the only run-time divisions by S (cell of a position: the epilogue's mask, the input conv's plane index) are a
  *     multiply and a shift (Shape::magic), a few times per lane and board.
  *   - Residual values through a per-workgroup global scratch, written and read by the same lane (conv3x3_inplace of nn_forward.hip).
- *   - The value head's dense layers are not launched here: launch_forward() (nn_forward.hip) runs value_head_kernel behind the tower for all
- *     boards of the launch, K = 4 * rows * cols padded to 32 (AgxNet::kpad(), handed to launch() for the row stride of NetParams::vhead_x).
+ *   - The value head's dense layers are not launched here: agx_res::launch() (nn_forward.hip) runs value_head_kernel behind the tower for all
+ *     boards of the launch, K = 4 * rows * cols padded to 32 (agx_res::Net::kpad(), handed to launch() for the row stride of NetParams::vhead_x).
  *   - The types, the launch record and the helpers shared with nn_forward.hip are in nn_device.hpp.
  *
  * Slower per FLOP than the two specialised kernels (DESIGN.md 3.1 has the measured ratios): no row- or column-stationary reuse of
@@ -38,7 +38,7 @@ namespace
 			int NT;       // 16-position tiles of the output: ceil(rows * S / 16)
 			int ntw;      // tiles per position group: ceil(NT / PG)
 			int HW;
-			int kpad;     // value-head dense input length (the host's AgxNet::kpad()): 4 HW rounded up to 32
+			int kpad;     // value-head dense input length (the host's agx_res::Net::kpad()): 4 HW rounded up to 32
 			int plane16;  // 16-byte units of the activation plane: (1 + S + NT * 16 + S + 2) positions
 			int S5;       // row stride of the padded input plane: S + 4
 			int npos5;    // its positions: (rows + 4) * S5 + 4

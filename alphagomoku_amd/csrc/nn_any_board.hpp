@@ -1,5 +1,5 @@
 /*
- * nn_any_board.hpp — the run-time-shaped tower kernel (nn_any_board.hip) as nn_forward.hip's host code sees it.
+ * nn_any_board.hpp — the run-time-shaped tower kernel (nn_any_board.hip) as the residual towers' host code (agx_res in nn_forward.hip) sees it.
  */
 #ifndef AGX_NN_ANY_BOARD_HPP_
 #define AGX_NN_ANY_BOARD_HPP_
@@ -17,9 +17,9 @@ namespace agx_any
 
 	/* bytes of residual scratch one workgroup of the persistent grid needs (the same for every board shape) */
 	size_t skip_bytes_per_workgroup(int filters);
-	/* The tower kernel (`grid` workgroups) for a launch record filled by launch_forward() on `stream`; an AGX_* status.  p.skip is
+	/* The tower kernel (`grid` workgroups) for a launch record filled by agx_res::launch() on `stream`; an AGX_* status.  p.skip is
 	 * grid x skip_bytes_per_workgroup(filters), p.vhead_x [batch][kpad] halves with the padding zero; weight fragments are in the tap-major order
-	 * of pack_conv(): [tap][k-step][16-channel tile][lane][8], the raw input conv in pack_conv5x5_raw()'s. */
+	 * of pack_conv() (nn_pack.hpp): [tap][k-step][16-channel tile][lane][8], the raw input conv in pack_conv5x5_raw()'s. */
 	int launch(const agx_nn::NetParams &p, int rows, int cols, int filters, bool raw, int grid, int kpad, const uint32_t *d_features, float *d_policy, hipStream_t stream);
 }
 

@@ -27,9 +27,11 @@
  *     activation is rounded to fp16 like a stored plane before what follows it.  Every reduction over lanes and waves runs in an order
  *     fixed by the board shape alone: results do not depend on the grid, the batch or the slot list.
  *
- * The host side (packing of the canonical blob, the launch) is at the end; nn_forward.hip dispatches here (nn_convnext.hpp).
+ * The host side (packing of the canonical blob with the packers of nn_pack.hpp, the launch) is at the end; nn_net.cpp dispatches here
+ * (nn_convnext.hpp).
  */
 #include "nn_device.hpp"
+#include "nn_pack.hpp"
 #include "nn_convnext.hpp"
 
 #include <vector>
@@ -719,38 +721,6 @@ namespace
 #undef AGX_CNX_LANE
 	}
 
-	/* canonical [cin][cout] fp32 -> MFMA A fragments [cin / 32][cout / 16][lane][8]: lane l holds out-channel tile * 16 + (l & 15),
-	 * in-channels kc * 32 + 8 * (l >> 4) + j (pack_conv of nn_forward.hip with one tap) */
-	void pack_1x1(const float *w, int cin, int cout, std::vector<half_t> &dst)
-	{
-		const int kcs = cin / 32, mtiles = cout / 16;
-		const size_t base = dst.size();
-		dst.resize(base + static_cast<size_t>(cin) * cout);
-		for (int kc = 0; kc < kcs; kc++)
-			for (int mt = 0; mt < mtiles; mt++)
-				for (int lane = 0; lane < 64; lane++)
-					for (int j = 0; j < 8; j++)
-						dst[base + ((static_cast<size_t>(kc) * mtiles + mt) * 64 + lane) * 8 + j] = static_cast<half_t>(
-								w[static_cast<size_t>(kc * 32 + 8 * (lane >> 4) + j) * cout + mt * 16 + (lane & 15)]);
-	}
-	/* the 5x5 conv of the 8-channel input: k-step t = 2 * dy + g holds the four horizontal taps dx = 4 g + (lane >> 4) x 8 channels (taps
-	 * beyond dx = 4 are zero): [10][cout / 16][lane][8] */
-	void pack_conv5x5_raw(const float *w, int cout, std::vector<half_t> &dst)
-	{
-		const int mtiles = cout / 16;
-		dst.assign(static_cast<size_t>(10) * mtiles * 512, static_cast<half_t>(0.0f));
-		for (int t = 0; t < 10; t++)
-			for (int mt = 0; mt < mtiles; mt++)
-				for (int lane = 0; lane < 64; lane++)
-				{
-					const int dy = t / 2, dx = 4 * (t % 2) + (lane >> 4);
-					if (dx >= 5)
-						continue;
-					for (int j = 0; j < 8; j++)
-						dst[((static_cast<size_t>(t) * mtiles + mt) * 64 + lane) * 8 + j] = static_cast<half_t>(w[(static_cast<size_t>(dy * 5 + dx) * 8 + j) * cout + mt * 16 + (lane & 15)]);
-				}
-	}
-
 	template<int F>
 	void pack_blob(const AgxNetDesc &d, int moves_left, const float *ptr, std::vector<half_t> &h, std::vector<float> &f)
 	{
@@ -769,8 +739,8 @@ namespace
 			ptr += n;
 		};
 		auto conv1x1 = [&](int cout)
-		{
-			pack_1x1(ptr, F, cout, h);
+		{ // [cin / 32][cout / 16][lane][8]
+			pack_conv(ptr, 1, F, cout, h);
 			ptr += F * cout;
 		};
 		auto rows_padded = [&](int rows, int n, int padded)
@@ -909,7 +879,6 @@ namespace agx_cnx
 			float *d_action_values, float *d_moves_left, hipStream_t stream)
 	{
 		AGX_REQUIRE(net != nullptr && grid > 0, AGX_ERR_STATE, "agx_nn_forward: ConvNeXt weights not loaded");
-		AGX_REQUIRE(d_moves_left == nullptr || net->moves_left, AGX_ERR_INVALID, "agx_nn_forward: the network has no moves-left head");
 		const AgxNetDesc &d = net->desc;
 		Params p;
 		p.h = static_cast<const half_t*>(net->d_h);

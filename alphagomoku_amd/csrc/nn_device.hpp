@@ -1,6 +1,6 @@
 /*
  * nn_device.hpp — the device code that the two network kernel files share: nn_forward.hip (the 15x15 and 20x20 towers, the value head's
- * dense layers, the host side) and nn_any_board.hip (the run-time-shaped tower).  The vector types, the launch record NetParams, the small
+ * dense layers, the residual towers' host side) and nn_any_board.hip (the run-time-shaped tower).  The vector types, the launch record NetParams, the small
  * helpers of the layers (LDS barrier, fp16 + fp32 add, carried bias values, workgroup reductions) and the pieces both towers run word for
  * word: the unpacking of a feature byte, the staging of the heads' 1x1 weights, the action-values softmax.  The functions are in the unnamed
  * namespace and forced inline: each .hip file gets its own copy, exactly as if the text stood there.  The types are in agx_nn: NetParams
@@ -20,7 +20,7 @@ namespace agx_nn
 	typedef _Float16 half2 __attribute__((ext_vector_type(2)));
 	typedef float floatx4 __attribute__((ext_vector_type(4)));
 
-	/* One launch, filled by launch_forward() (nn_forward.hip) and passed by value to the tower kernel that runs — a fixed-shape one or the
+	/* One launch, filled by agx_res::launch() (nn_forward.hip) and passed by value to the tower kernel that runs — a fixed-shape one or the
 	 * run-time-shaped one.  The value head's dense fields (wv2, bv2, wv3, bv3) are read by the host only, for value_head_kernel's launch: they
 	 * stay in the record so that the towers' kernel-argument offsets do not move. */
 	struct NetParams

@@ -30,17 +30,21 @@
  *     accumulators until every wave has passed a barrier) and parks the residual input in a per-workgroup global scratch.
  *   - Template flags keep the variants apart: <F, ROWS, COLS, INPLACE, QHEAD>; the pv kernels carry no q-head code.
  *   - These kernels are the 15x15 and 20x20 boards' own.  Every other shape (5..20 rows and columns) runs the run-time-shaped kernel of
- *     nn_any_board.hip (AgxNet::any_board), and so do these two with AGX_NN_ANY_BOARD=1 in the environment.
+ *     nn_any_board.hip (agx_res::Net::any_board), and so do these two with AGX_NN_ANY_BOARD=1 in the environment.
  *   - What the two files have in common is in nn_device.hpp: the vector types, the launch record NetParams, the layers' small helpers, the
  *     unpacking of a feature byte, the staging of the heads' weights, the heads' fixed-order sums and softmax.  The k-loops and the layer
  *     epilogues are each file's own.
  *   - The value head's dense layers are one kernel (value_head_kernel, the input length an argument) launched from one place:
- *     launch_forward(), behind whichever tower ran.
+ *     agx_res::launch(), behind whichever tower ran.
+ *   - The host side at the end is namespace agx_res, the residual towers as nn_net.cpp sees them (nn_resnet.hpp): pack and upload a blob into
+ *     a fresh Net, destroy one, launch one.  AgxNet and the entry points of the C ABI are in nn_net.cpp; the packers shared with
+ *     nn_convnext.hip are in nn_pack.hpp.
  */
 #include "agx_internal.hpp"
 #include "nn_device.hpp"
+#include "nn_pack.hpp"
 #include "nn_any_board.hpp"
-#include "nn_convnext.hpp"
+#include "nn_resnet.hpp"
 
 #include <vector>
 #include <mutex>
@@ -1700,7 +1704,7 @@ namespace
 	 * Value head behind the tower, for every board of a launch: hidden = ReLU(W2^T x + b2) (4 HW -> D), out = softmax(W3^T hidden + b3)
 	 * (createValueHead, blocks.cpp:108-118).  One workgroup = 16 boards (one MFMA position tile) x all D hidden units: wave w owns the
 	 * 16-unit tiles w * D/64 .. and walks K in 32-input steps (weights pre-packed in A-fragment order, the boards' inputs are rows of
-	 * kpad halves: AgxNet::kpad()).  3.1 GFLOP for a whole self-play batch — microseconds.  The one kernel behind every tower, the
+	 * kpad halves: agx_res::Net::kpad()).  3.1 GFLOP for a whole self-play batch — microseconds.  The one kernel behind every tower, the
 	 * run-time-shaped one included: the input length is an argument.
 	 */
 	template<int D>
@@ -1766,35 +1770,9 @@ namespace
 	}
 
 	/*
-	 * Host side: pack canonical [kh][kw][cin][cout] fp32 weights into MFMA A-fragment order
-	 * [tap][kc][mtile][lane][8]: lane l holds out-channel mtile*16 + (l & 15), in-channels kc*32 + 8*(l >> 4) + j.
-	 */
-	void pack_conv(const float *w, int taps, int cin, int cout, std::vector<half_t> &dst)
-	{
-		const int kcs = cin / 32;
-		const int mtiles = cout / 16;
-		const size_t base = dst.size();
-		dst.resize(base + static_cast<size_t>(taps) * kcs * mtiles * 512);
-		half_t *out = dst.data() + base;
-		for (int t = 0; t < taps; t++)
-			for (int kc = 0; kc < kcs; kc++)
-				for (int mt = 0; mt < mtiles; mt++)
-					for (int lane = 0; lane < 64; lane++)
-						for (int j = 0; j < 8; j++)
-						{
-							const int oc = mt * 16 + (lane & 15);
-							const int ic = kc * 32 + 8 * (lane >> 4) + j;
-							const float v = w[(static_cast<size_t>(t) * cin + ic) * cout + oc];
-							out[(((static_cast<size_t>(t) * kcs + kc) * mtiles + mt) * 64 + lane) * 8 + j] = static_cast<half_t>(v);
-						}
-	}
-}
-
-namespace
-{
-	/*
-	 * The same fragments in the order the row-stationary k-loop consumes them (conv3x3_mac_rows): [kc][dx][channel group][dy][tile][lane][8],
-	 * so the 3 * MT fragments a wave needs for one stage are consecutive.  3x3 kernels only; MT = cout / (16 * groups) tiles per channel group.
+	 * Host side.  The tap-major fragment order [tap][kc][mtile][lane][8] is pack_conv (nn_pack.hpp).  Here: the same fragments in the order the
+	 * row-stationary k-loop consumes them (conv3x3_mac_rows): [kc][dx][channel group][dy][tile][lane][8], so the 3 * MT fragments a wave needs
+	 * for one stage are consecutive.  3x3 kernels only; MT = cout / (16 * groups) tiles per channel group.
 	 */
 	void pack_conv_rows(const float *w, int cin, int cout, std::vector<half_t> &dst, bool by_row_shift = false, int groups = 4)
 	{ // by_row_shift: the column-tile loop (conv3x3_mac_cols) — stage = (chunk, dy), inside it dx: the same order with the roles exchanged
@@ -1818,97 +1796,7 @@ namespace
 									out[(frag * 64 + lane) * 8 + j] = static_cast<half_t>(w[(static_cast<size_t>(t) * cin + ic) * cout + oc]);
 								}
 	}
-}
 
-namespace
-{
-	/* conv5x5 of an 8-channel input (ResnetPVraw) for conv5x5_input<.., RAW>: k-step t = 2 * dy + g holds the four horizontal taps
-	 * dx = 4 g + (lane >> 4) x 8 channels (taps beyond dx = 4 are zero): [10][cout / 16][lane][8] */
-	void pack_conv5x5_raw(const float *w, int cout, std::vector<half_t> &dst)
-	{
-		const int mtiles = cout / 16;
-		dst.assign(static_cast<size_t>(10) * mtiles * 512, static_cast<half_t>(0.0f));
-		for (int t = 0; t < 10; t++)
-			for (int mt = 0; mt < mtiles; mt++)
-				for (int lane = 0; lane < 64; lane++)
-				{
-					const int dy = t / 2, dx = 4 * (t % 2) + (lane >> 4);
-					if (dx >= 5)
-						continue;
-					for (int j = 0; j < 8; j++)
-						dst[((static_cast<size_t>(t) * mtiles + mt) * 64 + lane) * 8 + j] = static_cast<half_t>(w[(static_cast<size_t>(dy * 5 + dx) * 8 + j) * cout + mt * 16 + (lane & 15)]);
-				}
-	}
-}
-
-struct AgxNet
-{
-		AgxNetDesc desc;
-		bool loaded = false;
-		void *d_w_in = nullptr;
-		void *d_w_tower = nullptr;
-		void *d_bias = nullptr;
-		void *d_wp2 = nullptr;
-		void *d_wv1 = nullptr;
-		void *d_wv2 = nullptr;
-		void *d_bv2 = nullptr;
-		void *d_wv3 = nullptr;
-		void *d_wq2 = nullptr;  // action-values head 1x1 weights [F][4] (padded), only with desc.action_values
-		float bq2[3] = { 0, 0, 0 };
-		// single-plane variant: residual scratch, one slice per workgroup of the persistent grid.  Launches on DIFFERENT streams may run
-		// concurrently (pool slices driven from several streams share one network), so every stream gets its own scratch; launches on
-		// one stream are ordered and share theirs.
-		std::mutex skip_mutex;
-		struct StreamScratch
-		{
-				hipStream_t stream;
-				void *skip;   // single-plane variant: residual scratch
-				void *vhead;  // value-head inputs of one launch: [boards][KPAD] halves
-				int vhead_boards;
-		};
-		std::vector<StreamScratch> scratch_by_stream;
-		size_t skip_bytes = 0;
-		bool inplace = false;
-		bool any_board = false; // the run-time-shaped kernel (nn_any_board.hip): every shape but 15x15 / 20x20, or AGX_NN_ANY_BOARD=1
-		float bp2 = 0.0f;
-		float bv1[4] = { 0, 0, 0, 0 };
-		float bv3[3] = { 0, 0, 0 };
-		int num_cus = 256;
-		int launch_width = 0; // 0 = every CU
-		int kpad() const { return (desc.rows * desc.cols * 4 + 31) / 32 * 32; } // value-head dense input length: 4 HW padded to whole MFMA k-steps
-		// AGX_ARCH_CONVNEXT: the network lives in nn_convnext.hip; of the members above only desc, loaded, num_cus and launch_width are used
-		int architecture = AGX_ARCH_RESNET;
-		int moves_left = 0;
-		agx_cnx::Net *convnext = nullptr;
-};
-
-namespace
-{
-	bool is_supported(const AgxNetDesc &d)
-	{
-		return d.rows >= agx_any::MIN_SIDE && d.rows <= agx_any::MAX_SIDE && d.cols >= agx_any::MIN_SIDE && d.cols <= agx_any::MAX_SIDE && (d.filters == 64 || d.filters == 128) && d.blocks >= 0
-				&& (d.in_channels == 32 || (d.in_channels == 8 && d.action_values == 0)) // 8: ResnetPVraw (networks.cpp:107-129); the raw PVQ variant is off the path
-				&& d.value_hidden == ((2 * d.filters < 256) ? 2 * d.filters : 256) && (d.action_values == 0 || d.action_values == 1);
-	}
-	void free_net_buffers(AgxNet *net)
-	{
-		void **ptrs[] = { &net->d_w_in, &net->d_w_tower, &net->d_bias, &net->d_wp2, &net->d_wv1, &net->d_wv2, &net->d_bv2, &net->d_wv3, &net->d_wq2 };
-		for (void **p : ptrs)
-		{
-			if (*p != nullptr)
-				(void) hipFree(*p);
-			*p = nullptr;
-		}
-		std::lock_guard<std::mutex> lock(net->skip_mutex);
-		for (auto &slice : net->scratch_by_stream)
-		{
-			if (slice.skip != nullptr)
-				(void) hipFree(slice.skip);
-			if (slice.vhead != nullptr)
-				(void) hipFree(slice.vhead);
-		}
-		net->scratch_by_stream.clear();
-	}
 	template<typename T>
 	int upload(void **dst, const std::vector<T> &src)
 	{
@@ -1918,365 +1806,294 @@ namespace
 	}
 }
 
-extern "C" {
-
-size_t agx_net_blob_floats(const AgxNetDesc *d)
+namespace agx_res
 {
-	if (d == nullptr)
-		return 0;
-	const size_t F = d->filters, C = d->in_channels, HW = static_cast<size_t>(d->rows) * d->cols, D = d->value_hidden;
-	size_t n = 25 * C * F + F;
-	n += static_cast<size_t>(d->blocks) * 2 * (9 * F * F + F);
-	n += 9 * F * F + F + F + 1;
-	n += F * 4 + 4 + HW * 4 * D + D + D * 3 + 3;
-	if (d->action_values)
-		n += 9 * F * F + F + F * 3 + 3;
-	return n;
-}
-
-size_t agx_net_blob_floats_ex(const AgxNetDesc *d, int architecture, int moves_left)
-{
-	if (d == nullptr)
-		return 0;
-	if (architecture == AGX_ARCH_CONVNEXT)
-		return agx_cnx::blob_floats(*d, moves_left);
-	return (architecture == AGX_ARCH_RESNET && moves_left == 0) ? agx_net_blob_floats(d) : 0;
-}
-
-int agx_net_create_ex(const AgxNetDesc *desc, int architecture, int moves_left, AgxNet **out)
-{
-	AGX_REQUIRE(desc != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_net_create_ex: null argument");
-	if (architecture == AGX_ARCH_RESNET && moves_left == 0)
-		return agx_net_create(desc, out);
-	AGX_REQUIRE(architecture == AGX_ARCH_CONVNEXT, AGX_ERR_UNSUPPORTED, "agx_net_create_ex: unsupported architecture %d with moves_left=%d (the residual networks have no moves-left head)",
-			architecture, moves_left);
-	AGX_REQUIRE(agx_cnx::supported(*desc, moves_left), AGX_ERR_UNSUPPORTED,
-			"agx_net_create_ex: unsupported ConvNeXt network %dx%d blocks=%d filters=%d cin=%d hidden=%d action_values=%d moves_left=%d (supported: 5..20 rows and cols, F in {64,128}, cin 8, hidden 256, with the action-values head)",
-			desc->rows, desc->cols, desc->blocks, desc->filters, desc->in_channels, desc->value_hidden, desc->action_values, moves_left);
-	AgxNet *net = new AgxNet();
-	net->desc = *desc;
-	net->architecture = architecture;
-	net->moves_left = moves_left;
-	int dev = 0;
-	hipDeviceProp_t prop;
-	if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-		net->num_cus = prop.multiProcessorCount;
-	*out = net;
-	return AGX_OK;
-}
-
-int agx_net_architecture(const AgxNet *net, int *architecture, int *moves_left)
-{
-	AGX_REQUIRE(net != nullptr && architecture != nullptr && moves_left != nullptr, AGX_ERR_INVALID, "agx_net_architecture: null argument");
-	*architecture = net->architecture;
-	*moves_left = net->moves_left;
-	return AGX_OK;
-}
-
-int agx_net_create(const AgxNetDesc *desc, AgxNet **out)
-{
-	AGX_REQUIRE(desc != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_net_create: null argument");
-	AGX_REQUIRE(is_supported(*desc), AGX_ERR_UNSUPPORTED,
-			"agx_net_create: unsupported network %dx%d blocks=%d filters=%d cin=%d hidden=%d (supported: 5..20 rows and cols, F in {64,128}, cin 32, or cin 8 without the action-values head)", desc->rows,
-			desc->cols, desc->blocks, desc->filters, desc->in_channels, desc->value_hidden);
-	AgxNet *net = new AgxNet();
-	net->desc = *desc;
-	int dev = 0;
-	hipDeviceProp_t prop;
-	if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-		net->num_cus = prop.multiProcessorCount;
-	*out = net;
-	return AGX_OK;
-}
-
-int agx_net_load_weights(AgxNet *net, const float *h_blob, size_t n_floats)
-{
-	AGX_REQUIRE(net != nullptr && h_blob != nullptr, AGX_ERR_INVALID, "agx_net_load_weights: null argument");
-	if (net->architecture == AGX_ARCH_CONVNEXT)
+	struct Net
 	{
-		const size_t expected = agx_cnx::blob_floats(net->desc, net->moves_left);
-		AGX_REQUIRE(n_floats == expected, AGX_ERR_INVALID, "agx_net_load_weights: blob has %zu floats, expected %zu", n_floats, expected);
-		agx_cnx::Net *fresh = nullptr;
-		const int status = agx_cnx::load(net->desc, net->moves_left, h_blob, &fresh);
-		if (status != AGX_OK)
-			return status;
-		if (net->convnext != nullptr)
-		{ // (launches of the old weights may be in flight)
-			AGX_HIP_CHECK(hipDeviceSynchronize());
-			agx_cnx::destroy(net->convnext);
-		}
-		net->convnext = fresh;
-		net->loaded = true;
-		return AGX_OK;
-	}
-	AGX_REQUIRE(n_floats == agx_net_blob_floats(&net->desc), AGX_ERR_INVALID, "agx_net_load_weights: blob has %zu floats, expected %zu", n_floats,
-			agx_net_blob_floats(&net->desc));
-	free_net_buffers(net);
-	net->loaded = false;
-
-	const int F = net->desc.filters, C = net->desc.in_channels, HW = net->desc.rows * net->desc.cols, D = net->desc.value_hidden;
-	const int blocks = net->desc.blocks;
-	const float *ptr = h_blob;
-
-	std::vector<half_t> w_in, w_tower, wv2;
-	std::vector<float> bias, wp2, wv1, bv2, wv3;
-
-	if (C == 8)
-		pack_conv5x5_raw(ptr, F, w_in);
-	else
-		pack_conv(ptr, 25, C, F, w_in);
-	ptr += 25 * C * F;
-	bias.insert(bias.end(), ptr, ptr + F);
-	ptr += F;
-	// 15x15 and 20x20 boards have kernels of their own; every other shape — and these two with AGX_NN_ANY_BOARD=1 — runs the run-time-shaped
-	// kernel (nn_any_board.hip), which reads its fragments tap-major (pack_conv)
-	const bool board15 = (net->desc.rows == 15 && net->desc.cols == 15), board20 = (net->desc.rows == 20 && net->desc.cols == 20);
-	const char *any = getenv("AGX_NN_ANY_BOARD");
-	net->any_board = !(board15 || board20) || (any != nullptr && any[0] == '1');
-	// 15x15 boards (row stride 16 = one MFMA tile) run the row-stationary k-loop, which reads the fragments in its own order
-	const bool row_order = board15 && !net->any_board;
-	// 20x20 boards with 128 filters run the column-tile k-loop (Geometry::COLT)
-	const bool column_order = board20 && F == 128 && !net->any_board;
-	auto pack3x3 = [&](const float *w)
-	{
-		if (row_order)
-			pack_conv_rows(w, F, F, w_tower, false, (F == 128) ? Geometry<128, 15, 15>::CG : Geometry<64, 15, 15>::CG);
-		else if (column_order)
-			pack_conv_rows(w, F, F, w_tower, true, Geometry<128, 20, 20>::CG);
-		else
-			pack_conv(w, 9, F, F, w_tower);
-	};
-	for (int l = 0; l < 2 * blocks + 1; l++)
-	{
-		pack3x3(ptr);
-		ptr += 9 * F * F;
-		bias.insert(bias.end(), ptr, ptr + F);
-		ptr += F;
-	}
-	wp2.assign(ptr, ptr + F);
-	ptr += F;
-	net->bp2 = *ptr++;
-	wv1.assign(ptr, ptr + F * 4);
-	ptr += F * 4;
-	for (int i = 0; i < 4; i++)
-		net->bv1[i] = *ptr++;
-	{ // dense 4 HW -> D in MFMA A-fragment order [k-step][16-unit tile][lane][8] (value_head_kernel), zero beyond the last input
-		const int kpad = net->kpad(), mtiles = D / 16;
-		wv2.assign(static_cast<size_t>(kpad) * D, static_cast<half_t>(0.0f));
-		for (int kc = 0; kc < kpad / 32; kc++)
-			for (int mt = 0; mt < mtiles; mt++)
-				for (int lane = 0; lane < 64; lane++)
-					for (int j = 0; j < 8; j++)
-					{
-						const int unit = mt * 16 + (lane & 15), k = kc * 32 + 8 * (lane >> 4) + j;
-						if (k < HW * 4)
-							wv2[((static_cast<size_t>(kc) * mtiles + mt) * 64 + lane) * 8 + j] = static_cast<half_t>(ptr[static_cast<size_t>(k) * D + unit]);
-					}
-	}
-	ptr += static_cast<size_t>(HW) * 4 * D;
-	bv2.assign(ptr, ptr + D);
-	ptr += D;
-	wv3.assign(ptr, ptr + D * 3);
-	ptr += D * 3;
-	for (int i = 0; i < 3; i++)
-		net->bv3[i] = *ptr++;
-	std::vector<float> wq2;
-	if (net->desc.action_values)
-	{ // createActionValuesHead (blocks.cpp:119-127): the 3x3 conv joins the packed tower layers, the 1x1 conv is kept in fp32
-		pack3x3(ptr);
-		ptr += 9 * F * F;
-		bias.insert(bias.end(), ptr, ptr + F);
-		ptr += F;
-		wq2.assign(static_cast<size_t>(F) * 4, 0.0f);
-		for (int c = 0; c < F; c++)
-			for (int o = 0; o < 3; o++)
-				wq2[c * 4 + o] = ptr[c * 3 + o];
-		ptr += F * 3;
-		for (int i = 0; i < 3; i++)
-			net->bq2[i] = *ptr++;
-	}
-
-	// 20x20 boards use the single-plane kernel (two planes do not fit into LDS); AGX_NN_SINGLE_PLANE=1 selects it for 15x15 too
-	const char *force = getenv("AGX_NN_SINGLE_PLANE");
-	net->inplace = net->any_board || board20 || (force != nullptr && force[0] == '1');
-	if (net->any_board) // (one plane for every shape; its residual scratch is sized for the largest board)
-		net->skip_bytes = agx_any::skip_bytes_per_workgroup(F) * static_cast<size_t>(net->num_cus);
-	else if (net->inplace)
-	{
-		const size_t per_wg = board20 ? ((F == 128) ? Geometry<128, 20, 20>::SKIP_PER_WG : Geometry<64, 20, 20>::SKIP_PER_WG)
-				: ((F == 128) ? Geometry<128, 15, 15>::SKIP_PER_WG : Geometry<64, 15, 15>::SKIP_PER_WG);
-		net->skip_bytes = per_wg * 8 * static_cast<size_t>(net->num_cus);
-	}
-	int status = AGX_OK;
-	if ((status = upload(&net->d_w_in, w_in)) != AGX_OK || (status = upload(&net->d_w_tower, w_tower)) != AGX_OK
-			|| (status = upload(&net->d_bias, bias)) != AGX_OK || (status = upload(&net->d_wp2, wp2)) != AGX_OK
-			|| (status = upload(&net->d_wv1, wv1)) != AGX_OK || (status = upload(&net->d_wv2, wv2)) != AGX_OK
-			|| (status = upload(&net->d_bv2, bv2)) != AGX_OK || (status = upload(&net->d_wv3, wv3)) != AGX_OK
-			|| (!wq2.empty() && (status = upload(&net->d_wq2, wq2)) != AGX_OK))
-	{
-		free_net_buffers(net);
-		return status;
-	}
-	net->loaded = true;
-	return AGX_OK;
-}
-
-static int launch_forward(AgxNet *net, const uint32_t *d_features, const int *d_slot_list, const int *d_count, int batch, float *d_policy, float *d_value,
-		float *d_action_values, void *stream, float *d_moves_left = nullptr)
-{
-	AGX_REQUIRE(net != nullptr, AGX_ERR_INVALID, "agx_nn_forward: null network");
-	AGX_REQUIRE(net->loaded, AGX_ERR_STATE, "agx_nn_forward: weights not loaded");
-	AGX_REQUIRE(batch >= 0, AGX_ERR_INVALID, "agx_nn_forward: negative batch");
-	if (batch == 0)
-		return AGX_OK;
-	AGX_REQUIRE(d_features != nullptr && d_policy != nullptr && d_value != nullptr, AGX_ERR_INVALID, "agx_nn_forward: null buffer");
-	AGX_REQUIRE(d_moves_left == nullptr || net->moves_left, AGX_ERR_INVALID, "agx_nn_forward: the network has no moves-left head");
-	if (net->architecture == AGX_ARCH_CONVNEXT)
-	{ // the same persistent grid and launch-width cap as below; the ConvNeXt tower needs no scratch
-		const int cnx_width = (net->launch_width > 0 && net->launch_width < net->num_cus) ? net->launch_width : net->num_cus;
-		return agx_cnx::launch(net->convnext, (batch < cnx_width) ? batch : cnx_width, d_features, d_slot_list, d_count, batch, d_policy, d_value, d_action_values,
-				d_moves_left, static_cast<hipStream_t>(stream));
-	}
-
-	NetParams p;
-	p.w_in = static_cast<const half8*>(net->d_w_in);
-	p.w_tower = static_cast<const half8*>(net->d_w_tower);
-	p.bias = static_cast<const float*>(net->d_bias);
-	p.wp2 = static_cast<const float*>(net->d_wp2);
-	p.wv1 = static_cast<const float*>(net->d_wv1);
-	p.wv2 = static_cast<const half_t*>(net->d_wv2);
-	p.bv2 = static_cast<const float*>(net->d_bv2);
-	p.wv3 = static_cast<const float*>(net->d_wv3);
-	p.bp2 = net->bp2;
-	for (int i = 0; i < 4; i++)
-		p.bv1[i] = net->bv1[i];
-	for (int i = 0; i < 3; i++)
-		p.bv3[i] = net->bv3[i];
-	p.blocks = net->desc.blocks;
-	p.batch = batch;
-	p.slot_list = d_slot_list;
-	p.count_ptr = d_count;
-	AGX_REQUIRE(d_action_values == nullptr || net->desc.action_values, AGX_ERR_INVALID, "agx_nn_forward: the network has no action-values head");
-	p.q = d_action_values;
-	p.wq2 = (d_action_values != nullptr) ? static_cast<const float*>(net->d_wq2) : nullptr;
-	for (int i = 0; i < 3; i++)
-		p.bq2[i] = net->bq2[i];
-
-	// persistent grid: one workgroup per CU it may use.  A pool stepped as pipelined slices narrows the launch (agx_net_set_launch_width) so that
-	// the CUs it leaves free run the OTHER slice's search kernels at the same time: a tower workgroup fills its CU's LDS and registers, so
-	// the two kinds of work never share a CU, they share the chip
-	const int width = (net->launch_width > 0 && net->launch_width < net->num_cus) ? net->launch_width : net->num_cus;
-	const int grid = (batch < width) ? batch : width;
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	p.skip = nullptr;
-	const int kpad = net->kpad();
-	{ // per-stream scratch: launches on one stream are ordered and share it, launches on different streams may overlap
-		std::lock_guard<std::mutex> lock(net->skip_mutex);
-		AgxNet::StreamScratch *mine = nullptr;
-		for (auto &slice : net->scratch_by_stream)
-			if (slice.stream == s)
-				mine = &slice;
-		if (mine == nullptr)
-		{
-			net->scratch_by_stream.push_back(AgxNet::StreamScratch { s, nullptr, nullptr, 0 });
-			mine = &net->scratch_by_stream.back();
-		}
-		if (net->inplace && mine->skip == nullptr)
-			AGX_HIP_CHECK(hipMalloc(&mine->skip, net->skip_bytes));
-		if (mine->vhead_boards < batch)
-		{ // grows to the largest launch seen on this stream (a pool's launches all have the same capacity)
-			if (mine->vhead != nullptr)
+			AgxNetDesc desc;
+			void *d_w_in = nullptr;
+			void *d_w_tower = nullptr;
+			void *d_bias = nullptr;
+			void *d_wp2 = nullptr;
+			void *d_wv1 = nullptr;
+			void *d_wv2 = nullptr;
+			void *d_bv2 = nullptr;
+			void *d_wv3 = nullptr;
+			void *d_wq2 = nullptr;  // action-values head 1x1 weights [F][4] (padded), only with desc.action_values
+			float bp2 = 0.0f;
+			float bv1[4] = { 0, 0, 0, 0 };
+			float bv3[3] = { 0, 0, 0 };
+			float bq2[3] = { 0, 0, 0 };
+			bool inplace = false;
+			bool any_board = false; // the run-time-shaped kernel (nn_any_board.hip): every shape but 15x15 / 20x20, or AGX_NN_ANY_BOARD=1
+			size_t skip_bytes = 0;
+			// single-plane variant: residual scratch, one slice per workgroup of the persistent grid.  Launches on DIFFERENT streams may run
+			// concurrently (pool slices driven from several streams share one network), so every stream gets its own scratch; launches on
+			// one stream are ordered and share theirs.
+			std::mutex skip_mutex;
+			struct StreamScratch
 			{
-				AGX_HIP_CHECK(hipStreamSynchronize(s));
-				AGX_HIP_CHECK(hipFree(mine->vhead));
-				mine->vhead = nullptr;
-			}
-			const size_t bytes = static_cast<size_t>(batch) * kpad * sizeof(half_t);
-			AGX_HIP_CHECK(hipMalloc(&mine->vhead, bytes));
-			AGX_HIP_CHECK(hipMemsetAsync(mine->vhead, 0, bytes, s)); // the k-padding stays zero: the tower kernel only writes the first 4 HW halves of a row
-			mine->vhead_boards = batch;
-		}
-		p.skip = static_cast<half4*>(mine->skip);
-		p.vhead_x = static_cast<half_t*>(mine->vhead);
+					hipStream_t stream;
+					void *skip;   // single-plane variant: residual scratch
+					void *vhead;  // value-head inputs of one launch: [boards][KPAD] halves
+					int vhead_boards;
+			};
+			std::vector<StreamScratch> scratch_by_stream;
+			int kpad() const { return (desc.rows * desc.cols * 4 + 31) / 32 * 32; } // value-head dense input length: 4 HW padded to whole MFMA k-steps
+	};
+
+	bool supported(const AgxNetDesc &d, int moves_left)
+	{
+		return moves_left == 0 && d.rows >= agx_any::MIN_SIDE && d.rows <= agx_any::MAX_SIDE && d.cols >= agx_any::MIN_SIDE && d.cols <= agx_any::MAX_SIDE
+				&& (d.filters == 64 || d.filters == 128) && d.blocks >= 0
+				&& (d.in_channels == 32 || (d.in_channels == 8 && d.action_values == 0)) // 8: ResnetPVraw (networks.cpp:107-129); the raw PVQ variant is off the path
+				&& d.value_hidden == ((2 * d.filters < 256) ? 2 * d.filters : 256) && (d.action_values == 0 || d.action_values == 1);
 	}
-	const bool big = (net->desc.rows == 20 && net->desc.cols == 20), wide = (net->desc.filters == 128), qhead = (p.q != nullptr), raw = (net->desc.in_channels == 8);
-	const dim3 g(grid), t(512);
+
+	size_t blob_floats(const AgxNetDesc &d)
+	{
+		const size_t F = d.filters, C = d.in_channels, HW = static_cast<size_t>(d.rows) * d.cols, D = d.value_hidden;
+		size_t n = 25 * C * F + F;
+		n += static_cast<size_t>(d.blocks) * 2 * (9 * F * F + F);
+		n += 9 * F * F + F + F + 1;
+		n += F * 4 + 4 + HW * 4 * D + D + D * 3 + 3;
+		if (d.action_values)
+			n += 9 * F * F + F + F * 3 + 3;
+		return n;
+	}
+
+	void destroy(Net *net)
+	{
+		if (net == nullptr)
+			return;
+		for (void *p : { net->d_w_in, net->d_w_tower, net->d_bias, net->d_wp2, net->d_wv1, net->d_wv2, net->d_bv2, net->d_wv3, net->d_wq2 })
+			if (p != nullptr)
+				(void) hipFree(p);
+		for (auto &slice : net->scratch_by_stream)
+		{
+			if (slice.skip != nullptr)
+				(void) hipFree(slice.skip);
+			if (slice.vhead != nullptr)
+				(void) hipFree(slice.vhead);
+		}
+		delete net;
+	}
+
+	int load(const AgxNetDesc &desc, int num_cus, const float *h_blob, Net **out)
+	{
+		AGX_REQUIRE(supported(desc, 0) && num_cus > 0 && h_blob != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_net_load_weights: invalid residual network");
+		Net *net = new Net();
+		net->desc = desc;
+		const int F = desc.filters, C = desc.in_channels, HW = desc.rows * desc.cols, D = desc.value_hidden;
+		const int blocks = desc.blocks;
+		const float *ptr = h_blob;
+
+		std::vector<half_t> w_in, w_tower, wv2;
+		std::vector<float> bias, wp2, wv1, bv2, wv3;
+
+		if (C == 8)
+			pack_conv5x5_raw(ptr, F, w_in);
+		else
+			pack_conv(ptr, 25, C, F, w_in);
+		ptr += 25 * C * F;
+		bias.insert(bias.end(), ptr, ptr + F);
+		ptr += F;
+		// 15x15 and 20x20 boards have kernels of their own; every other shape — and these two with AGX_NN_ANY_BOARD=1 — runs the run-time-shaped
+		// kernel (nn_any_board.hip), which reads its fragments tap-major (pack_conv)
+		const bool board15 = (desc.rows == 15 && desc.cols == 15), board20 = (desc.rows == 20 && desc.cols == 20);
+		const char *any = getenv("AGX_NN_ANY_BOARD");
+		net->any_board = !(board15 || board20) || (any != nullptr && any[0] == '1');
+		// 15x15 boards (row stride 16 = one MFMA tile) run the row-stationary k-loop, which reads the fragments in its own order
+		const bool row_order = board15 && !net->any_board;
+		// 20x20 boards with 128 filters run the column-tile k-loop (Geometry::COLT)
+		const bool column_order = board20 && F == 128 && !net->any_board;
+		auto pack3x3 = [&](const float *w)
+		{
+			if (row_order)
+				pack_conv_rows(w, F, F, w_tower, false, (F == 128) ? Geometry<128, 15, 15>::CG : Geometry<64, 15, 15>::CG);
+			else if (column_order)
+				pack_conv_rows(w, F, F, w_tower, true, Geometry<128, 20, 20>::CG);
+			else
+				pack_conv(w, 9, F, F, w_tower);
+		};
+		for (int l = 0; l < 2 * blocks + 1; l++)
+		{
+			pack3x3(ptr);
+			ptr += 9 * F * F;
+			bias.insert(bias.end(), ptr, ptr + F);
+			ptr += F;
+		}
+		wp2.assign(ptr, ptr + F);
+		ptr += F;
+		net->bp2 = *ptr++;
+		wv1.assign(ptr, ptr + F * 4);
+		ptr += F * 4;
+		for (int i = 0; i < 4; i++)
+			net->bv1[i] = *ptr++;
+		{ // dense 4 HW -> D in MFMA A-fragment order [k-step][16-unit tile][lane][8] (value_head_kernel), zero beyond the last input
+			const int kpad = net->kpad(), mtiles = D / 16;
+			wv2.assign(static_cast<size_t>(kpad) * D, static_cast<half_t>(0.0f));
+			for (int kc = 0; kc < kpad / 32; kc++)
+				for (int mt = 0; mt < mtiles; mt++)
+					for (int lane = 0; lane < 64; lane++)
+						for (int j = 0; j < 8; j++)
+						{
+							const int unit = mt * 16 + (lane & 15), k = kc * 32 + 8 * (lane >> 4) + j;
+							if (k < HW * 4)
+								wv2[((static_cast<size_t>(kc) * mtiles + mt) * 64 + lane) * 8 + j] = static_cast<half_t>(ptr[static_cast<size_t>(k) * D + unit]);
+						}
+		}
+		ptr += static_cast<size_t>(HW) * 4 * D;
+		bv2.assign(ptr, ptr + D);
+		ptr += D;
+		wv3.assign(ptr, ptr + D * 3);
+		ptr += D * 3;
+		for (int i = 0; i < 3; i++)
+			net->bv3[i] = *ptr++;
+		std::vector<float> wq2;
+		if (desc.action_values)
+		{ // createActionValuesHead (blocks.cpp:119-127): the 3x3 conv joins the packed tower layers, the 1x1 conv is kept in fp32
+			pack3x3(ptr);
+			ptr += 9 * F * F;
+			bias.insert(bias.end(), ptr, ptr + F);
+			ptr += F;
+			wq2.assign(static_cast<size_t>(F) * 4, 0.0f);
+			for (int c = 0; c < F; c++)
+				for (int o = 0; o < 3; o++)
+					wq2[c * 4 + o] = ptr[c * 3 + o];
+			ptr += F * 3;
+			for (int i = 0; i < 3; i++)
+				net->bq2[i] = *ptr++;
+		}
+
+		// 20x20 boards use the single-plane kernel (two planes do not fit into LDS); AGX_NN_SINGLE_PLANE=1 selects it for 15x15 too
+		const char *force = getenv("AGX_NN_SINGLE_PLANE");
+		net->inplace = net->any_board || board20 || (force != nullptr && force[0] == '1');
+		if (net->any_board) // (one plane for every shape; its residual scratch is sized for the largest board)
+			net->skip_bytes = agx_any::skip_bytes_per_workgroup(F) * static_cast<size_t>(num_cus);
+		else if (net->inplace)
+		{
+			const size_t per_wg = board20 ? ((F == 128) ? Geometry<128, 20, 20>::SKIP_PER_WG : Geometry<64, 20, 20>::SKIP_PER_WG)
+					: ((F == 128) ? Geometry<128, 15, 15>::SKIP_PER_WG : Geometry<64, 15, 15>::SKIP_PER_WG);
+			net->skip_bytes = per_wg * 8 * static_cast<size_t>(num_cus);
+		}
+		int status = AGX_OK;
+		if ((status = upload(&net->d_w_in, w_in)) != AGX_OK || (status = upload(&net->d_w_tower, w_tower)) != AGX_OK
+				|| (status = upload(&net->d_bias, bias)) != AGX_OK || (status = upload(&net->d_wp2, wp2)) != AGX_OK
+				|| (status = upload(&net->d_wv1, wv1)) != AGX_OK || (status = upload(&net->d_wv2, wv2)) != AGX_OK
+				|| (status = upload(&net->d_bv2, bv2)) != AGX_OK || (status = upload(&net->d_wv3, wv3)) != AGX_OK
+				|| (!wq2.empty() && (status = upload(&net->d_wq2, wq2)) != AGX_OK))
+		{
+			destroy(net);
+			return status;
+		}
+		*out = net;
+		return AGX_OK;
+	}
+
+	int launch(Net *net, int grid, const uint32_t *d_features, const int *d_slot_list, const int *d_count, int batch, float *d_policy, float *d_value,
+			float *d_action_values, hipStream_t s)
+	{
+		AGX_REQUIRE(net != nullptr && grid > 0, AGX_ERR_STATE, "agx_nn_forward: weights not loaded");
+		NetParams p;
+		p.w_in = static_cast<const half8*>(net->d_w_in);
+		p.w_tower = static_cast<const half8*>(net->d_w_tower);
+		p.bias = static_cast<const float*>(net->d_bias);
+		p.wp2 = static_cast<const float*>(net->d_wp2);
+		p.wv1 = static_cast<const float*>(net->d_wv1);
+		p.wv2 = static_cast<const half_t*>(net->d_wv2);
+		p.bv2 = static_cast<const float*>(net->d_bv2);
+		p.wv3 = static_cast<const float*>(net->d_wv3);
+		p.bp2 = net->bp2;
+		for (int i = 0; i < 4; i++)
+			p.bv1[i] = net->bv1[i];
+		for (int i = 0; i < 3; i++)
+			p.bv3[i] = net->bv3[i];
+		p.blocks = net->desc.blocks;
+		p.batch = batch;
+		p.slot_list = d_slot_list;
+		p.count_ptr = d_count;
+		p.q = d_action_values;
+		p.wq2 = (d_action_values != nullptr) ? static_cast<const float*>(net->d_wq2) : nullptr;
+		for (int i = 0; i < 3; i++)
+			p.bq2[i] = net->bq2[i];
+		p.skip = nullptr;
+		const int kpad = net->kpad();
+		{ // per-stream scratch: launches on one stream are ordered and share it, launches on different streams may overlap
+			std::lock_guard<std::mutex> lock(net->skip_mutex);
+			Net::StreamScratch *mine = nullptr;
+			for (auto &slice : net->scratch_by_stream)
+				if (slice.stream == s)
+					mine = &slice;
+			if (mine == nullptr)
+			{
+				net->scratch_by_stream.push_back(Net::StreamScratch { s, nullptr, nullptr, 0 });
+				mine = &net->scratch_by_stream.back();
+			}
+			if (net->inplace && mine->skip == nullptr)
+				AGX_HIP_CHECK(hipMalloc(&mine->skip, net->skip_bytes));
+			if (mine->vhead_boards < batch)
+			{ // grows to the largest launch seen on this stream (a pool's launches all have the same capacity)
+				if (mine->vhead != nullptr)
+				{
+					AGX_HIP_CHECK(hipStreamSynchronize(s));
+					AGX_HIP_CHECK(hipFree(mine->vhead));
+					mine->vhead = nullptr;
+				}
+				const size_t bytes = static_cast<size_t>(batch) * kpad * sizeof(half_t);
+				AGX_HIP_CHECK(hipMalloc(&mine->vhead, bytes));
+				AGX_HIP_CHECK(hipMemsetAsync(mine->vhead, 0, bytes, s)); // the k-padding stays zero: the tower kernel only writes the first 4 HW halves of a row
+				mine->vhead_boards = batch;
+			}
+			p.skip = static_cast<half4*>(mine->skip);
+			p.vhead_x = static_cast<half_t*>(mine->vhead);
+		}
+		const bool big = (net->desc.rows == 20 && net->desc.cols == 20), wide = (net->desc.filters == 128), qhead = (p.q != nullptr), raw = (net->desc.in_channels == 8);
+		const dim3 g(grid), t(512);
 #define AGX_LAUNCH_TOWER(FF, NN, IP, QH, RW) hipLaunchKernelGGL((nn_tower_kernel<FF, NN, NN, IP, QH, RW>), g, t, 0, s, p, d_features, d_policy, d_value)
 #define AGX_LAUNCH_HEADS(FF, NN, IP) do { if (qhead) AGX_LAUNCH_TOWER(FF, NN, IP, true, false); else if (raw) AGX_LAUNCH_TOWER(FF, NN, IP, false, true); \
 		else AGX_LAUNCH_TOWER(FF, NN, IP, false, false); } while (0)
-	if (net->any_board)
-	{
-		const int status = agx_any::launch(p, net->desc.rows, net->desc.cols, net->desc.filters, raw, grid, kpad, d_features, d_policy, s);
-		if (status != AGX_OK)
-			return status;
-	}
-	else if (net->inplace)
-	{
-		if (big && wide)
-			AGX_LAUNCH_HEADS(128, 20, true);
-		else if (big)
-			AGX_LAUNCH_HEADS(64, 20, true);
+		if (net->any_board)
+		{
+			const int status = agx_any::launch(p, net->desc.rows, net->desc.cols, net->desc.filters, raw, grid, kpad, d_features, d_policy, s);
+			if (status != AGX_OK)
+				return status;
+		}
+		else if (net->inplace)
+		{
+			if (big && wide)
+				AGX_LAUNCH_HEADS(128, 20, true);
+			else if (big)
+				AGX_LAUNCH_HEADS(64, 20, true);
+			else if (wide)
+				AGX_LAUNCH_HEADS(128, 15, true);
+			else
+				AGX_LAUNCH_HEADS(64, 15, true);
+		}
 		else if (wide)
-			AGX_LAUNCH_HEADS(128, 15, true);
+			AGX_LAUNCH_HEADS(128, 15, false);
 		else
-			AGX_LAUNCH_HEADS(64, 15, true);
-	}
-	else if (wide)
-		AGX_LAUNCH_HEADS(128, 15, false);
-	else
-		AGX_LAUNCH_HEADS(64, 15, false);
+			AGX_LAUNCH_HEADS(64, 15, false);
 #undef AGX_LAUNCH_HEADS
 #undef AGX_LAUNCH_TOWER
-	{ // the value head's dense layers for all boards of the launch, behind whichever tower ran
-		const dim3 vg((batch + 15) / 16), vt(256);
+		{ // the value head's dense layers for all boards of the launch, behind whichever tower ran
+			const dim3 vg((batch + 15) / 16), vt(256);
 #define AGX_LAUNCH_VALUE(DD) hipLaunchKernelGGL((value_head_kernel<DD>), vg, vt, 0, s, p.vhead_x, reinterpret_cast<const half8*>(p.wv2), p.bv2, p.wv3, \
 		p.bv3[0], p.bv3[1], p.bv3[2], d_slot_list, d_count, batch, kpad, d_value)
-		if (wide)
-			AGX_LAUNCH_VALUE(256);
-		else
-			AGX_LAUNCH_VALUE(128);
+			if (wide)
+				AGX_LAUNCH_VALUE(256);
+			else
+				AGX_LAUNCH_VALUE(128);
 #undef AGX_LAUNCH_VALUE
+		}
+		AGX_HIP_CHECK(hipGetLastError());
+		return AGX_OK;
 	}
-	AGX_HIP_CHECK(hipGetLastError());
-	return AGX_OK;
-}
-
-int agx_nn_forward(AgxNet *net, const uint32_t *d_features, int batch, float *d_policy, float *d_value, void *stream)
-{
-	return launch_forward(net, d_features, nullptr, nullptr, batch, d_policy, d_value, nullptr, stream);
-}
-int agx_nn_forward_pvq(AgxNet *net, const uint32_t *d_features, int batch, float *d_policy, float *d_value, float *d_action_values, void *stream)
-{
-	return launch_forward(net, d_features, nullptr, nullptr, batch, d_policy, d_value, d_action_values, stream);
-}
-int agx_nn_forward_indirect(AgxNet *net, const uint32_t *d_features, const int *d_slot_list, const int *d_count, int max_batch, float *d_policy,
-		float *d_value, void *stream)
-{
-	AGX_REQUIRE(d_slot_list != nullptr && d_count != nullptr, AGX_ERR_INVALID, "agx_nn_forward_indirect: null list");
-	return launch_forward(net, d_features, d_slot_list, d_count, max_batch, d_policy, d_value, nullptr, stream);
-}
-int agx_nn_forward_indirect_pvq(AgxNet *net, const uint32_t *d_features, const int *d_slot_list, const int *d_count, int max_batch, float *d_policy,
-		float *d_value, float *d_action_values, void *stream)
-{
-	AGX_REQUIRE(d_slot_list != nullptr && d_count != nullptr, AGX_ERR_INVALID, "agx_nn_forward_indirect_pvq: null list");
-	return launch_forward(net, d_features, d_slot_list, d_count, max_batch, d_policy, d_value, d_action_values, stream);
-}
-
-int agx_nn_forward_pvqm(AgxNet *net, const uint32_t *d_features, int batch, float *d_policy, float *d_value, float *d_action_values, float *d_moves_left,
-		void *stream)
-{
-	return launch_forward(net, d_features, nullptr, nullptr, batch, d_policy, d_value, d_action_values, stream, d_moves_left);
-}
-int agx_nn_forward_indirect_pvqm(AgxNet *net, const uint32_t *d_features, const int *d_slot_list, const int *d_count, int max_batch, float *d_policy,
-		float *d_value, float *d_action_values, float *d_moves_left, void *stream)
-{
-	AGX_REQUIRE(d_slot_list != nullptr && d_count != nullptr, AGX_ERR_INVALID, "agx_nn_forward_indirect_pvqm: null list");
-	return launch_forward(net, d_features, d_slot_list, d_count, max_batch, d_policy, d_value, d_action_values, stream, d_moves_left);
 }
 
 #ifdef AGX_NN_PROFILE
 /* profile builds only: shader cycles per phase summed over the workgroups (waves 0 and 4), then reset.  out[2][16] */
-int agx_debug_nn_profile(unsigned long long *out)
+extern "C" int agx_debug_nn_profile(unsigned long long *out)
 {
 	AGX_HIP_CHECK(hipDeviceSynchronize());
 	AGX_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_nn_prof), sizeof(unsigned long long) * 32));
@@ -2285,29 +2102,3 @@ int agx_debug_nn_profile(unsigned long long *out)
 	return AGX_OK;
 }
 #endif
-
-int agx_net_set_launch_width(AgxNet *net, int workgroups)
-{
-	AGX_REQUIRE(net != nullptr && workgroups >= 0, AGX_ERR_INVALID, "agx_net_set_launch_width: invalid argument");
-	net->launch_width = workgroups;
-	return AGX_OK;
-}
-
-int agx_net_description(const AgxNet *net, AgxNetDesc *out)
-{
-	AGX_REQUIRE(net != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_net_description: null argument");
-	*out = net->desc;
-	return AGX_OK;
-}
-
-int agx_net_destroy(AgxNet *net)
-{
-	if (net == nullptr)
-		return AGX_OK;
-	free_net_buffers(net);
-	agx_cnx::destroy(net->convnext);
-	delete net;
-	return AGX_OK;
-}
-
-} /* extern "C" */

@@ -78,6 +78,9 @@ typedef struct AgxNet AgxNet; /* opaque */
  * order is NHWC row-major: index = (row*cols + col)*4 + c.  */
 size_t agx_net_blob_floats(const AgxNetDesc* desc);
 int agx_net_create(const AgxNetDesc* desc, AgxNet** out);
+/* Packs and uploads the blob; may be called again on a network in use (it waits for the device before the old weights go).  A blob of the
+ * wrong length is AGX_ERR_INVALID before anything is touched.  A reload that fails later (an allocation, a copy) leaves the weights loaded
+ * before it in place, for every architecture: the new ones are complete on the device before the old ones are let go. */
 int agx_net_load_weights(AgxNet* net, const float* h_blob, size_t n_floats);
 /* d_features: uint32[batch][rows*cols] (one bit-packed word per cell);
  * d_policy: float[batch][rows*cols] (softmax over the board); d_value: float[batch][3] = (win, draw, loss). */

@@ -333,3 +333,65 @@ def test_one_network_on_two_streams(agx_lib):
     for s in streams:
         check(lib.agx_stream_destroy(s))
     net.close()
+
+
+RELOAD_CASES = [   # the smallest network that reaches each tower and each kind of scratch
+    ("two-plane 15x15 pv", synthetic.net_desc(blocks=1, filters=64)),
+    ("single-plane 20x20 pvq", synthetic.net_desc(rows=20, cols=20, blocks=1, filters=64, action_values=1)),     # residual scratch, q head
+    ("any-board 7x9 raw", synthetic.net_desc(rows=7, cols=9, blocks=1, filters=64, in_channels=8)),
+    ("convnext 5x6 pvqm", synthetic.convnext_desc(rows=5, cols=6, blocks=1, filters=64, moves_left=1)),
+]
+
+
+@pytest.mark.parametrize("label,d", RELOAD_CASES, ids=[c[0].replace(" ", "-") for c in RELOAD_CASES])
+def test_reload_into_a_live_network(agx_lib, label, d):
+    """agx_net_load_weights on a handle that has weights and per-stream scratch: the new weights give the bits of a fresh network (a larger
+    batch behind the reload, so the value-head scratch grows), the first weights loaded again give the first bits, and a refused blob leaves
+    the loaded weights in place."""
+    import ctypes
+    from alphagomoku_amd import lib, check
+    from alphagomoku_amd.networks import AGNetwork, DeviceBuffer
+    make = synthetic.make_convnext_weights if d.get("architecture") == "convnext" else synthetic.make_weights
+    blob_a, blob_b = make(d, seed=1234)[0], make(d, seed=4321)[0]
+    hw = d["rows"] * d["cols"]
+    heads = [hw, 3] + ([hw * 2] if d["action_values"] else []) + ([hw] if d.get("moves_left") else [])
+    small, large = synthetic.random_features(3, d["rows"], d["cols"], seed=21), synthetic.random_features(40, d["rows"], d["cols"], seed=22)
+
+    def forward_on(net, features, stream):
+        df = DeviceBuffer(features.nbytes)
+        df.upload(features)
+        outs = [DeviceBuffer(len(features) * n * 4) for n in heads]
+        ptrs = [o.ptr for o in outs] + [None] * (4 - len(outs))
+        net.forwardDevice(df.ptr, len(features), ptrs[0], ptrs[1], stream, ptrs[2], ptrs[3])
+        check(lib.agx_device_synchronize())
+        bits = [o.download((len(features), n), np.uint32) for o, n in zip(outs, heads)]
+        for b in [df] + outs:
+            b.free()
+        return bits
+
+    def same(x, y):
+        return len(x) == len(y) and all(np.array_equal(a, b) for a, b in zip(x, y))
+
+    stream = ctypes.c_void_p()
+    check(lib.agx_stream_create(ctypes.byref(stream)))
+    fresh = AGNetwork(d)
+    fresh.loadWeights(blob_b)
+    want_b = forward_on(fresh, large, None)
+    fresh.close()
+    net = AGNetwork(d)
+    try:
+        net.loadWeights(blob_a)
+        first = forward_on(net, small, None)                          # two scratch records: the null stream's and the created one's
+        assert same(forward_on(net, small, stream), first), label
+        net.loadWeights(blob_b)
+        assert same(forward_on(net, large, None), want_b), label
+        assert same(forward_on(net, large, stream), want_b), label
+        assert not same(forward_on(net, small, None), first), "%s: the two blobs give the same outputs" % label
+        net.loadWeights(blob_a)
+        assert same(forward_on(net, small, None), first) and same(forward_on(net, small, stream), first), label
+        short = blob_a[:-1].copy()
+        assert lib.agx_net_load_weights(net._net, short.ctypes.data_as(ctypes.c_void_p), short.size) == 1, label    # AGX_ERR_INVALID
+        assert same(forward_on(net, small, None), first) and same(forward_on(net, small, stream), first), label
+    finally:
+        net.close()
+        check(lib.agx_stream_destroy(stream))
