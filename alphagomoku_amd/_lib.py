@@ -360,8 +360,8 @@ class AgxPositionOutputs(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ["policy", "value", "action_values", "top_cells", "top_probs", "status"]]
 
 
-ARCH_RESNET, ARCH_CONVNEXT = 0, 1   # AgxNetArchitecture
-ARCHITECTURES = {"resnet": ARCH_RESNET, "convnext": ARCH_CONVNEXT}
+ARCH_RESNET, ARCH_CONVNEXT, ARCH_BOTTLENECK = 0, 1, 2   # AgxNetArchitecture
+ARCHITECTURES = {"resnet": ARCH_RESNET, "convnext": ARCH_CONVNEXT, "bottleneck": ARCH_BOTTLENECK}
 POSEVAL_MASK_FORBIDDEN, POSEVAL_RENORMALISE = 1, 2
 POSEVAL_STATUS_BAD_INPUT, POSEVAL_STATUS_FOUL_PROBE = 1, 2
 

@@ -89,18 +89,22 @@ namespace ag
 			game_config(gameOptions)
 	{
 		const bool convnext = (architecture == "ConvNextPVQraw" || architecture == "ConvNextPVQMraw");
-		if (architecture != "ResnetPV" && architecture != "ResnetPVQ" && architecture != "ResnetPVraw" && !convnext)
+		// BottleneckBroadcastPVraw and BottleneckPoolingPVraw build the very graph of BottleneckPVraw as the reference is written (networks.cpp:254-322:
+		// the broadcast lines are commented out, createPoolingBlock returns its input): they are taken and report the name BottleneckPVraw
+		const bool bottleneck_raw = (architecture == "BottleneckPVraw" || architecture == "BottleneckBroadcastPVraw" || architecture == "BottleneckPoolingPVraw");
+		const bool bottleneck = (architecture == "BottleneckPV" || architecture == "BottleneckPVQ" || bottleneck_raw);
+		if (architecture != "ResnetPV" && architecture != "ResnetPVQ" && architecture != "ResnetPVraw" && !convnext && !bottleneck)
 			throw std::logic_error("AGNetwork: unknown architecture '" + architecture
-					+ "' (the device towers implement ResnetPV, ResnetPVraw, ResnetPVQ, ConvNextPVQraw and ConvNextPVQMraw)");
-		this->architecture = convnext ? AGX_ARCH_CONVNEXT : AGX_ARCH_RESNET;
+					+ "' (the device towers implement ResnetPV, ResnetPVraw, ResnetPVQ, BottleneckPV, BottleneckPVraw, BottleneckPVQ, ConvNextPVQraw and ConvNextPVQMraw)");
+		this->architecture = convnext ? AGX_ARCH_CONVNEXT : (bottleneck ? AGX_ARCH_BOTTLENECK : AGX_ARCH_RESNET);
 		moves_left = (architecture == "ConvNextPVQMraw") ? 1 : 0;
 		desc.rows = gameOptions.rows;
 		desc.cols = gameOptions.cols;
 		desc.blocks = blocks;
 		desc.filters = filters;
-		desc.in_channels = (architecture == "ResnetPVraw" || convnext) ? 8 : 32; // networks.cpp:107-129: the raw networks see the 8 low bits of a feature word
+		desc.in_channels = (architecture == "ResnetPVraw" || bottleneck_raw || convnext) ? 8 : 32; // networks.cpp:107-129: the raw networks see the 8 low bits of a feature word
 		desc.value_hidden = convnext ? 256 : std::min(256, 2 * filters);
-		desc.action_values = (architecture == "ResnetPVQ" || convnext) ? 1 : 0;
+		desc.action_values = (architecture == "ResnetPVQ" || architecture == "BottleneckPVQ" || convnext) ? 1 : 0;
 		create();
 	}
 	AGNetwork::~AGNetwork()
@@ -137,6 +141,8 @@ namespace ag
 	{
 		if (architecture == AGX_ARCH_CONVNEXT)
 			return moves_left ? "ConvNextPVQMraw" : "ConvNextPVQraw";
+		if (architecture == AGX_ARCH_BOTTLENECK)
+			return desc.action_values ? "BottleneckPVQ" : (desc.in_channels == 8 ? "BottleneckPVraw" : "BottleneckPV");
 		return desc.action_values ? "ResnetPVQ" : (desc.in_channels == 8 ? "ResnetPVraw" : "ResnetPV");
 	}
 	size_t AGNetwork::numberOfWeights() const
@@ -277,7 +283,7 @@ namespace ag
 		f.write((architecture == AGX_ARCH_RESNET) ? "AGXW" : "AGXC", 4);
 		f.write(reinterpret_cast<const char*>(&desc), sizeof(desc));
 		if (architecture != AGX_ARCH_RESNET)
-		{ // the ConvNeXt container: two more ints behind the description
+		{ // the container of the other architectures (ConvNeXt, bottleneck): two more ints behind the description
 			const int32_t extra[2] = { architecture, moves_left };
 			f.write(reinterpret_cast<const char*>(extra), sizeof(extra));
 		}

@@ -44,6 +44,7 @@
 #include "nn_device.hpp"
 #include "nn_pack.hpp"
 #include "nn_any_board.hpp"
+#include "nn_bottleneck.hpp"
 #include "nn_resnet.hpp"
 
 #include <vector>
@@ -1825,6 +1826,7 @@ namespace agx_res
 			float bv3[3] = { 0, 0, 0 };
 			float bq2[3] = { 0, 0, 0 };
 			bool inplace = false;
+			bool bottleneck = false; // bottleneck blocks (nn_bottleneck.hip: one run-time-shaped kernel for every shape) between the same input block and heads
 			bool any_board = false; // the run-time-shaped kernel (nn_any_board.hip): every shape but 15x15 / 20x20, or AGX_NN_ANY_BOARD=1
 			size_t skip_bytes = 0;
 			// single-plane variant: residual scratch, one slice per workgroup of the persistent grid.  Launches on DIFFERENT streams may run
@@ -1850,11 +1852,14 @@ namespace agx_res
 				&& d.value_hidden == ((2 * d.filters < 256) ? 2 * d.filters : 256) && (d.action_values == 0 || d.action_values == 1);
 	}
 
-	size_t blob_floats(const AgxNetDesc &d)
+	size_t blob_floats(const AgxNetDesc &d, bool bottleneck)
 	{
 		const size_t F = d.filters, C = d.in_channels, HW = static_cast<size_t>(d.rows) * d.cols, D = d.value_hidden;
 		size_t n = 25 * C * F + F;
-		n += static_cast<size_t>(d.blocks) * 2 * (9 * F * F + F);
+		if (bottleneck) // W1 [F][F/2] b1, W2 [3][3][F/2][F/2] b2, W3 [3][3][F/2][F] b3
+			n += static_cast<size_t>(d.blocks) * (F * (F / 2) + F / 2 + 9 * (F / 2) * (F / 2) + F / 2 + 9 * (F / 2) * F + F);
+		else
+			n += static_cast<size_t>(d.blocks) * 2 * (9 * F * F + F);
 		n += 9 * F * F + F + F + 1;
 		n += F * 4 + 4 + HW * 4 * D + D + D * 3 + 3;
 		if (d.action_values)
@@ -1879,11 +1884,12 @@ namespace agx_res
 		delete net;
 	}
 
-	int load(const AgxNetDesc &desc, int num_cus, const float *h_blob, Net **out)
+	int load(const AgxNetDesc &desc, int num_cus, const float *h_blob, Net **out, bool bottleneck)
 	{
 		AGX_REQUIRE(supported(desc, 0) && num_cus > 0 && h_blob != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_net_load_weights: invalid residual network");
 		Net *net = new Net();
 		net->desc = desc;
+		net->bottleneck = bottleneck;
 		const int F = desc.filters, C = desc.in_channels, HW = desc.rows * desc.cols, D = desc.value_hidden;
 		const int blocks = desc.blocks;
 		const float *ptr = h_blob;
@@ -1902,7 +1908,7 @@ namespace agx_res
 		// kernel (nn_any_board.hip), which reads its fragments tap-major (pack_conv)
 		const bool board15 = (desc.rows == 15 && desc.cols == 15), board20 = (desc.rows == 20 && desc.cols == 20);
 		const char *any = getenv("AGX_NN_ANY_BOARD");
-		net->any_board = !(board15 || board20) || (any != nullptr && any[0] == '1');
+		net->any_board = bottleneck || !(board15 || board20) || (any != nullptr && any[0] == '1');
 		// 15x15 boards (row stride 16 = one MFMA tile) run the row-stationary k-loop, which reads the fragments in its own order
 		const bool row_order = board15 && !net->any_board;
 		// 20x20 boards with 128 filters run the column-tile k-loop (Geometry::COLT)
@@ -1916,7 +1922,18 @@ namespace agx_res
 			else
 				pack_conv(w, 9, F, F, w_tower);
 		};
-		for (int l = 0; l < 2 * blocks + 1; l++)
+		for (int blk = 0; bottleneck && blk < blocks; blk++)
+		{ // createBottleneckBlock_v3 (blocks.cpp:84-97): 1x1 F -> F/2, 3x3 F/2 -> F/2, 3x3 F/2 -> F, tap-major fragments
+			const int widths[3][3] = { { 1, F, F / 2 }, { 9, F / 2, F / 2 }, { 9, F / 2, F } }; // taps, in, out
+			for (const auto &layer : widths)
+			{
+				pack_conv(ptr, layer[0], layer[1], layer[2], w_tower);
+				ptr += layer[0] * layer[1] * layer[2];
+				bias.insert(bias.end(), ptr, ptr + layer[2]);
+				ptr += layer[2];
+			}
+		}
+		for (int l = 0; l < (bottleneck ? 0 : 2 * blocks) + 1; l++)
 		{
 			pack3x3(ptr);
 			ptr += 9 * F * F;
@@ -1970,7 +1987,7 @@ namespace agx_res
 		const char *force = getenv("AGX_NN_SINGLE_PLANE");
 		net->inplace = net->any_board || board20 || (force != nullptr && force[0] == '1');
 		if (net->any_board) // (one plane for every shape; its residual scratch is sized for the largest board)
-			net->skip_bytes = agx_any::skip_bytes_per_workgroup(F) * static_cast<size_t>(num_cus);
+			net->skip_bytes = (bottleneck ? agx_btl::skip_bytes_per_workgroup(F) : agx_any::skip_bytes_per_workgroup(F)) * static_cast<size_t>(num_cus);
 		else if (net->inplace)
 		{
 			const size_t per_wg = board20 ? ((F == 128) ? Geometry<128, 20, 20>::SKIP_PER_WG : Geometry<64, 20, 20>::SKIP_PER_WG)
@@ -2055,7 +2072,8 @@ namespace agx_res
 		else AGX_LAUNCH_TOWER(FF, NN, IP, false, false); } while (0)
 		if (net->any_board)
 		{
-			const int status = agx_any::launch(p, net->desc.rows, net->desc.cols, net->desc.filters, raw, grid, kpad, d_features, d_policy, s);
+			const int status = net->bottleneck ? agx_btl::launch(p, net->desc.rows, net->desc.cols, net->desc.filters, raw, grid, kpad, d_features, d_policy, s)
+					: agx_any::launch(p, net->desc.rows, net->desc.cols, net->desc.filters, raw, grid, kpad, d_features, d_policy, s);
 			if (status != AGX_OK)
 				return status;
 		}

@@ -1,7 +1,7 @@
 /*
  * nn_net.cpp — AgxNet and every network entry point of the C ABI (include/agx.h): the small thing above the towers.  An architecture is a
  * namespace with supported / blob_floats / load / destroy / launch over an opaque Net: agx_res (nn_resnet.hpp; the kernels and their host
- * side are in nn_forward.hip) and agx_cnx (nn_convnext.hpp, nn_convnext.hip).  Each function below checks its arguments once and forks on
+ * side are in nn_forward.hip; the bottleneck towers are a block kind of the same Net, kernel in nn_bottleneck.hip) and agx_cnx (nn_convnext.hpp, nn_convnext.hip).  Each function below checks its arguments once and forks on
  * the architecture in one place.
  */
 #include "agx_internal.hpp"
@@ -16,6 +16,7 @@ struct AgxNet
 		int num_cus = 256;
 		int launch_width = 0; // 0 = every CU
 		// the loaded weights: the pointer of `architecture` is non-null once agx_net_load_weights succeeded, the other one stays null
+		// (`resnet` carries the residual and the bottleneck towers)
 		agx_res::Net *resnet = nullptr;
 		agx_cnx::Net *convnext = nullptr;
 };
@@ -32,6 +33,8 @@ size_t agx_net_blob_floats_ex(const AgxNetDesc *d, int architecture, int moves_l
 			return (moves_left == 0) ? agx_res::blob_floats(*d) : 0;
 		case AGX_ARCH_CONVNEXT:
 			return agx_cnx::blob_floats(*d, moves_left);
+		case AGX_ARCH_BOTTLENECK:
+			return (moves_left == 0 && agx_res::supported(*d, 0)) ? agx_res::blob_floats(*d, true) : 0;
 		default:
 			return 0;
 	}
@@ -53,6 +56,11 @@ int agx_net_create_ex(const AgxNetDesc *desc, int architecture, int moves_left, 
 			AGX_REQUIRE(agx_res::supported(*desc, moves_left), AGX_ERR_UNSUPPORTED,
 					"agx_net_create: unsupported network %dx%d blocks=%d filters=%d cin=%d hidden=%d (supported: 5..20 rows and cols, F in {64,128}, cin 32, or cin 8 without the action-values head)",
 					desc->rows, desc->cols, desc->blocks, desc->filters, desc->in_channels, desc->value_hidden);
+			break;
+		case AGX_ARCH_BOTTLENECK:
+			AGX_REQUIRE(agx_res::supported(*desc, moves_left), AGX_ERR_UNSUPPORTED,
+					"agx_net_create_ex: unsupported bottleneck network %dx%d blocks=%d filters=%d cin=%d hidden=%d action_values=%d moves_left=%d (supported: 5..20 rows and cols, F in {64,128}, blocks >= 0, hidden min(256, 2F), cin 32, or cin 8 without the action-values head, no moves-left head)",
+					desc->rows, desc->cols, desc->blocks, desc->filters, desc->in_channels, desc->value_hidden, desc->action_values, moves_left);
 			break;
 		case AGX_ARCH_CONVNEXT:
 			AGX_REQUIRE(agx_cnx::supported(*desc, moves_left), AGX_ERR_UNSUPPORTED,
@@ -100,7 +108,8 @@ int agx_net_load_weights(AgxNet *net, const float *h_blob, size_t n_floats)
 	switch (net->architecture)
 	{
 		case AGX_ARCH_RESNET:
-			status = agx_res::load(net->desc, net->num_cus, h_blob, &resnet);
+		case AGX_ARCH_BOTTLENECK:
+			status = agx_res::load(net->desc, net->num_cus, h_blob, &resnet, net->architecture == AGX_ARCH_BOTTLENECK);
 			break;
 		case AGX_ARCH_CONVNEXT:
 			status = agx_cnx::load(net->desc, net->moves_left, h_blob, &convnext);
@@ -139,6 +148,7 @@ static int launch_forward(AgxNet *net, const uint32_t *d_features, const int *d_
 	switch (net->architecture)
 	{
 		case AGX_ARCH_RESNET:
+		case AGX_ARCH_BOTTLENECK:
 			return agx_res::launch(net->resnet, grid, d_features, d_slot_list, d_count, batch, d_policy, d_value, d_action_values, s);
 		case AGX_ARCH_CONVNEXT:
 			return agx_cnx::launch(net->convnext, grid, d_features, d_slot_list, d_count, batch, d_policy, d_value, d_action_values, d_moves_left, s);

@@ -32,7 +32,8 @@ class DeviceBuffer:
 
 class AGNetwork:
     """A network on the device.  `desc` is a dict as made by synthetic.net_desc() (ResnetPV / PVraw / PVQ) or synthetic.convnext_desc()
-    (ConvNextPVQraw / PVQMraw: desc["architecture"] == "convnext", desc["moves_left"] 0 or 1)."""
+    (ConvNextPVQraw / PVQMraw: desc["architecture"] == "convnext", desc["moves_left"] 0 or 1) or synthetic.bottleneck_desc() (BottleneckPV /
+    PVraw / PVQ: desc["architecture"] == "bottleneck")."""
 
     def __init__(self, desc):
         self.desc = dict(desc)

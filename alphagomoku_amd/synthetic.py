@@ -84,6 +84,43 @@ def make_convnext_weights(desc, seed=1234, residual_gain=0.5):
     return blob, parts
 
 
+def bottleneck_desc(rows=15, cols=15, blocks=6, filters=128, in_channels=32, action_values=0):
+    """BottleneckPV (in_channels 32), BottleneckPVraw (in_channels 8) or BottleneckPVQ (action_values 1), networks.cpp:170-361: net_desc() with
+    blocks of createBottleneckBlock_v3 (blocks.cpp:84-97): 1x1 F -> F/2, 3x3 F/2 -> F/2, 3x3 F/2 -> F, residual add, ReLU"""
+    return dict(net_desc(rows, cols, blocks, filters, in_channels, action_values), architecture="bottleneck", moves_left=0)
+
+
+def make_bottleneck_weights(desc, seed=1234, residual_gain=1.0, policy_gain=1.0):
+    """Returns (blob, parts) for a bottleneck_desc(): the canonical fp32 blob of include/agx.h (batch norms folded: scale 1, shift = small
+    normal bias) and the named arrays in blob order.  He-normal, fixed seed.  residual_gain scales the third convolution of every block and
+    policy_gain the policy head's final 1x1 convolution, for the reasons make_weights gives: under plain He-init the un-normalised residual
+    sums double their variance per block."""
+    rng = np.random.default_rng(seed)
+    F, C, HW, D = desc["filters"], desc["in_channels"], desc["rows"] * desc["cols"], desc["value_hidden"]
+    H = F // 2
+
+    def he(shape, fan_in):
+        return (rng.standard_normal(shape) * np.sqrt(2.0 / fan_in)).astype(np.float32)
+
+    def shift(n):
+        return (0.01 * rng.standard_normal(n)).astype(np.float32)
+
+    parts = [("conv_in.w", he((5, 5, C, F), 25 * C)), ("conv_in.b", shift(F))]
+    for i in range(desc["blocks"]):
+        parts += [("block%d.w1" % i, he((F, H), F)), ("block%d.b1" % i, shift(H)),
+                  ("block%d.w2" % i, he((3, 3, H, H), 9 * H)), ("block%d.b2" % i, shift(H)),
+                  ("block%d.w3" % i, he((3, 3, H, F), 9 * H) * np.float32(residual_gain)), ("block%d.b3" % i, shift(F))]
+    parts += [("policy.w1", he((3, 3, F, F), 9 * F)), ("policy.b1", shift(F)),
+              ("policy.w2", he((F,), F) * np.float32(policy_gain)), ("policy.b2", shift(1))]
+    parts += [("value.w1", he((F, 4), F)), ("value.b1", shift(4)),
+              ("value.w2", he((HW * 4, D), HW * 4)), ("value.b2", shift(D)),
+              ("value.w3", he((D, 3), D)), ("value.b3", shift(3))]
+    if desc.get("action_values", 0):
+        parts += [("q.w1", he((3, 3, F, F), 9 * F)), ("q.b1", shift(F)), ("q.w2", he((F, 3), F)), ("q.b2", shift(3))]
+    blob = np.concatenate([p[1].reshape(-1) for p in parts]).astype(np.float32)
+    return blob, parts
+
+
 def random_features(batch, rows, cols, seed=0):
     """Random bit-packed feature words with plausible sparsity (stones/legal bits dense, threat bits sparse)."""
     rng = np.random.default_rng(seed)
@@ -117,8 +154,8 @@ def make_openings(n, count, seed0=0, rules=0):
 
 def save_weights(path, desc, blob):
     """the weight container ag::AGNetwork::loadFromFile reads (include/alphagomoku_agx/networks.hpp): "AGXW", AgxNetDesc (7 ints), u64 count, fp32 blob.
-    A ConvNeXt description (convnext_desc) is written under a second magic, "AGXC", with two more ints behind the seven: AgxNetArchitecture
-    and moves_left."""
+    A ConvNeXt or bottleneck description (convnext_desc, bottleneck_desc) is written under a second magic, "AGXC", with two more ints behind
+    the seven: AgxNetArchitecture and moves_left."""
     import struct
     from ._lib import ARCHITECTURES
     architecture = ARCHITECTURES[desc.get("architecture", "resnet")]

@@ -165,6 +165,8 @@ def _conv(cin, cout, k, bias=False):
 
 class TowerModule(nn.Module):
     """ResnetPV (desc in_channels 32), ResnetPVraw (in_channels 8) or ResnetPVQ (action_values 1); desc as synthetic.net_desc() makes it.
+    With desc["architecture"] == "bottleneck" (synthetic.bottleneck_desc()) BottleneckPV / BottleneckPVraw / BottleneckPVQ: the same input block
+    and heads around blocks of three normed convolutions, 1x1 F -> F/2, 3x3 F/2 -> F/2, 3x3 F/2 -> F (createBottleneckBlock_v3, blocks.cpp:84-97).
     forward(input): load_batch's `input` [n, rows, cols, 32] (float32, or float16 which is widened); in_channels == 8 takes planes 0..7 (bit c of
     the feature word = channel c, AGNetwork.cpp:249-258).  Returns the LOGITS: policy [n, rows * cols], value [n, 3], q [n, rows, cols, 3]
     contiguous (None without the head); the softmaxes belong to the loss and to the device tower."""
@@ -176,7 +178,13 @@ class TowerModule(nn.Module):
         if c not in (8, 32):
             raise ValueError("in_channels must be 32 or 8")
         self.conv_in = _Normed(_conv(c, f, 5), f, True)
-        self.blocks = nn.ModuleList(nn.ModuleList([_Normed(_conv(f, f, 3), f, True), _Normed(_conv(f, f, 3), f, True)]) for _ in range(desc["blocks"]))
+        self.bottleneck = desc.get("architecture", "resnet") == "bottleneck"
+        if self.bottleneck:
+            h = f // 2
+            self.blocks = nn.ModuleList(nn.ModuleList([_Normed(_conv(f, h, 1), h, True), _Normed(_conv(h, h, 3), h, True), _Normed(_conv(h, f, 3), f, True)])
+                                        for _ in range(desc["blocks"]))
+        else:
+            self.blocks = nn.ModuleList(nn.ModuleList([_Normed(_conv(f, f, 3), f, True), _Normed(_conv(f, f, 3), f, True)]) for _ in range(desc["blocks"]))
         self.policy1 = _Normed(_conv(f, f, 3), f, True)
         self.policy2 = _conv(f, 1, 1, bias=True)
         self.value1 = _Normed(_conv(f, 4, 1), 4, True)
@@ -192,8 +200,11 @@ class TowerModule(nn.Module):
         n = x.shape[0]
         x = x[..., :self.desc["in_channels"]].to(self.policy2.weight.dtype).permute(0, 3, 1, 2)   # NHWC planes -> NCHW
         x = F.relu(self.conv_in(x))
-        for first, second in self.blocks:
-            x = F.relu(x + second(F.relu(first(x))))
+        for block in self.blocks:
+            y = x
+            for layer in block[:-1]:
+                y = F.relu(layer(y))
+            x = F.relu(x + block[-1](y))
         policy = self.policy2(F.relu(self.policy1(x))).reshape(n, -1)
         v = F.relu(self.value1(x)).permute(0, 2, 3, 1).reshape(n, -1)                           # the value head flattens in NHWC order
         value = self.value3(F.relu(self.value2(v)))
@@ -205,8 +216,8 @@ class TowerModule(nn.Module):
     def _layers(self):
         """(normed layers, biased layers) in blob order: ('normed', m) | ('biased', m)"""
         out = [("normed", self.conv_in)]
-        for first, second in self.blocks:
-            out += [("normed", first), ("normed", second)]
+        for block in self.blocks:
+            out += [("normed", layer) for layer in block]
         out += [("normed", self.policy1), ("biased", self.policy2), ("normed", self.value1), ("normed", self.value2), ("biased", self.value3)]
         if self.q1 is not None:
             out += [("normed", self.q1), ("biased", self.q2)]
@@ -299,10 +310,11 @@ def _from_blob_order(w, like):
     return w.permute(3, 2, 0, 1) if like.dim() == 4 else w.t()
 
 
-def export_blob(module):
+def export_blob(module, float64=False):
     """The module as the canonical weight blob of agx.h (what AGNetwork.loadWeights takes): every batch norm is folded into its layer with
     its RUNNING statistics — w * s, shift - mean * s, s = 1 / sqrt(var + eps), with a learnable scale ('gamma' layers) s = gamma / sqrt(var +
-    eps) and shift = beta — in float64, rounded once to float32, transposed to the blob's order.  Returns a numpy float32 array of agx_net_blob_floats(desc) values (the call waits for the copy from the device)."""
+    eps) and shift = beta — in float64, rounded once to float32 (float64=True: not rounded, for comparisons in float64; the device takes float32),
+    transposed to the blob's order.  Returns a numpy float32 array of agx_net_blob_floats(desc) values (the call waits for the copy from the device)."""
     parts = []
     with torch.no_grad():
         for kind, m in module._layers():
@@ -316,7 +328,7 @@ def export_blob(module):
                 parts += [_to_blob_order(w * s.view([-1] + [1] * (w.dim() - 1))), m.norm.bias.double() - m.norm.running_mean.double() * s]
             else:
                 parts += [_to_blob_order(m.weight.double()), m.bias.double()]
-        blob = torch.cat([p.reshape(-1) for p in parts]).to(torch.float32).cpu().numpy()
+        blob = torch.cat([p.reshape(-1) for p in parts]).to(torch.float64 if float64 else torch.float32).cpu().numpy()
     want = blob_floats(module.desc)
     if blob.size != want:
         raise AgxError("export_blob: the module holds %d values, the blob of its description %d" % (blob.size, want))

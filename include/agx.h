@@ -122,8 +122,17 @@ int agx_nn_forward_indirect_pvq(AgxNet* net, const uint32_t* d_features, const i
  *   value    Wv1[F][F] bv1[F]  Wv2[F][256] bv2[256]  Wv3[256][3] bv3[3]
  *   q        Wq1[F][F] bq1[F]  Wq2[F][3] bq2[3]
  *   m (only with moves_left)  Wm1[F][32] bm1[32]  Wm2[32][128] bm2[128]  Wm3[128][HW] bm3[HW]
- * 1x1 convolutions and dense layers are [in][out]; the depthwise convolution is a cross-correlation with "same" zero padding. */
-enum AgxNetArchitecture { AGX_ARCH_RESNET = 0, AGX_ARCH_CONVNEXT = 1 };
+ * 1x1 convolutions and dense layers are [in][out]; the depthwise convolution is a cross-correlation with "same" zero padding.
+ *
+ * Bottleneck networks: BottleneckPV, BottleneckPVraw and BottleneckPVQ (networks.cpp:170-361; blocks of createBottleneckBlock_v3,
+ * blocks.cpp:84-97).  For AGX_ARCH_BOTTLENECK the description is the residual networks': rows and cols 5..20, filters F 64 or 128 (the inner
+ * width is F/2), blocks >= 0, value_hidden min(256, 2F), in_channels 32, or 8 without the action-values head; moves_left 0.  Input block and
+ * heads are the residual networks'.  The canonical fp32 blob after the batch-norm fold:
+ *   conv_in  W[5][5][Cin][F] b[F]
+ *   blocks x { W1[F][F/2] b1[F/2]   W2[3][3][F/2][F/2] b2[F/2]   W3[3][3][F/2][F] b3[F] }
+ *            y = relu(W1.x + b1) ; y = relu(W2*y + b2) ; x = relu(x + W3*y + b3)
+ *   policy / value / action values: exactly the residual networks' parts (above), in their order */
+enum AgxNetArchitecture { AGX_ARCH_RESNET = 0, AGX_ARCH_CONVNEXT = 1, AGX_ARCH_BOTTLENECK = 2 };
 size_t agx_net_blob_floats_ex(const AgxNetDesc* desc, int architecture, int moves_left); /* 0 for a combination that does not exist */
 /* architecture AGX_ARCH_RESNET with moves_left 0 is agx_net_create.  What the kernels do not cover is AGX_ERR_UNSUPPORTED with a message.
  * Every entry point that takes an AgxNet takes the result: agx_net_load_weights (the blob above), agx_nn_forward[_indirect][_pvq],

@@ -86,21 +86,23 @@ namespace agx
 			AgxNetDesc m_desc { };
 			int m_architecture = AGX_ARCH_RESNET, m_moves_left = 0;
 		public:
-			/* architecture "ResnetPV" (networks.cpp:71-93), "ResnetPVQ" (:143-168, adds the action-values head), "ConvNextPVQraw" (:1078-1140) or
+			/* architecture "ResnetPV" (networks.cpp:71-93), "ResnetPVQ" (:143-168, adds the action-values head), "BottleneckPV" (:170-204),
+			 * "BottleneckPVraw" (:206-240, the 8 low bits of a feature word in), "BottleneckPVQ" (:324-361), "ConvNextPVQraw" (:1078-1140) or
 			 * "ConvNextPVQMraw" (:1142-1219, adds the moves-left output) */
 			AGNetwork(const GameConfig &cfg, int blocks, int filters, const std::string &architecture = "ResnetPV")
 			{
 				const bool convnext = (architecture == "ConvNextPVQraw" || architecture == "ConvNextPVQMraw");
-				if (architecture != "ResnetPV" && architecture != "ResnetPVQ" && !convnext)
+				const bool bottleneck = (architecture == "BottleneckPV" || architecture == "BottleneckPVraw" || architecture == "BottleneckPVQ");
+				if (architecture != "ResnetPV" && architecture != "ResnetPVQ" && !convnext && !bottleneck)
 					throw std::logic_error("AGNetwork: unknown architecture '" + architecture + "'");
-				m_architecture = convnext ? AGX_ARCH_CONVNEXT : AGX_ARCH_RESNET;
+				m_architecture = convnext ? AGX_ARCH_CONVNEXT : (bottleneck ? AGX_ARCH_BOTTLENECK : AGX_ARCH_RESNET);
 				m_moves_left = (architecture == "ConvNextPVQMraw") ? 1 : 0;
-				m_desc.action_values = (architecture == "ResnetPVQ" || convnext) ? 1 : 0;
+				m_desc.action_values = (architecture == "ResnetPVQ" || architecture == "BottleneckPVQ" || convnext) ? 1 : 0;
 				m_desc.rows = cfg.rows;
 				m_desc.cols = cfg.cols;
 				m_desc.blocks = blocks;
 				m_desc.filters = filters;
-				m_desc.in_channels = convnext ? 8 : 32;
+				m_desc.in_channels = (convnext || architecture == "BottleneckPVraw") ? 8 : 32;
 				m_desc.value_hidden = convnext ? 256 : ((2 * filters < 256) ? 2 * filters : 256);
 				check(agx_net_create_ex(&m_desc, m_architecture, m_moves_left, &m_net));
 			}

@@ -67,9 +67,11 @@ namespace ag
 		public:
 			AGNetwork() noexcept = default;
 			/* architecture "ResnetPV" / "ResnetPVraw" (outputs "pv"; the raw network reads the 8 low bits of a feature word), "ResnetPVQ" ("pvq"),
+			 * "BottleneckPV" / "BottleneckPVraw" ("pv") / "BottleneckPVQ" ("pvq") — "BottleneckBroadcastPVraw" and "BottleneckPoolingPVraw" are taken too:
+			 * as the reference is written they build the graph of BottleneckPVraw, and name() says so —,
 			 * "ConvNextPVQraw" ("pvq", raw input) or "ConvNextPVQMraw" ("pvqm": unpackOutput's movesLeft is the mean of the 'm' output).  The weight
 			 * container of saveToFile / loadFromFile is "AGXW" + AgxNetDesc + u64 count + fp32 blob for the residual networks and "AGXC" + AgxNetDesc
-			 * + two ints (AgxNetArchitecture, moves_left) + u64 count + fp32 blob for the ConvNeXt ones. */
+			 * + two ints (AgxNetArchitecture, moves_left) + u64 count + fp32 blob for the ConvNeXt and bottleneck ones. */
 			AGNetwork(const GameConfig &gameOptions, const std::string &architecture, int blocks, int filters);
 			AGNetwork(const AGNetwork &other) = delete;
 			AGNetwork& operator=(const AGNetwork &other) = delete;

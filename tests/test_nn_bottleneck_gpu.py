@@ -1,0 +1,338 @@
+"""The bottleneck towers (csrc/nn_bottleneck.hip: BottleneckPV / BottleneckPVraw / BottleneckPVQ) on the GPU.
+
+  * exact parity with the float64 reference of nn_bottleneck_ref.py on networks that round nowhere before the softmax
+    (test_nn_bottleneck_cpu.py proves it for every case here): 5x5 (waves without tiles), 8x8 (one tile per wave at F = 64), 6x20 / 20x6,
+    7x19, 15x15, 20x20, each with both filter counts, blocks 0 / 1 / 3, pv / raw / pvq, random and transparent heads.  Logit differences are
+    recovered from the softmax outputs (nn_exact.logit_deviation) and must stay within a quarter of the head's grid step.
+  * the entry points: slot list, narrowed launch, batch sizes, NULL q buffer, refusals.
+  * He-init networks against the storage-rounding restatement, bound derived on the CPU (nn_bottleneck_ref.tolerance).
+  * the network in a pool, under a position evaluator, from / under the trainer, and through the compiled classes.
+"""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import nn_bottleneck_ref as br
+import nn_exact as nx
+from alphagomoku_amd import synthetic
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = np.uint32(0x7FC0DEAD)                                 # a NaN payload no kernel produces
+
+
+@pytest.fixture(scope="module")
+def olib():
+    import oracle_lib as ol
+    return ol.load()
+
+
+def load(desc, blob):
+    from alphagomoku_amd.networks import AGNetwork
+    net = AGNetwork(desc)
+    net.loadWeights(blob)
+    return net
+
+
+def assert_exact(outputs, desc, blob, ref, label=""):
+    """device outputs (policy, value[, q]) against reference logits (the rule of test_nn_exact_gpu.assert_exact): every board within g / 4
+    in logit differences, arg-max equal wherever the reference's top two logits differ"""
+    g = br.head_grids(desc, blob)
+    report = []
+    assert len(outputs) == (3 if ref.q is not None else 2), label
+    for name, out, logits in zip(("policy", "value", "q"), outputs, (ref.policy, ref.value, ref.q)):
+        assert np.isfinite(out).all() and (out >= 0).all(), (label, name)
+        dev = nx.logit_deviation(out, logits)
+        report.append("%s %.2e (g/%.0f)" % (name, dev.max(), g[name] / max(dev.max(), 1e-30)))
+        assert (dev <= g[name] / 4).all(), "%s %s: logit deviation %.3e on board %d, grid %.3e" % (label, name, dev.max(), int(dev.argmax()), g[name])
+        if name != "q":
+            top2 = np.sort(logits, axis=1)[:, -2:]
+            decided = top2[:, 1] > top2[:, 0]
+            assert (out.argmax(1) == logits.argmax(1))[decided].all(), (label, name)
+    assert np.abs(outputs[0].sum(1) - 1.0).max() < 1e-5 and np.abs(outputs[1].sum(1) - 1.0).max() < 1e-5, label
+    print("exact %s: %s" % (label, ", ".join(report)))
+
+
+@pytest.mark.parametrize("rows,cols,filters,kind,blocks,heads,seed", br.network_cases())
+def test_exact_networks(agx_lib, rows, cols, filters, kind, blocks, heads, seed):
+    """policy, value and q logits EQUAL the float64 reference at every cell and class, on the directed and the random boards"""
+    desc, blob = br.cached_weights(rows, cols, filters, kind, blocks, heads, seed)
+    ref = br.cached_reference(rows, cols, filters, kind, blocks, heads, seed)
+    net = load(desc, blob)
+    try:
+        out = net.forward(br.features_of(rows, cols))
+    finally:
+        net.close()
+    assert_exact(out, desc, blob, ref, "%s %s heads seed %d" % (br.describe(desc), heads, seed))
+
+
+# ------------------------------------------------------------------------------------------------------------------------ entry points
+
+def device_buffers(hw, slots, with_q):
+    from alphagomoku_amd.networks import DeviceBuffer
+    sizes = [slots * hw, slots * 3] + ([slots * hw * 2] if with_q else [])
+    bufs = [DeviceBuffer(n * 4) for n in sizes]
+    for b, n in zip(bufs, sizes):
+        b.upload(np.full(n, SENTINEL, np.uint32))
+    return bufs, [(slots, hw), (slots, 3), (slots, hw, 2)][:len(sizes)]
+
+
+@pytest.mark.parametrize("rows,cols,filters,kind,blocks,heads,seed", br.ENTRY_POINT_CASES)
+def test_slot_list_launch_width_and_batch_sizes(agx_lib, rows, cols, filters, kind, blocks, heads, seed):
+    """the indirect (slot-list) call equals the direct call bit for bit, listed slots only, a NaN sentinel elsewhere; a launch narrowed to 3
+    workgroups equals the full-width launch bit for bit; batches of 1, 2 and 7 boards; a board's bits do not depend on where it sits; a
+    count above max_batch is capped"""
+    from alphagomoku_amd import check
+    from alphagomoku_amd.networks import DeviceBuffer
+    desc, blob = br.cached_weights(rows, cols, filters, kind, blocks, heads, seed)
+    with_q = kind == "pvq"
+    hw = rows * cols
+    f = br.features_of(rows, cols)
+    net = load(desc, blob)
+    try:
+        base = net.forward(f)
+        assert_exact(base, desc, blob, br.cached_reference(rows, cols, filters, kind, blocks, heads, seed), "entry points " + br.describe(desc))
+        check(agx_lib.agx_net_set_launch_width(net._net, 3))
+        for n in (1, 2, 7, len(f)):
+            out = net.forward(f[:n])
+            assert all(np.array_equal(a, b[:n]) for a, b in zip(out, base)), n
+        idx = (np.arange(7) * 5 + 3) % len(f)
+        assert all(np.array_equal(a, b[idx]) for a, b in zip(net.forward(f[idx]), base))
+        for width in (3, 0):
+            check(agx_lib.agx_net_set_launch_width(net._net, width))
+            slots, max_batch = len(f) + 5, len(f)
+            order = np.random.default_rng(3).permutation(slots)[:max_batch].astype(np.int32)
+            slot_features = np.zeros((slots, hw), np.uint32)
+            slot_features[order] = f
+            d_f, d_list, d_count = DeviceBuffer(slot_features.nbytes), DeviceBuffer(order.nbytes), DeviceBuffer(4)
+            d_f.upload(slot_features)
+            d_list.upload(order)
+            for count in (1, 7, max_batch, max_batch + 9):           # (a count above max_batch is capped)
+                d_count.upload(np.array([count], np.int32))
+                bufs, shapes = device_buffers(hw, slots, with_q)
+                if with_q:
+                    check(agx_lib.agx_nn_forward_indirect_pvqm(net._net, d_f.ptr, d_list.ptr, d_count.ptr, max_batch, *[b.ptr for b in bufs], None, None))
+                else:
+                    check(agx_lib.agx_nn_forward_indirect(net._net, d_f.ptr, d_list.ptr, d_count.ptr, max_batch, *[b.ptr for b in bufs], None))
+                check(agx_lib.agx_device_synchronize())
+                used = order[:min(count, max_batch)]
+                for b, shape, want in zip(bufs, shapes, base):
+                    got = b.download(shape, np.float32)
+                    assert np.array_equal(got[used], want[:len(used)]), (width, count)
+                    untouched = np.setdiff1d(np.arange(slots), used)
+                    assert (got[untouched].view(np.uint32) == SENTINEL).all(), (width, count)
+                    b.free()
+            for b in (d_f, d_list, d_count):
+                b.free()
+    finally:
+        net.close()
+
+
+def test_null_q_buffer_and_refusals(agx_lib):
+    from alphagomoku_amd import check
+    from alphagomoku_amd.networks import DeviceBuffer
+    rows, cols = 8, 16
+    hw = rows * cols
+    f = br.features_of(rows, cols)[:9]
+    d_f = DeviceBuffer(f.nbytes)
+    d_f.upload(f)
+    for case in br.ENTRY_POINT_CASES[1:]:                        # 8x16 1x128 pvq, 8x16 1x64 pv
+        desc, blob = br.cached_weights(*case)
+        with_q = case[3] == "pvq"
+        net = load(desc, blob)
+        arch, ml = ctypes.c_int(-1), ctypes.c_int(-1)
+        check(agx_lib.agx_net_architecture(net._net, ctypes.byref(arch), ctypes.byref(ml)))
+        assert (arch.value, ml.value) == (2, 0)
+        full = net.forward(f)
+        bufs, shapes = device_buffers(hw, len(f), True)
+        m = DeviceBuffer(len(f) * hw * 4)
+        m.upload(np.full(len(f) * hw, SENTINEL, np.uint32))
+        # a moves-left buffer on any bottleneck network is refused and nothing is launched
+        assert agx_lib.agx_nn_forward_pvqm(net._net, d_f.ptr, len(f), bufs[0].ptr, bufs[1].ptr, bufs[2].ptr if with_q else None, m.ptr, None) == 1    # AGX_ERR_INVALID
+        assert b"moves-left" in agx_lib.agx_last_error()
+        check(agx_lib.agx_device_synchronize())
+        assert all((b.download(s, np.uint32) == SENTINEL).all() for b, s in zip(bufs + [m], shapes + [(len(f), hw)]))
+        if with_q:
+            # a NULL q buffer skips the head: the other outputs keep their bits, through every call that can say so
+            for call in ("forward", "pvq", "pvqm"):
+                if call == "forward":
+                    check(agx_lib.agx_nn_forward(net._net, d_f.ptr, len(f), bufs[0].ptr, bufs[1].ptr, None))
+                elif call == "pvq":
+                    check(agx_lib.agx_nn_forward_pvq(net._net, d_f.ptr, len(f), bufs[0].ptr, bufs[1].ptr, None, None))
+                else:
+                    check(agx_lib.agx_nn_forward_pvqm(net._net, d_f.ptr, len(f), bufs[0].ptr, bufs[1].ptr, None, None, None))
+                check(agx_lib.agx_device_synchronize())
+                assert all(np.array_equal(bufs[i].download(shapes[i], np.float32), full[i]) for i in range(2)), call
+                assert (bufs[2].download(shapes[2], np.uint32) == SENTINEL).all(), call
+            check(agx_lib.agx_nn_forward_pvqm(net._net, d_f.ptr, len(f), bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, None, None))      # a NULL moves-left buffer is fine
+            check(agx_lib.agx_device_synchronize())
+            assert all(np.array_equal(bufs[i].download(shapes[i], np.float32), full[i]) for i in range(3))
+        else:
+            # a q buffer on a pv network is refused and nothing is launched
+            assert agx_lib.agx_nn_forward_pvq(net._net, d_f.ptr, len(f), bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, None) == 1
+            assert b"action-values" in agx_lib.agx_last_error()
+            check(agx_lib.agx_device_synchronize())
+            assert all((b.download(s, np.uint32) == SENTINEL).all() for b, s in zip(bufs, shapes))
+        for b in bufs + [m]:
+            b.free()
+        net.close()
+    d_f.free()
+
+
+# --------------------------------------------------------------------------------------------------------------------------- tolerance
+
+@pytest.mark.parametrize("rows,cols,blocks,filters,kind", br.HE_INIT_CASES)
+def test_he_init_network_within_the_derived_tolerance(agx_lib, rows, cols, blocks, filters, kind):
+    """make_bottleneck_weights against the storage-rounding restatement (fp16 where the kernel stores, fp32 sums).  The bound per output is
+    nn_bottleneck_ref.tolerance: 1e-3, or 4 x the restatement's forwards / backwards gap where that is larger — computed on the CPU before
+    the device's outputs are looked at.  The measured table (gap -> bound, device deviation on MI355X) is in DESIGN 3.14."""
+    desc = br.make_desc(rows, cols, filters, kind, blocks)
+    blob, _ = synthetic.make_bottleneck_weights(desc, residual_gain=br.HE_INIT_RESIDUAL_GAIN)
+    f = synthetic.random_features(4, rows, cols, seed=7)
+    forwards = br.restatement(desc, blob, f)
+    bounds, gaps = br.tolerance(desc, blob, f, forwards)
+    net = load(desc, blob)
+    try:
+        out = net.forward(f)
+    finally:
+        net.close()
+    assert len(out) == len(forwards)
+    deviations = [float(np.abs(o - w).max()) for o, w in zip(out, forwards)]
+    for name, dev, bound, gap in zip(("policy", "value", "q"), deviations, bounds, gaps):
+        print("tolerance %dx%d %dx%d %s %s: device deviation %.3e, bound %.3e (CPU gap %.3e)" % (rows, cols, blocks, filters, kind, name, dev, bound, gap))
+    for name, o, dev, bound in zip(("policy", "value", "q"), out, deviations, bounds):
+        assert np.isfinite(o).all() and dev <= bound, (name, dev, bound)
+    assert (out[0].argmax(1) == forwards[0].argmax(1)).all()
+
+
+# --------------------------------------------------------------------------------------------------------------------- above the tower
+
+def test_games_bit_exact_with_the_bottleneck_network_in_the_loop(agx_lib, olib):
+    """the pattern of test_nn_convnext_gpu.test_games_bit_exact_with_the_convnext_network_in_the_loop with a 2 x 64 BottleneckPVQ network:
+    freestyle 15x15, 4 games; the oracle tree is fed the device network's outputs (policy, value, q), root edges are compared bit for bit
+    after every step"""
+    from test_engine_gpu import _play_and_compare
+    d = synthetic.bottleneck_desc(15, 15, 2, 64, action_values=1)
+    blob, _ = synthetic.make_bottleneck_weights(d)
+    net = load(d, blob)
+
+    def evaluator(feats):
+        p, v, q = net.forward(np.ascontiguousarray(feats, dtype=np.uint32))
+        return p, np.ascontiguousarray(v[:, :2]), q
+    try:
+        compared, stats = _play_and_compare(olib, 0, games=4, batch=4, sims=100, max_steps=250, evaluator=evaluator, action_values=1,
+                                            speculative_solver=1, speculative_waves=48)
+        assert compared > 300 and stats["moves_played"] > 0
+    finally:
+        net.close()
+
+
+def test_pool_steps_with_the_network_on_the_device(agx_lib):
+    """GeneratorPool.step(net) (the pool's network stage on the device) == the network's outputs written by hand into the slot buffers"""
+    from alphagomoku_amd import selfplay
+    d = synthetic.bottleneck_desc(15, 15, 2, 64, action_values=1)
+    blob, _ = synthetic.make_bottleneck_weights(d)
+    net = load(d, blob)
+    openings = synthetic.make_openings(15, 4, seed0=3)
+    pools = []
+    for _ in range(2):
+        pool = selfplay.GeneratorPool(selfplay.default_config(n_games=4, max_batch_size=4, max_simulations=40, tss_table_entries=1 << 14,
+                                                              node_capacity=2048, edge_capacity=32768, action_values=1))
+        pool.begin(selfplay.pack_openings(openings))
+        pools.append(pool)
+    try:
+        for step in range(12):
+            pools[0].step(net)
+            pools[1].select_solve()
+            slots, feats = pools[1].scheduled()
+            if len(slots):
+                p, v, q = net.forward(feats)
+                pools[1].provide(slots, p, v, q)
+            pools[1].expand_backup()
+            for g in range(4):
+                a, b = pools[0].game_info(g), pools[1].game_info(g)
+                assert a["n_moves"] == b["n_moves"] and a["root_visits"] == b["root_visits"], (step, g)
+                assert [(e["move"], e["visits"], e["win"], e["draw"], e["prior"]) for e in a["edges"]] == \
+                       [(e["move"], e["visits"], e["win"], e["draw"], e["prior"]) for e in b["edges"]], (step, g)
+        assert any(e["win"] != 0.0 for e in pools[0].game_info(0)["edges"])   # the q outputs really seed the edges
+    finally:
+        for pool in pools:
+            pool.close()
+        net.close()
+
+
+def test_evaluate_positions_with_a_bottleneck_network(agx_lib):
+    """evaluate_positions == tests/position_eval_ref.py applied to the tower's own outputs, bit for bit"""
+    import oracle_lib as ol
+    import position_eval_ref as ref
+    from test_position_eval_gpu import Evaluator, combine_positions, check_against_restatement, tower_rows
+    n = 15
+    d = synthetic.bottleneck_desc(n, n, 1, 64, action_values=1)
+    blob, _ = synthetic.make_bottleneck_weights(d, seed=8)
+    net = load(d, blob)
+    positions = combine_positions(n)
+    boards, signs = [b for b, _ in positions], [s for _, s in positions]
+    pe = Evaluator(agx_lib, ol.RULES["RENJU"], n, len(positions))
+    try:
+        for mask in (0x01, 0xFF):
+            features, status = pe.encode(boards, signs, mask)
+            rows = tower_rows(net, features)
+            assert not status.any() and rows[2] is not None
+            for flags, top_k in ((0, 0), (ref.RENORMALISE, 8)):
+                out = pe.evaluate(net, boards, signs, mask, flags, top_k, True)
+                assert not out["status"].any()
+                check_against_restatement(out, n, positions, mask, flags, top_k, rows, features)
+        out = net.evaluate_positions(np.stack(boards), np.array(signs, np.uint8), ol.RULES["RENJU"], top_k=4)
+        assert out["policy"].shape == (len(boards), n, n) and out["action_values"].shape == (len(boards), n, n, 2) and np.isfinite(out["value"]).all()
+    finally:
+        pe.close()
+        net.close()
+
+
+def test_module_export_and_trainer_steps(agx_lib, olib, tmp_path):
+    """in a process of its own (tests/nn_bottleneck_torch_main.py): TowerModule -> load_module -> tower against module.eval() within the
+    derived tolerance; three Trainer.steps lower the loss"""
+    import training_batch_ref as tb
+    n = 9
+    games = [tb.oracle_game(olib, 0, n, 40, sims=32), tb.crafted_game(olib, n)]
+    path = tmp_path / "freestyle_9.bin"
+    tb.write_fragment(path, "FREESTYLE", n, games)
+    parsed = [tb.parse_game(g) for g in games]
+    samples = np.array([(0, g, k, a) for g, game in enumerate(parsed) for k in range(len(game["samples"])) for a in range(8)], np.int32)
+    samples = samples[::(len(samples) // 64) | 1]
+    listing = tmp_path / "samples.npy"
+    np.save(listing, samples)
+    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "nn_bottleneck_torch_main.py")
+    run = subprocess.run([sys.executable, script, str(path), str(listing)], capture_output=True, text=True, timeout=300)
+    print(run.stdout[-4000:])
+    assert run.returncode == 0 and run.stdout.strip().splitlines()[-1] == "ok", run.stdout[-3000:] + run.stderr[-3000:]
+
+
+def test_reference_named_classes_from_a_compiled_program(agx_lib, tmp_path):
+    """tests/cpp/bottleneck_main.cpp: ag::AGNetwork(..., "BottleneckPVQ"), a weight container read back, one batch forwarded, names and
+    output configs checked; the program prints its outputs, which must be the Python wrapper's"""
+    from alphagomoku_amd import build
+    d = synthetic.bottleneck_desc(15, 15, 1, 64, action_values=1)
+    blob, _ = synthetic.make_bottleneck_weights(d, seed=6)
+    path = tmp_path / "bottleneck.agxw"
+    synthetic.save_weights(path, d, blob)
+    f = synthetic.random_features(3, 15, 15, seed=2)
+    fpath = tmp_path / "features.bin"
+    f.tofile(fpath)
+    run = subprocess.run([build.BOTTLENECK_TEST, str(path), str(fpath), "3"], capture_output=True, text=True, timeout=120)
+    print(run.stdout[-2000:])
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
+    assert run.stdout.strip().splitlines()[-1] == "ok"
+    lines = dict(line.split(" ", 1) for line in run.stdout.strip().splitlines() if " " in line)
+    assert lines["name"] == "BottleneckPVQ" and lines["outputs"] == "pvq"
+    net = load(d, blob)
+    try:
+        p, v, q = net.forward(f)
+    finally:
+        net.close()
+    want = ["%.9g" % float(np.float32(x)) for x in (p[2].max(), v[2, 0], q[2, 7, 0])]
+    assert lines["values"].split() == want
