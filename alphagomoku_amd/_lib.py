@@ -435,3 +435,35 @@ def _declare(c):  # noqa: F811
     c.agx_position_searcher_slots.argtypes = [vp, vp, vp]
     c.agx_position_searcher_finished.argtypes = [vp, vp, ctypes.POINTER(ci)]
     c.agx_position_searcher_search.argtypes = [vp, vp, ci, vp, vp, vp, outputs, ci, ci, vp]
+
+
+class AgxPositionSampleSink(ctypes.Structure):
+    _fields_ = [("d_bytes", ctypes.c_void_p), ("stride", ctypes.c_int), ("d_sizes", ctypes.c_void_p)]
+
+
+class AgxReanalyseOptions(ctypes.Structure):
+    _fields_ = [("chunk", ctypes.c_int), ("serial_base", ctypes.c_int), ("max_steps", ctypes.c_int)]
+
+
+class AgxReanalyseStats(ctypes.Structure):
+    _fields_ = [("games", ctypes.c_int64), ("samples", ctypes.c_int64), ("replaced", ctypes.c_int64), ("kept", ctypes.c_int64),
+                ("status", ctypes.c_int64 * 4), ("steps", ctypes.c_int64)]
+
+
+def sample_stride(cells):
+    """bytes that hold any format-201 sample of a board of `cells` cells (16 + 6 per cell), rounded up to a multiple of 4"""
+    return (16 + 6 * cells + 3) // 4 * 4
+
+
+_declare_searcher = _declare
+
+
+def _declare(c):  # noqa: F811
+    _declare_searcher(c)
+    vp, ci, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+    outputs, sink = ctypes.POINTER(AgxPositionSearchOutputs), ctypes.POINTER(AgxPositionSampleSink)
+    c.agx_position_searcher_begin_ex.argtypes = [vp, ci, vp, vp, vp, outputs, sink, ci, ci, vp]
+    c.agx_position_searcher_search_ex.argtypes = [vp, vp, ci, vp, vp, vp, outputs, sink, ci, ci, vp]
+    c.agx_dataset_positions.argtypes = [vp, ci, vp, vp, vp, vp]
+    c.agx_game_buffer_add_reanalysed.argtypes = [vp, vp, sz, ci, vp, vp]
+    c.agx_dataset_reanalyse.argtypes = [vp, ci, vp, vp, vp, ctypes.POINTER(AgxReanalyseOptions), ctypes.POINTER(AgxReanalyseStats), vp]

@@ -29,6 +29,8 @@ namespace agx
 	int position_solver_describe(AgxPositionSolver *solver, int *rules, int *board_size, int *capacity, AgxSolvedPositions *workspace);
 	/* ... and "the work enqueued on `stream` so far still reads the solver's workspace": the solver's next call on another stream waits for it */
 	int position_solver_mark(AgxPositionSolver *solver, hipStream_t stream);
+	/* engine.hip, for agx_dataset_reanalyse (training_batch.hip): what a position searcher was created for */
+	int position_searcher_describe(AgxPositionSearcher *ps, int *rules, int *board_size, int *slots);
 }
 
 #define AGX_HIP_CHECK(expr)                                                                         \

@@ -3172,6 +3172,7 @@ namespace
 			const int32_t *serials; // [n] noise / symmetry serial (GameState::opening_id), null = 0
 			int n, max_pv, max_steps;
 			AgxPositionSearchOutputs out; // each may be null
+			AgxPositionSampleSink sink;   // format-201 samples (position_write_sample); d_bytes or d_sizes null = none
 			int *cursor;        // next position of the list
 			int *finished;      // positions whose outputs are written
 			int *slot_position; // [n_games] the position a slot searches, -1 = free
@@ -3203,6 +3204,8 @@ namespace
 				o.pv[static_cast<size_t>(p) * J.max_pv + i] = 0;
 		if (tid == 0)
 		{
+			if (J.sink.d_bytes != nullptr && J.sink.d_sizes != nullptr)
+				J.sink.d_sizes[p] = 0; // no root, no sample: the bytes stay as they are
 			if (o.status != nullptr)
 				o.status[p] = status;
 			if (o.root != nullptr)
@@ -3428,6 +3431,109 @@ namespace
 			}
 		}
 	}
+	/* The root of position p as the reference's SearchDataStorage_v201 bytes (sample_v201.hpp): k_advance's quantiser (SearchDataPack of the
+	 * root -> loadFrom + serialize, dataset/SearchDataStorage.cpp:326-374,410-419) for one wave, on the cell -> edge map of the harvest
+	 * stage.  The three maxima go through wave reductions (non-negative floats order like their bits); the kept cells — an edge with visits
+	 * or a proven score — are compacted in cell order by ballots, 64 cells at a time; on boards of more than 255 cells, where a cell 255 or
+	 * more past the previous entry gets an entry too, lane 0 walks the ballots' words instead (at most 400 cells).  entry_cell: LDS of the
+	 * caller, [MAXHW]; kept: [(MAXHW + 63) / 64]. */
+	__device__ void position_write_sample(const PositionJob &J, int p, const GameState &gs, const DNode &root, const DEdge *edges, const int16_t *cell_edge,
+			uint16_t *entry_cell, u64 *kept, int *sh_count, int hw, int lane)
+	{
+		const int n_edges = root.n_edges;
+		uint32_t max_prior = 0u, max_value = 0u, max_visits = 0u;
+		for (int i = lane; i < n_edges; i += 64)
+		{
+			const DEdge e = edges[root.edge_begin + i];
+			const float wd = fmaxf(e.win, e.draw);
+			max_prior = max(max_prior, __float_as_uint((e.prior > 0.0f) ? e.prior : 0.0f));
+			max_value = max(max_value, __float_as_uint((wd > 0.0f) ? wd : 0.0f));
+			max_visits = max(max_visits, static_cast<uint32_t>(max(e.visits, 0)));
+		}
+		max_prior = wave_reduce_umax(max_prior);
+		max_value = wave_reduce_umax(max_value);
+		max_visits = wave_reduce_umax(max_visits);
+		const float prior_scale = v201::prior_scale(__uint_as_float(max_prior)), value_scale = v201::value_scale(__uint_as_float(max_value));
+		const float visit_scale = v201::visit_scale(fmaxf(1.0f, static_cast<float>(max_visits)));
+		// ---- which cells get an entry (:333-337, in cell order) ----
+		int count = 0;
+		for (int base = 0; base < hw; base += 64)
+		{
+			const int i = base + lane;
+			bool natural = false;
+			if (i < hw && cell_edge[i] >= 0)
+			{
+				const DEdge e = edges[root.edge_begin + cell_edge[i]];
+				natural = e.visits > 0 || s_proven(e.score);
+			}
+			const u64 m = __ballot(natural);
+			if (hw <= 255)
+			{ // no cell can be 255 past anything: the entries are the kept cells
+				if (natural)
+					entry_cell[count + __popcll(m & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))))] = static_cast<uint16_t>(i);
+				count += __popcll(m);
+			}
+			else if (lane == 0)
+				kept[base >> 6] = m;
+		}
+		if (hw > 255)
+		{
+			if (lane == 0)
+			{
+				int last = 0;
+				for (int i = 0; i < hw; i++)
+					if (((kept[i >> 6] >> (i & 63)) & 1ull) || (i - last) >= 255)
+					{
+						entry_cell[count++] = static_cast<uint16_t>(i);
+						last = i;
+					}
+				*sh_count = count;
+			}
+			__syncthreads();
+			count = *sh_count;
+		}
+		__syncthreads();
+		// ---- header and entries; byte stores: the sink's address need not be aligned beyond the caller's stride ----
+		uint8_t *out = J.sink.d_bytes + static_cast<size_t>(p) * static_cast<size_t>(J.sink.stride);
+		if (lane < v201::HEADER_BYTES)
+		{
+			uint32_t word; // the 16 header bytes as four little-endian words
+			switch (lane >> 2)
+			{
+				case 0: word = v201::ScaleFormat::encode(value_scale) | (v201::ScaleFormat::encode(prior_scale) << 16); break;
+				case 1: word = v201::ScaleFormat::encode(visit_scale) | (static_cast<uint32_t>(root.score & 0xFFFFu) << 16); break;
+				case 2: word = static_cast<uint32_t>(gs.n_moves & 0xFFFF) | (static_cast<uint32_t>((root.flags >> 3) & 7) << 16); break; // stones on the board the root stands for
+				default: word = static_cast<uint32_t>(count); break;
+			}
+			out[lane] = static_cast<uint8_t>(word >> (8 * (lane & 3)));
+		}
+		for (int k = lane; k < count; k += 64)
+		{
+			const int cell = entry_cell[k], previous = (k > 0) ? entry_cell[k - 1] : 0;
+			const int ei = cell_edge[cell];
+			int visits = 0;
+			float prior = 0.0f, win = 0.0f, draw = 0.0f;
+			uint32_t score = s_unknown(0); // a filler cell without an edge: the SearchDataPack defaults (Score(), Value())
+			if (ei >= 0)
+			{
+				const DEdge e = edges[root.edge_begin + ei];
+				visits = e.visits;
+				prior = e.prior;
+				win = e.win;
+				draw = e.draw;
+				score = e.score;
+			}
+			uint8_t *q = out + v201::HEADER_BYTES + v201::ENTRY_BYTES * k;
+			q[0] = static_cast<uint8_t>(cell - previous);
+			q[1] = static_cast<uint8_t>(v201::VisitFormat::encode(static_cast<float>(visits) / visit_scale));
+			q[2] = static_cast<uint8_t>(v201::PriorFormat::encode(prior / prior_scale));
+			q[3] = static_cast<uint8_t>(v201::score_code(score));
+			q[4] = static_cast<uint8_t>(v201::PriorFormat::encode(win / value_scale));
+			q[5] = static_cast<uint8_t>(v201::PriorFormat::encode(draw / value_scale));
+		}
+		if (lane == 0)
+			J.sink.d_sizes[p] = v201::HEADER_BYTES + v201::ENTRY_BYTES * count;
+	}
 	/* k_advance's place in a step of the position searcher, one wave per slot: a slot whose move rule has fired (or whose engine error word is
 	 * set, or that has spent max_steps steps) writes the outputs of its position and becomes a finished game: leaves still in flight give their
 	 * virtual losses back (k_cancel_pending), park buffers are forgotten, grown arenas wait for k_arena_service, the slot is free. */
@@ -3435,6 +3541,9 @@ namespace
 	{
 		__shared__ u64 sh_cboard[BWORDS];
 		__shared__ int16_t cell_edge[MAXHW];
+		__shared__ uint16_t entry_cell[MAXHW]; // (the sample sink's: position_write_sample)
+		__shared__ u64 kept_cells[(MAXHW + 63) / 64];
+		__shared__ int sh_entries;
 		const int g = E.g0 + blockIdx.x, lane = threadIdx.x, hw = E.hw, n = E.n;
 		const int p = J.slot_position[g];
 		if (p < 0)
@@ -3542,6 +3651,8 @@ namespace
 					o.info[4 * p + 3] = error;
 				}
 			}
+			if (J.sink.d_bytes != nullptr && J.sink.d_sizes != nullptr) // (uniform: the job's)
+				position_write_sample(J, p, gs, root, edges, cell_edge, entry_cell, kept_cells, &sh_entries, hw, lane);
 			// ---- the principal variation: k_principal_variation's walk from the root ----
 			const int *ht = ht_of(E, g);
 			QueryWalk q;
@@ -6066,7 +6177,7 @@ namespace
 		return AGX_OK;
 	}
 	int searcher_begin_locked(AgxPositionSearcher *ps, int n, const uint8_t *d_boards, const uint8_t *d_signs, const int32_t *d_serials,
-			const AgxPositionSearchOutputs *out, int max_pv, int max_steps, hipStream_t stream)
+			const AgxPositionSearchOutputs *out, const AgxPositionSampleSink *sink, int max_pv, int max_steps, hipStream_t stream)
 	{
 		bool open = false;
 		const int st = searcher_job_open(ps, &open);
@@ -6083,6 +6194,9 @@ namespace
 		ps->job.max_pv = max_pv;
 		ps->job.max_steps = (max_steps > 0) ? max_steps : searcher_default_steps(ps);
 		ps->job.out = *out;
+		std::memset(&ps->job.sink, 0, sizeof(ps->job.sink));
+		if (sink != nullptr && sink->d_bytes != nullptr && sink->d_sizes != nullptr)
+			ps->job.sink = *sink;
 		ps->job_n = n;
 		ps->job_finished = 0;
 		const EngineDev d = searcher_dev(ps);
@@ -6098,6 +6212,15 @@ namespace
 		AGX_REQUIRE(n == 0 || (d_boards != nullptr && d_signs != nullptr), AGX_ERR_INVALID, "%s: null boards or signs", what);
 		return AGX_OK;
 	}
+	int searcher_sink_checks(const AgxPositionSearcher *ps, const AgxPositionSampleSink *sink, const char *what)
+	{ // (after searcher_begin_checks) a sample never outgrows its stride: 16 bytes and at most one entry per cell
+		if (sink == nullptr || sink->d_bytes == nullptr || sink->d_sizes == nullptr)
+			return AGX_OK;
+		const int needed = agx::v201::HEADER_BYTES + agx::v201::ENTRY_BYTES * ps->engine->dev.hw;
+		AGX_REQUIRE(sink->stride >= needed && sink->stride % 4 == 0, AGX_ERR_INVALID, "%s: a sample stride of %d bytes (at least %d and a multiple of 4 expected)", what,
+				sink->stride, needed);
+		return AGX_OK;
+	}
 	int searcher_harvest_locked(AgxPositionSearcher *ps, hipStream_t stream)
 	{ // harvest -> arena service -> load: ordered by the launch order on one stream, as the stages behind k_advance are
 		const EngineDev d = searcher_dev(ps);
@@ -6107,6 +6230,15 @@ namespace
 		hipLaunchKernelGGL(k_load_positions, dim3(ps->slots), dim3(256), 0, stream, d, ps->job);
 		return AGX_OK;
 	}
+}
+
+int agx::position_searcher_describe(AgxPositionSearcher *ps, int *rules, int *board_size, int *slots)
+{
+	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "position searcher: null searcher");
+	*rules = ps->engine->dev.rules;
+	*board_size = ps->engine->dev.n;
+	*slots = ps->slots;
+	return AGX_OK;
 }
 
 extern "C" {
@@ -6209,11 +6341,19 @@ int agx_position_searcher_engine(AgxPositionSearcher *ps, AgxEngine **out)
 int agx_position_searcher_begin(AgxPositionSearcher *ps, int n, const uint8_t *d_boards, const uint8_t *d_signs, const int32_t *d_serials,
 		const AgxPositionSearchOutputs *out, int max_pv, int max_steps, void *stream)
 {
-	const int st = searcher_begin_checks(ps, n, d_boards, d_signs, out, max_pv, "agx_position_searcher_begin");
+	return agx_position_searcher_begin_ex(ps, n, d_boards, d_signs, d_serials, out, nullptr, max_pv, max_steps, stream);
+}
+
+int agx_position_searcher_begin_ex(AgxPositionSearcher *ps, int n, const uint8_t *d_boards, const uint8_t *d_signs, const int32_t *d_serials,
+		const AgxPositionSearchOutputs *out, const AgxPositionSampleSink *sink, int max_pv, int max_steps, void *stream)
+{
+	int st = searcher_begin_checks(ps, n, d_boards, d_signs, out, max_pv, "agx_position_searcher_begin");
+	if (st == AGX_OK)
+		st = searcher_sink_checks(ps, sink, "agx_position_searcher_begin");
 	if (st != AGX_OK || n == 0)
 		return st;
 	std::lock_guard<std::mutex> lock(ps->mutex);
-	return searcher_begin_locked(ps, n, d_boards, d_signs, d_serials, out, max_pv, max_steps, static_cast<hipStream_t>(stream));
+	return searcher_begin_locked(ps, n, d_boards, d_signs, d_serials, out, sink, max_pv, max_steps, static_cast<hipStream_t>(stream));
 }
 
 int agx_position_searcher_select_solve(AgxPositionSearcher *ps, void *stream)
@@ -6299,7 +6439,15 @@ int agx_position_searcher_finished(AgxPositionSearcher *ps, void *stream, int *c
 int agx_position_searcher_search(AgxPositionSearcher *ps, AgxNet *net, int n, const uint8_t *d_boards, const uint8_t *d_signs, const int32_t *d_serials,
 		const AgxPositionSearchOutputs *out, int max_pv, int max_steps, void *stream_)
 {
-	const int checked = searcher_begin_checks(ps, n, d_boards, d_signs, out, max_pv, "agx_position_searcher_search");
+	return agx_position_searcher_search_ex(ps, net, n, d_boards, d_signs, d_serials, out, nullptr, max_pv, max_steps, stream_);
+}
+
+int agx_position_searcher_search_ex(AgxPositionSearcher *ps, AgxNet *net, int n, const uint8_t *d_boards, const uint8_t *d_signs, const int32_t *d_serials,
+		const AgxPositionSearchOutputs *out, const AgxPositionSampleSink *sink, int max_pv, int max_steps, void *stream_)
+{
+	int checked = searcher_begin_checks(ps, n, d_boards, d_signs, out, max_pv, "agx_position_searcher_search");
+	if (checked == AGX_OK)
+		checked = searcher_sink_checks(ps, sink, "agx_position_searcher_search");
 	if (checked != AGX_OK)
 		return checked;
 	AGX_REQUIRE(net != nullptr, AGX_ERR_INVALID, "agx_position_searcher_search: null network");
@@ -6307,7 +6455,7 @@ int agx_position_searcher_search(AgxPositionSearcher *ps, AgxNet *net, int n, co
 		return AGX_OK;
 	hipStream_t stream = static_cast<hipStream_t>(stream_);
 	std::lock_guard<std::mutex> lock(ps->mutex);
-	int st = searcher_begin_locked(ps, n, d_boards, d_signs, d_serials, out, max_pv, max_steps, stream);
+	int st = searcher_begin_locked(ps, n, d_boards, d_signs, d_serials, out, sink, max_pv, max_steps, stream);
 	if (st != AGX_OK)
 		return st;
 	// every position finishes within max_steps steps of its load, a slot loads a new one in the step that finishes the old one: the slots work

@@ -474,6 +474,65 @@ int agx_game_buffer_forget_engine(AgxGameBuffer *b, const AgxEngine *engine)
 	return AGX_OK;
 }
 
+/* A saved game with some of its samples searched again (agx_dataset_reanalyse): the GameDataStorage bytes of h_game with sample k replaced
+ * by h_samples[k] where h_sizes[k] > 0; move list, outcome, rows and cols stay the game's. */
+int agx_game_buffer_add_reanalysed(AgxGameBuffer *b, const uint8_t *h_game, size_t size, int n_samples, const uint8_t *const*h_samples, const int32_t *h_sizes)
+{
+	using namespace agx::v201;
+	const char *who = "agx_game_buffer_add_reanalysed";
+	AGX_REQUIRE(b != nullptr && h_game != nullptr && n_samples >= 0 && (n_samples == 0 || (h_samples != nullptr && h_sizes != nullptr)), AGX_ERR_INVALID,
+			"%s: null argument or a negative sample count", who);
+	AGX_REQUIRE(size >= 20, AGX_ERR_INVALID, "%s: the game is truncated (%zu bytes)", who, size);
+	uint32_t count = 0, n_moves = 0;
+	std::memcpy(&count, h_game, 4);
+	AGX_REQUIRE(static_cast<long long>(count) == n_samples, AGX_ERR_INVALID, "%s: %d samples given for a game of %u", who, n_samples, count);
+	std::vector<uint8_t> out;
+	out.reserve(size);
+	put<uint32_t>(out, count);
+	size_t at = 4;
+	for (uint32_t k = 0; k < count; k++)
+	{
+		AGX_REQUIRE(size - at >= static_cast<size_t>(HEADER_BYTES), AGX_ERR_INVALID, "%s: the game is truncated in sample %u", who, k);
+		uint16_t move_number = 0;
+		uint32_t entries = 0;
+		std::memcpy(&move_number, h_game + at + 8, 2);
+		std::memcpy(&entries, h_game + at + 12, 4);
+		AGX_REQUIRE((size - at - HEADER_BYTES) / ENTRY_BYTES >= entries, AGX_ERR_INVALID, "%s: the game is truncated in sample %u (%u entries)", who, k, entries);
+		const size_t old_bytes = HEADER_BYTES + static_cast<size_t>(ENTRY_BYTES) * entries;
+		if (h_sizes[k] > 0)
+		{
+			AGX_REQUIRE(h_samples[k] != nullptr && h_sizes[k] >= HEADER_BYTES, AGX_ERR_INVALID, "%s: the replacement of sample %u is null or shorter than a header", who, k);
+			uint16_t new_number = 0;
+			uint32_t new_entries = 0;
+			std::memcpy(&new_number, h_samples[k] + 8, 2);
+			std::memcpy(&new_entries, h_samples[k] + 12, 4);
+			AGX_REQUIRE(static_cast<size_t>(h_sizes[k]) == HEADER_BYTES + static_cast<size_t>(ENTRY_BYTES) * new_entries, AGX_ERR_INVALID,
+					"%s: the replacement of sample %u has %d bytes where its %u entries need %zu", who, k, h_sizes[k], new_entries,
+					HEADER_BYTES + static_cast<size_t>(ENTRY_BYTES) * new_entries);
+			AGX_REQUIRE(new_number == move_number, AGX_ERR_INVALID, "%s: the replacement of sample %u stands at move %d, the game's sample at move %d", who, k, new_number,
+					move_number);
+			out.insert(out.end(), h_samples[k], h_samples[k] + h_sizes[k]);
+		}
+		else
+			out.insert(out.end(), h_game + at, h_game + at + old_bytes);
+		at += old_bytes;
+	}
+	AGX_REQUIRE(size - at >= 4, AGX_ERR_INVALID, "%s: the game is truncated before its moves", who);
+	std::memcpy(&n_moves, h_game + at, 4);
+	AGX_REQUIRE((size - at - 4) / 2 >= n_moves && size - at - 4 - 2 * static_cast<size_t>(n_moves) == 12, AGX_ERR_INVALID,
+			"%s: the game has %zu bytes where its layout needs %zu", who, size, at + 4 + 2 * static_cast<size_t>(n_moves) + 12);
+	int tail[3];
+	std::memcpy(tail, h_game + size - 12, 12);
+	AGX_REQUIRE(tail[1] == b->rows && tail[2] == b->cols, AGX_ERR_INVALID, "%s: the game is %dx%d, the buffer %dx%d", who, tail[1], tail[2], b->rows, b->cols);
+	out.insert(out.end(), h_game + at, h_game + size);
+	std::lock_guard<std::mutex> lock(b->mutex);
+	b->games.push_back(std::move(out));
+	b->outcomes.push_back(tail[0]);
+	b->lengths.push_back(static_cast<int>(n_moves));
+	b->samples.push_back(static_cast<int>(count));
+	return AGX_OK;
+}
+
 int agx_sample_v201_unpack(const uint8_t *h_bytes, size_t size, int rows, int cols, int32_t *visits, float *prior, float *value, uint16_t *score, int *header,
 		float *minimax_value, size_t *consumed)
 {

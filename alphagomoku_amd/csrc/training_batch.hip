@@ -544,6 +544,40 @@ namespace agx
 				wave_sync(); // the next sample reuses the LDS arrays
 			}
 		}
+
+		/* The positions of the samples as the position searcher takes them (agx_dataset_positions): stage 1 of k_training_batch without
+		 * the entry map — one wavefront per sample scatters the game's first move_number moves into a board in LDS and writes it out
+		 * whole, and the colour of move move_number as the side to move (the rule of k_training_batch; the host has checked that the
+		 * moves lie on the board and that move_number is below the game's move count). */
+		__global__ __launch_bounds__(64) void k_dataset_positions(const BatchRecord *records, int count, int n, int hw, uint8_t *boards, uint8_t *signs)
+		{
+			using namespace dev;
+			__shared__ uint8_t board[MAXHW];
+			const int lane = threadIdx.x;
+			for (int b = blockIdx.x; b < count; b += gridDim.x)
+			{
+				const BatchRecord rec = records[b];
+				const uint8_t *sample = rec.blob + rec.sample_off;
+				const uint8_t *moves = rec.blob + rec.moves_off;
+				const int move_number = min(static_cast<int>(load_u16(sample + 8)), rec.n_moves - 1);
+				for (int i = lane; i < hw; i += 64)
+					board[i] = 0;
+				wave_sync();
+				for (int k = lane; k < move_number; k += 64)
+				{ // Board::putMove of moves 0 .. move_number - 1
+					const uint32_t mv = load_u16(moves + 2 * k);
+					const int cell = static_cast<int>((mv >> 2) & 127u) * n + static_cast<int>((mv >> 9) & 127u);
+					if (cell < hw)
+						board[cell] = static_cast<uint8_t>(mv & 3u);
+				}
+				wave_sync();
+				for (int i = lane; i < hw; i += 64)
+					boards[static_cast<size_t>(b) * hw + i] = board[i];
+				if (lane == 0)
+					signs[b] = static_cast<uint8_t>(load_u16(moves + 2 * move_number) & 3u);
+				wave_sync(); // the next sample reuses the board
+			}
+		}
 	}
 }
 
@@ -756,6 +790,77 @@ namespace
 		}
 		return AGX_OK;
 	}
+	/* The record ring of the batch launches (agx_dataset_load_batch_ex, agx_dataset_positions), under the dataset's mutex.  take_record_slot:
+	 * the fragments the batch uses go to the device (once per fragment: a blocking copy out of pageable memory), the next slot of the ring is
+	 * free again once the launch that read it RING batches ago has finished — the only thing a call ever waits for. */
+	int take_record_slot(AgxDataset *d, const std::vector<Fragment*> &used, RecordSlot **out)
+	{
+		for (Fragment *f : used)
+			if (f->d_blob == nullptr)
+			{
+				AGX_HIP_CHECK(hipMalloc(&f->d_blob, std::max<size_t>(f->blob.size(), 1)));
+				AGX_HIP_CHECK(hipMemcpy(f->d_blob, f->blob.data(), f->blob.size(), hipMemcpyHostToDevice));
+			}
+		RecordSlot &slot = d->slots[d->next_slot];
+		d->next_slot = (d->next_slot + 1) % RING;
+		if (slot.in_flight)
+		{
+			AGX_HIP_CHECK(hipEventSynchronize(slot.done));
+			slot.in_flight = false;
+		}
+		*out = &slot;
+		return AGX_OK;
+	}
+	/* ... the samples resolved into the slot's pinned records and sent behind `stream` ... */
+	int send_records(AgxDataset *d, RecordSlot &slot, int n, const AgxDatasetSample *h_samples, hipStream_t stream)
+	{
+		if (slot.capacity < n)
+		{ // a larger batch than this slot has seen: new buffers (an allocation, which the runtime may serialise with the device's work); the
+		  // old ones are not freed here, which would synchronise the device, but with the dataset
+			if (slot.h != nullptr)
+				d->retired_host.push_back(slot.h);
+			if (slot.d != nullptr)
+				d->retired_device.push_back(slot.d);
+			slot.h = nullptr;
+			slot.d = nullptr;
+			slot.capacity = 0;
+			const int capacity = std::max(n, 1024);
+			AGX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&slot.h), sizeof(BatchRecord) * capacity, hipHostMallocDefault));
+			AGX_HIP_CHECK(hipMalloc(&slot.d, sizeof(BatchRecord) * capacity));
+			slot.capacity = capacity;
+		}
+		for (int b = 0; b < n; b++)
+		{
+			const AgxDatasetSample &s = h_samples[b];
+			const Fragment &f = *d->fragments.find(s.fragment)->second;
+			const GameIndex &g = f.games[s.game];
+			BatchRecord &r = slot.h[b];
+			r.blob = f.d_blob;
+			r.sample_off = g.sample_off[s.sample];
+			r.moves_off = g.moves_off;
+			r.n_moves = g.n_moves;
+			r.outcome = g.outcome;
+			r.augmentation = s.augmentation;
+			r.pad = 0;
+		}
+		// the waves of two launches share the spill areas: launches on one stream follow each other anyway, a launch on ANOTHER stream
+		// is ordered behind the previous one on the device (no host wait)
+		if (d->launched && d->last_stream != stream)
+			AGX_HIP_CHECK(hipStreamWaitEvent(stream, d->last_done, 0));
+		AGX_HIP_CHECK(hipMemcpyAsync(slot.d, slot.h, sizeof(BatchRecord) * n, hipMemcpyHostToDevice, stream));
+		return AGX_OK;
+	}
+	/* ... and the launch that reads them is on its way */
+	int mark_launched(AgxDataset *d, RecordSlot &slot, hipStream_t stream)
+	{
+		AGX_HIP_CHECK(hipGetLastError());
+		AGX_HIP_CHECK(hipEventRecord(slot.done, stream));
+		slot.in_flight = true;
+		d->launched = true;
+		d->last_stream = stream;
+		d->last_done = slot.done;
+		return AGX_OK;
+	}
 	void fill_shape(AgxTensorShape *t, std::initializer_list<int> dims)
 	{
 		if (t == nullptr)
@@ -963,59 +1068,20 @@ int agx_dataset_load_batch_ex(AgxDataset *d, int n, const AgxDatasetSample *h_sa
 	st = prepare_device(d);
 	if (st != AGX_OK)
 		return st;
-	for (Fragment *f : used)
-		if (f->d_blob == nullptr)
-		{ // once per fragment (a blocking copy out of pageable memory)
-			AGX_HIP_CHECK(hipMalloc(&f->d_blob, std::max<size_t>(f->blob.size(), 1)));
-			AGX_HIP_CHECK(hipMemcpy(f->d_blob, f->blob.data(), f->blob.size(), hipMemcpyHostToDevice));
-		}
-	RecordSlot &slot = d->slots[d->next_slot];
-	d->next_slot = (d->next_slot + 1) % RING;
-	if (slot.in_flight)
-	{ // the launch that read this slot RING batches ago: the only thing a call ever waits for
-		AGX_HIP_CHECK(hipEventSynchronize(slot.done));
-		slot.in_flight = false;
-	}
+	RecordSlot *taken = nullptr;
+	st = take_record_slot(d, used, &taken);
+	if (st != AGX_OK)
+		return st;
+	RecordSlot &slot = *taken;
 	if (*d->h_error != 0)
 	{ // left by a sample of an earlier batch (the kernel's note on ERR_FRAMES)
 		const int b = *d->h_error - 1;
 		*d->h_error = 0;
 		AGX_REQUIRE(false, AGX_ERR_STATE, "agx_dataset_load_batch: sample %d of an earlier batch nests renju 3x3 forks deeper than the foul test follows: its features are invalid", b);
 	}
-	if (slot.capacity < n)
-	{ // a larger batch than this slot has seen: new buffers (an allocation, which the runtime may serialise with the device's work); the
-	  // old ones are not freed here, which would synchronise the device, but with the dataset
-		if (slot.h != nullptr)
-			d->retired_host.push_back(slot.h);
-		if (slot.d != nullptr)
-			d->retired_device.push_back(slot.d);
-		slot.h = nullptr;
-		slot.d = nullptr;
-		slot.capacity = 0;
-		const int capacity = std::max(n, 1024);
-		AGX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&slot.h), sizeof(BatchRecord) * capacity, hipHostMallocDefault));
-		AGX_HIP_CHECK(hipMalloc(&slot.d, sizeof(BatchRecord) * capacity));
-		slot.capacity = capacity;
-	}
-	for (int b = 0; b < n; b++)
-	{
-		const AgxDatasetSample &s = h_samples[b];
-		const Fragment &f = *d->fragments.find(s.fragment)->second;
-		const GameIndex &g = f.games[s.game];
-		BatchRecord &r = slot.h[b];
-		r.blob = f.d_blob;
-		r.sample_off = g.sample_off[s.sample];
-		r.moves_off = g.moves_off;
-		r.n_moves = g.n_moves;
-		r.outcome = g.outcome;
-		r.augmentation = s.augmentation;
-		r.pad = 0;
-	}
-	// the waves of two launches share the spill areas: launches on one stream follow each other anyway, a launch on ANOTHER stream
-	// is ordered behind the previous one on the device (no host wait)
-	if (d->launched && d->last_stream != stream)
-		AGX_HIP_CHECK(hipStreamWaitEvent(stream, d->last_done, 0));
-	AGX_HIP_CHECK(hipMemcpyAsync(slot.d, slot.h, sizeof(BatchRecord) * n, hipMemcpyHostToDevice, stream));
+	st = send_records(d, slot, n, h_samples, stream);
+	if (st != AGX_OK)
+		return st;
 	agx::EngineDev E;
 	std::memset(&E, 0, sizeof(E));
 	E.rules = d->rules;
@@ -1062,13 +1128,7 @@ int agx_dataset_load_batch_ex(AgxDataset *d, int n, const AgxDatasetSample *h_sa
 				hipLaunchKernelGGL((agx::k_training_batch<agx::MAXN, agx::TARGETS_PLAIN>), dim3(waves), dim3(64), 0, stream, E, A);
 			break;
 	}
-	AGX_HIP_CHECK(hipGetLastError());
-	AGX_HIP_CHECK(hipEventRecord(slot.done, stream));
-	slot.in_flight = true;
-	d->launched = true;
-	d->last_stream = stream;
-	d->last_done = slot.done;
-	return AGX_OK;
+	return mark_launched(d, slot, stream);
 }
 
 int agx_dataset_load_batch_host(AgxDataset *d, int n, const AgxDatasetSample *h_samples, void *h_input, uint32_t *h_features, float *h_policy, float *h_value,
@@ -1142,6 +1202,181 @@ int agx_dataset_load_batch_host_ex(AgxDataset *d, int n, const AgxDatasetSample 
 		AGX_REQUIRE(failed == 0, AGX_ERR_STATE, "agx_dataset_load_batch_host: a sample (index %d of this or an earlier batch) nests renju 3x3 forks deeper than the foul test follows: its features are invalid",
 				failed - 1);
 	}
+	return AGX_OK;
+}
+
+int agx_dataset_positions(AgxDataset *d, int n, const AgxDatasetSample *h_samples, uint8_t *d_boards, uint8_t *d_signs, void *stream_)
+{
+	AGX_REQUIRE(d != nullptr && n >= 0 && (h_samples != nullptr || n == 0), AGX_ERR_INVALID, "agx_dataset_positions: null argument or a negative count");
+	AGX_REQUIRE(n == 0 || (d_boards != nullptr && d_signs != nullptr), AGX_ERR_INVALID, "agx_dataset_positions: null boards or signs");
+	std::lock_guard<std::mutex> lock(d->mutex);
+	std::vector<Fragment*> used;
+	std::vector<AgxDatasetSample> plain(h_samples, h_samples + n);
+	for (AgxDatasetSample &s : plain)
+		s.augmentation = 0; // (ignored: a position has no orientation of its own)
+	int st = resolve(d, n, plain.data(), &used);
+	if (st != AGX_OK || n == 0)
+		return st;
+	hipStream_t stream = static_cast<hipStream_t>(stream_);
+	st = prepare_device(d);
+	if (st != AGX_OK)
+		return st;
+	RecordSlot *slot = nullptr;
+	st = take_record_slot(d, used, &slot);
+	if (st == AGX_OK)
+		st = send_records(d, *slot, n, plain.data(), stream);
+	if (st != AGX_OK)
+		return st;
+	hipLaunchKernelGGL(agx::k_dataset_positions, dim3(std::min(n, MAX_WAVES)), dim3(64), 0, stream, slot->d, n, d->rows, d->rows * d->cols, d_boards, d_signs);
+	return mark_launched(d, *slot, stream);
+}
+
+namespace
+{
+	struct ReanalyseScratch
+	{ // what one pass allocates, freed on every way out
+			uint8_t *d_bytes = nullptr;  // boards | signs | sample bytes
+			int32_t *d_words = nullptr;  // serials | sizes | status | info
+			uint8_t *h_bytes = nullptr;  // pinned: sample bytes
+			int32_t *h_words = nullptr;  // pinned: serials | sizes | status | info
+			~ReanalyseScratch()
+			{
+				if (d_bytes != nullptr)
+					(void) hipFree(d_bytes);
+				if (d_words != nullptr)
+					(void) hipFree(d_words);
+				if (h_bytes != nullptr)
+					(void) hipHostFree(h_bytes);
+				if (h_words != nullptr)
+					(void) hipHostFree(h_words);
+			}
+	};
+}
+
+int agx_dataset_reanalyse(AgxDataset *d, int fragment, AgxPositionSearcher *searcher, AgxNet *net, AgxGameBuffer *out, const AgxReanalyseOptions *options,
+		AgxReanalyseStats *stats, void *stream_)
+{
+	const char *who = "agx_dataset_reanalyse";
+	AGX_REQUIRE(d != nullptr && searcher != nullptr && net != nullptr && out != nullptr, AGX_ERR_INVALID, "%s: null argument", who);
+	const AgxReanalyseOptions opt = (options != nullptr) ? *options : AgxReanalyseOptions { 0, 0, 0 };
+	AGX_REQUIRE(opt.chunk >= 0, AGX_ERR_INVALID, "%s: a chunk of %d positions", who, opt.chunk);
+	int s_rules = 0, s_size = 0, s_slots = 0, o_rules = 0, o_rows = 0, o_cols = 0;
+	int st = agx::position_searcher_describe(searcher, &s_rules, &s_size, &s_slots);
+	if (st == AGX_OK)
+		st = agx_game_buffer_config(out, &o_rules, &o_rows, &o_cols, nullptr);
+	if (st != AGX_OK)
+		return st;
+	AGX_REQUIRE(s_rules == d->rules && s_size == d->rows && s_size == d->cols, AGX_ERR_INVALID, "%s: the searcher plays rules %d on %dx%d, the dataset rules %d on %dx%d", who,
+			s_rules, s_size, s_size, d->rules, d->rows, d->cols);
+	AGX_REQUIRE(o_rules == d->rules && o_rows == d->rows && o_cols == d->cols, AGX_ERR_INVALID, "%s: the output buffer holds rules %d on %dx%d, the dataset rules %d on %dx%d", who,
+			o_rules, o_rows, o_cols, d->rules, d->rows, d->cols);
+	// the work list: the samples of the fragment in (game, sample) order
+	std::vector<AgxDatasetSample> list;
+	std::vector<int> game_samples;
+	{
+		std::lock_guard<std::mutex> lock(d->mutex);
+		auto it = d->fragments.find(fragment);
+		AGX_REQUIRE(it != d->fragments.end(), AGX_ERR_INVALID, "%s: fragment %d is not loaded", who, fragment);
+		const Fragment &f = *it->second;
+		for (size_t g = 0; g < f.games.size(); g++)
+		{
+			game_samples.push_back(static_cast<int>(f.games[g].sample_off.size()));
+			for (size_t k = 0; k < f.games[g].sample_off.size(); k++)
+				list.push_back(AgxDatasetSample { fragment, static_cast<int>(g), static_cast<int>(k), 0 });
+		}
+	}
+	AgxReanalyseStats total;
+	std::memset(&total, 0, sizeof(total));
+	if (stats != nullptr)
+		*stats = total;
+	if (list.empty())
+		return AGX_OK;
+	hipStream_t stream = static_cast<hipStream_t>(stream_);
+	const size_t hw = static_cast<size_t>(d->rows) * d->cols;
+	const size_t stride = (agx::v201::HEADER_BYTES + agx::v201::ENTRY_BYTES * hw + 3) / 4 * 4;
+	const size_t chunk = std::min<size_t>(list.size(), (opt.chunk > 0) ? opt.chunk : 16384);
+	const size_t signs_at = chunk * hw, bytes_at = (signs_at + chunk + 255) / 256 * 256;
+	ReanalyseScratch m;
+	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m.d_bytes), bytes_at + chunk * stride));
+	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m.d_words), chunk * 7 * sizeof(int32_t)));
+	AGX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m.h_bytes), chunk * stride, hipHostMallocDefault));
+	AGX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m.h_words), chunk * 7 * sizeof(int32_t), hipHostMallocDefault));
+	AgxPositionSearchOutputs outputs;
+	std::memset(&outputs, 0, sizeof(outputs));
+	outputs.status = m.d_words + 2 * chunk;
+	outputs.info = m.d_words + 3 * chunk;
+	const AgxPositionSampleSink sink = { m.d_bytes + bytes_at, static_cast<int>(stride), m.d_words + chunk };
+	// the game whose samples are coming in (the list is in game order: one game is open at a time)
+	size_t game = 0;
+	std::vector<std::vector<uint8_t>> fresh;
+	std::vector<const uint8_t*> pointers;
+	std::vector<int32_t> sizes;
+	for (size_t j0 = 0; j0 < list.size(); j0 += chunk)
+	{
+		const int count = static_cast<int>(std::min(chunk, list.size() - j0));
+		st = agx_dataset_positions(d, count, list.data() + j0, m.d_bytes, m.d_bytes + signs_at, stream_);
+		if (st != AGX_OK)
+			return st;
+		for (int i = 0; i < count; i++)
+			m.h_words[i] = static_cast<int32_t>(static_cast<uint32_t>(opt.serial_base) + static_cast<uint32_t>(j0 + i));
+		AGX_HIP_CHECK(hipMemcpyAsync(m.d_words, m.h_words, count * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+		st = agx_position_searcher_search_ex(searcher, net, count, m.d_bytes, m.d_bytes + signs_at, m.d_words, &outputs, &sink, 0, opt.max_steps, stream_);
+		if (st != AGX_OK)
+			return st;
+		// sizes | status | info in one copy, then the used part of every sample's stride in one more
+		AGX_HIP_CHECK(hipMemcpyAsync(m.h_words + chunk, m.d_words + chunk, chunk * 6 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+		AGX_HIP_CHECK(hipStreamSynchronize(stream));
+		const int32_t *h_sizes = m.h_words + chunk, *h_status = m.h_words + 2 * chunk, *h_info = m.h_words + 3 * chunk;
+		size_t used = 0;
+		for (int i = 0; i < count; i++)
+		{
+			AGX_REQUIRE(h_sizes[i] >= 0 && static_cast<size_t>(h_sizes[i]) <= stride && h_status[i] >= 0 && h_status[i] <= 3, AGX_ERR_STATE,
+					"%s: position %zu came back with %d bytes and status %d", who, j0 + i, h_sizes[i], h_status[i]);
+			if (h_status[i] == 0)
+				used = std::max(used, static_cast<size_t>(h_sizes[i]));
+		}
+		if (used > 0)
+		{
+			AGX_HIP_CHECK(hipMemcpy2DAsync(m.h_bytes, stride, sink.d_bytes, stride, used, count, hipMemcpyDeviceToHost, stream));
+			AGX_HIP_CHECK(hipStreamSynchronize(stream));
+		}
+		for (int i = 0; i < count; i++)
+		{
+			const bool replace = (h_status[i] == 0 && h_sizes[i] > 0); // a truncated search is no training target
+			total.samples++;
+			total.status[h_status[i]]++;
+			total.steps += h_info[4 * i + 2];
+			(replace ? total.replaced : total.kept)++;
+			fresh.emplace_back();
+			if (replace)
+				fresh.back().assign(m.h_bytes + i * stride, m.h_bytes + i * stride + h_sizes[i]);
+			if (static_cast<int>(fresh.size()) < game_samples[game])
+				continue;
+			pointers.clear();
+			sizes.clear();
+			for (const std::vector<uint8_t> &s : fresh)
+			{
+				pointers.push_back(s.data());
+				sizes.push_back(static_cast<int32_t>(s.size()));
+			}
+			{
+				std::lock_guard<std::mutex> lock(d->mutex);
+				auto it = d->fragments.find(fragment);
+				AGX_REQUIRE(it != d->fragments.end() && game < it->second->games.size() && static_cast<int>(it->second->games[game].sample_off.size()) == game_samples[game],
+						AGX_ERR_STATE, "%s: fragment %d was unloaded or replaced during the pass", who, fragment);
+				const GameIndex &g = it->second->games[game];
+				const size_t begin = g.sample_off[0] - 4, end = g.moves_off + 2 * static_cast<size_t>(g.n_moves) + 12;
+				st = agx_game_buffer_add_reanalysed(out, it->second->blob.data() + begin, end - begin, game_samples[game], pointers.data(), sizes.data());
+			}
+			if (st != AGX_OK)
+				return st;
+			total.games++;
+			fresh.clear();
+			game++;
+		}
+	}
+	if (stats != nullptr)
+		*stats = total;
 	return AGX_OK;
 }
 

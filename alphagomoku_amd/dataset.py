@@ -171,6 +171,57 @@ class TrainingDataset:
                                            1 if q_weights else 0, ctypes.byref(out), stream))
         return score_dict(out)
 
+    def positions(self, samples, *, torch_tensors=None, stream=None):
+        """The positions of `samples` ([n, 4] or [n, 3]: fragment, game, sample; an augmentation is ignored) as PositionSearcher takes them:
+        (boards [n, rows * cols] uint8 with 0 empty / 1 cross / 2 circle, signs [n] uint8: 1 cross / 2 circle to move), scattered on the
+        device from the fragment's resident bytes.  When torch shares the library's HIP runtime (torch_tensors=None: decided by that) the
+        two are device torch tensors and the launch goes on torch.cuda.current_stream(), nothing synchronised; otherwise numpy arrays
+        after a round trip on `stream`."""
+        rec = np.asarray(samples, dtype=np.int32)
+        if rec.ndim == 2 and rec.shape[1] == 3:
+            rec = np.concatenate([rec, np.zeros((rec.shape[0], 1), np.int32)], axis=1)
+        rec = self._records(rec)
+        n, cells = rec.shape[0], self.rows * self.cols
+        if torch_tensors is None:
+            torch_tensors = _lib.torch_shares_hip_runtime()
+        if torch_tensors:
+            if not _lib.torch_shares_hip_runtime():
+                raise AgxError("this torch carries a HIP runtime of its own: call alphagomoku_amd._lib.share_torch_hip_runtime() before the library is "
+                               "first used in this process, or ask for numpy arrays (torch_tensors=False)")
+            import torch
+            dev = torch.device("cuda", torch.cuda.current_device())
+            boards, signs = torch.empty((n, cells), dtype=torch.uint8, device=dev), torch.empty((n,), dtype=torch.uint8, device=dev)
+            if stream is None:
+                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            check(lib.agx_dataset_positions(self._h, n, rec.ctypes.data_as(ctypes.c_void_p), boards.data_ptr(), signs.data_ptr(), stream))
+            return boards, signs
+        from .networks import DeviceBuffer
+        d_boards, d_signs = DeviceBuffer(max(n * cells, 1)), DeviceBuffer(max(n, 1))
+        try:
+            check(lib.agx_dataset_positions(self._h, n, rec.ctypes.data_as(ctypes.c_void_p), d_boards.ptr, d_signs.ptr, stream))
+            check(lib.agx_stream_synchronize(stream))
+            if n == 0:
+                return np.zeros((0, cells), np.uint8), np.zeros((0,), np.uint8)
+            return d_boards.download((n, cells), np.uint8), d_signs.download((n,), np.uint8)
+        finally:
+            d_boards.free()
+            d_signs.free()
+
+    def reanalyse(self, searcher, net, fragment=0, out=None, chunk=0, serial_base=0, max_steps=None, stream=None):
+        """The samples of `fragment` searched again with `net` by `searcher` (search.PositionSearcher of the same rules and board): returns
+        (GameBuffer, stats) — the same games, moves and outcomes, every sample whose search ended by the move rule (status 0) replaced by
+        the fresh root's format-201 bytes, the others kept as they were.  `chunk` positions per searcher job (0 = 16384); position j of
+        the pass, in (game, sample) order, is searched with serial serial_base + j.  The result depends neither on chunk nor on the
+        searcher's slot count.  out: a GameBuffer to append to (default: a new one).  stats: games, samples, replaced, kept, status
+        (samples per status word 0..3), steps."""
+        from .selfplay import GameBuffer
+        if out is None:
+            out = GameBuffer(self.rules, self.rows, self.cols)
+        options = _lib.AgxReanalyseOptions(int(chunk), int(serial_base), 0 if max_steps is None else int(max_steps))
+        stats = _lib.AgxReanalyseStats()
+        check(lib.agx_dataset_reanalyse(self._h, int(fragment), searcher.handle, net._net, out._h, ctypes.byref(options), ctypes.byref(stats), stream))
+        return out, dict(games=stats.games, samples=stats.samples, replaced=stats.replaced, kept=stats.kept, status=list(stats.status), steps=stats.steps)
+
     def sample(self, batch_size, generator):
         """BaseSampler::pick_sample (torch_api.cpp:46-77) batch_size times: the games in a shuffled order, of every game one random
         sample under one random symmetry; when every game has been visited the order is shuffled again.  generator: a

@@ -73,7 +73,14 @@ class PositionSearcher:
             raise ValueError("serials [n] expected")
         return n
 
-    def _torch_job(self, boards, signs, serials, max_pv, stream, out):
+    def _sample_shapes(self):
+        """the sample sink's two arrays behind [n]: sample [stride] uint8 (the format-201 bytes), sample_bytes int32 (how many of them)"""
+        return dict(sample=((_lib.sample_stride(self.board_size * self.board_size),), np.uint8), sample_bytes=((), np.int32))
+
+    def _sink(self, sample, sample_bytes):
+        return _lib.AgxPositionSampleSink(sample, _lib.sample_stride(self.board_size * self.board_size), sample_bytes)
+
+    def _torch_job(self, boards, signs, serials, max_pv, stream, out, samples=False):
         import torch
         if not _lib.torch_shares_hip_runtime():
             raise _lib.AgxError("this torch carries a HIP runtime of its own: call alphagomoku_amd._lib.share_torch_hip_runtime() before the "
@@ -82,7 +89,10 @@ class PositionSearcher:
             raise ValueError("boards and signs are uint8 tensors, serials an int32 tensor")
         n = int(boards.shape[0])
         shapes = self._shapes(max_pv)
-        kinds = {np.uint16: torch.int16, np.int16: torch.int16, np.int32: torch.int32, np.float32: torch.float32}
+        kinds = {np.uint16: torch.int16, np.int16: torch.int16, np.int32: torch.int32, np.float32: torch.float32, np.uint8: torch.uint8}
+        given = out is not None
+        if samples:
+            shapes.update(self._sample_shapes())
         if stream is None:
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         if out is None:
@@ -91,8 +101,14 @@ class PositionSearcher:
         for k, t in out.items():
             if k not in shapes or tuple(t.shape) != (n,) + shapes[k][0] or t.dtype != kinds[shapes[k][1]]:
                 raise ValueError("output '%s' has no place in this call, or another shape or dtype than the call writes" % k)
-            setattr(c_out, k, _address(t))
-        return c_out, out, stream
+            if k not in ("sample", "sample_bytes"):
+                setattr(c_out, k, _address(t))
+        sink = None
+        if samples:
+            if given and ("sample" not in out or "sample_bytes" not in out):
+                raise ValueError("with samples=True the dict `out` must hold 'sample' and 'sample_bytes'")
+            sink = self._sink(_address(out["sample"]), _address(out["sample_bytes"]))
+        return c_out, out, stream, sink
 
     def _free_staged(self):
         if self._staged is not None:
@@ -100,9 +116,11 @@ class PositionSearcher:
                 buf.free()
             self._staged = None
 
-    def _numpy_job(self, boards, signs, serials, max_pv):
+    def _numpy_job(self, boards, signs, serials, max_pv, samples=False):
         n = int(boards.shape[0])
         shapes = self._shapes(max_pv)
+        if samples:
+            shapes.update(self._sample_shapes())
         self._free_staged()
         b = np.ascontiguousarray(boards, dtype=np.uint8)
         s = np.ascontiguousarray(signs, dtype=np.uint8)
@@ -121,10 +139,12 @@ class PositionSearcher:
             d_serials.upload(r)
         c_out = _lib.AgxPositionSearchOutputs()
         for k, buf in outs.items():
-            setattr(c_out, k, buf.ptr)
-        return c_out, d_boards.ptr, d_signs.ptr, (d_serials.ptr if d_serials is not None else None)
+            if k not in ("sample", "sample_bytes"):
+                setattr(c_out, k, buf.ptr)
+        sink = self._sink(outs["sample"].ptr, outs["sample_bytes"].ptr) if samples else None
+        return c_out, d_boards.ptr, d_signs.ptr, (d_serials.ptr if d_serials is not None else None), sink
 
-    def search(self, boards, signs, net, serials=None, max_pv=8, max_steps=None, stream=None, out=None):
+    def search(self, boards, signs, net, serials=None, max_pv=8, max_steps=None, stream=None, out=None, samples=False):
         """boards [n, size, size] (or [n, size * size]) uint8 with 0 empty / 1 cross / 2 circle, signs [n] uint8 (1 cross / 2 circle to move),
         serials [n] int32 or None (all 0), net an AGNetwork -> dict of status [n] int32 (0 searched, 1 bad input, 2 engine error, 3 step
         limit), root [n, 4] int32 (visits, score bits, flags, edges), root_value [n, 2], best_move [n] uint16, the dense per-cell rows visits
@@ -134,34 +154,38 @@ class PositionSearcher:
         launches go on torch.cuda.current_stream() unless `stream` names one (the library must share torch's HIP runtime, as for
         PositionSolver.solve), the outputs named in the dict `out` are written where they lie (without `out` torch allocates all of them;
         torch has no unsigned 16-bit arithmetic, so best_move, score and pv are int16 tensors holding the same bits).  Either way the call
-        returns with the stream drained."""
+        returns with the stream drained.  samples=True adds sample [n, stride] uint8 and sample_bytes [n] int32: the root of every position
+        as the reference's format-201 sample (the bytes a self-play game started from the position would record for its first move),
+        sample[i][:sample_bytes[i]]; 0 bytes where there is no root (status 1, 2, or 3 before the first expansion)."""
         n = self._check_inputs(boards, signs, serials)
         steps = 0 if max_steps is None else int(max_steps)
         if hasattr(boards, "data_ptr"):
-            c_out, out, stream = self._torch_job(boards, signs, serials, max_pv, stream, out)
-            check(lib.agx_position_searcher_search(self._searcher, net._net, n, _address(boards), _address(signs), _address(serials), ctypes.byref(c_out),
-                                                   int(max_pv), steps, stream))
+            c_out, out, stream, sink = self._torch_job(boards, signs, serials, max_pv, stream, out, samples)
+            check(lib.agx_position_searcher_search_ex(self._searcher, net._net, n, _address(boards), _address(signs), _address(serials), ctypes.byref(c_out),
+                                                      sink, int(max_pv), steps, stream))
             return out
-        c_out, d_boards, d_signs, d_serials = self._numpy_job(boards, signs, serials, max_pv)
+        c_out, d_boards, d_signs, d_serials, sink = self._numpy_job(boards, signs, serials, max_pv, samples)
         try:
-            check(lib.agx_position_searcher_search(self._searcher, net._net, n, d_boards, d_signs, d_serials, ctypes.byref(c_out), int(max_pv), steps, stream))
+            check(lib.agx_position_searcher_search_ex(self._searcher, net._net, n, d_boards, d_signs, d_serials, ctypes.byref(c_out), sink, int(max_pv), steps,
+                                                      stream))
             return self.results(stream)
         finally:
             self._free_staged()
 
     # ---- staged stepping: a caller with an evaluator of its own (and the tests) ----
-    def begin(self, boards, signs, serials=None, max_pv=8, max_steps=None, stream=None, out=None):
+    def begin(self, boards, signs, serials=None, max_pv=8, max_steps=None, stream=None, out=None, samples=False):
         """records the job and loads the first positions.  Torch device tensors: returns the dict of output tensors (as search); numpy
-        arrays: the job is staged in device buffers the searcher keeps, results() downloads the outputs once finished() == n."""
+        arrays: the job is staged in device buffers the searcher keeps, results() downloads the outputs once finished() == n.
+        samples=True: the format-201 samples too, as in search."""
         n = self._check_inputs(boards, signs, serials)
         steps = 0 if max_steps is None else int(max_steps)
         if hasattr(boards, "data_ptr"):
-            c_out, out, stream = self._torch_job(boards, signs, serials, max_pv, stream, out)
-            check(lib.agx_position_searcher_begin(self._searcher, n, _address(boards), _address(signs), _address(serials), ctypes.byref(c_out),
-                                                  int(max_pv), steps, stream))
+            c_out, out, stream, sink = self._torch_job(boards, signs, serials, max_pv, stream, out, samples)
+            check(lib.agx_position_searcher_begin_ex(self._searcher, n, _address(boards), _address(signs), _address(serials), ctypes.byref(c_out), sink,
+                                                     int(max_pv), steps, stream))
             return out
-        c_out, d_boards, d_signs, d_serials = self._numpy_job(boards, signs, serials, max_pv)
-        check(lib.agx_position_searcher_begin(self._searcher, n, d_boards, d_signs, d_serials, ctypes.byref(c_out), int(max_pv), steps, stream))
+        c_out, d_boards, d_signs, d_serials, sink = self._numpy_job(boards, signs, serials, max_pv, samples)
+        check(lib.agx_position_searcher_begin_ex(self._searcher, n, d_boards, d_signs, d_serials, ctypes.byref(c_out), sink, int(max_pv), steps, stream))
         return None
 
     def results(self, stream=None):

@@ -469,6 +469,20 @@ class GameBuffer:
     def save(self, path, compress=True):
         check(lib.agx_game_buffer_save(self._h, str(path).encode(), 1 if compress else 0))
 
+    def load(self, path):
+        """appends the games of a file written by save"""
+        check(lib.agx_game_buffer_load(self._h, str(path).encode()))
+
+    def add_reanalysed(self, game, samples):
+        """appends `game` (GameDataStorage bytes, uint8) with sample k replaced by samples[k] (uint8 bytes of a format-201 sample; None or
+        empty: the old sample stays); moves, outcome and board size are kept"""
+        game = np.ascontiguousarray(game, dtype=np.uint8)
+        kept = [np.ascontiguousarray(s if s is not None else [], dtype=np.uint8) for s in samples]
+        pointers = (ctypes.c_void_p * max(len(kept), 1))(*[s.ctypes.data if s.size else None for s in kept])
+        sizes = np.array([s.size for s in kept], np.int32)
+        check(lib.agx_game_buffer_add_reanalysed(self._h, game.ctypes.data_as(ctypes.c_void_p), game.size, len(kept), pointers,
+                                                 sizes.ctypes.data_as(ctypes.c_void_p)))
+
     def close(self):
         if self._h:
             lib.agx_game_buffer_destroy(self._h)

@@ -1042,6 +1042,62 @@ int agx_position_searcher_search(AgxPositionSearcher* ps, AgxNet* net, int n, co
 		const int32_t* d_serials, const AgxPositionSearchOutputs* out, int max_pv, int max_steps, void* stream);
 /* Calls on one searcher share its pool: a call on another stream than the previous one is ordered behind it on the device. */
 
+/* Format-201 samples out of the searcher: the harvest stage quantises the root of position i to the reference's SearchDataStorage_v201
+ * bytes (csrc/sample_v201.hpp) at d_bytes + i * stride — exactly what the first move record of a self-play game that started from the
+ * position would carry: the three scales from the maxima over the root's edges, the root's score, move number = stones on the board, the
+ * root's flags, the entry count, then 6 bytes per kept cell in cell order (an edge with visits or a proven score; and any cell 255 or more
+ * cells past the previous entry) — and the byte count into d_sizes[i].  Status 0 and status 3 with a root write the sample of the root as
+ * it stands; status 1, 2 and 3 without a root write size 0 and leave the bytes alone.  stride >= 16 + 6 * cells, a multiple of 4
+ * (AGX_ERR_INVALID otherwise); a NULL sink, or one with either pointer NULL, means no samples: the calls are then the ones above. */
+typedef struct AgxPositionSampleSink
+{ /* device addresses */
+	uint8_t* d_bytes;  /* [n][stride] */
+	int stride;
+	int32_t* d_sizes;  /* [n] */
+} AgxPositionSampleSink;
+int agx_position_searcher_begin_ex(AgxPositionSearcher* ps, int n, const uint8_t* d_boards, const uint8_t* d_signs, const int32_t* d_serials,
+		const AgxPositionSearchOutputs* out, const AgxPositionSampleSink* sink, int max_pv, int max_steps, void* stream);
+int agx_position_searcher_search_ex(AgxPositionSearcher* ps, AgxNet* net, int n, const uint8_t* d_boards, const uint8_t* d_signs,
+		const int32_t* d_serials, const AgxPositionSearchOutputs* out, const AgxPositionSampleSink* sink, int max_pv, int max_steps, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Saved games reanalysed on the device: the positions of a fragment's samples searched again with the current network, a buffer of the
+ * same games with fresh policy / action-value / score targets (csrc/training_batch.hip: k_dataset_positions; the sink above;
+ * csrc/game_buffer.cpp).  Moves and outcome stay the game's.
+ * ---------------------------------------------------------------------------------------------- */
+/* The positions of n samples (fragment, game, sample; the augmentation is ignored) as the searcher takes them: d_boards uint8[n][cells]
+ * (0 / 1 / 2, row-major: the game's first move_number moves), d_signs uint8[n] (the colour of move move_number).  One launch on `stream`,
+ * one wavefront per sample, on the fragment bytes resident on the device; indices are validated first, as by agx_dataset_load_batch. */
+int agx_dataset_positions(AgxDataset* dataset, int n, const AgxDatasetSample* h_samples, uint8_t* d_boards, uint8_t* d_signs, void* stream);
+/* Appends the format-201 game h_game[size] to `out` with sample k replaced by h_samples[k][0 .. h_sizes[k]) where h_sizes[k] > 0 (the old
+ * bytes stay where it is 0); move list, outcome, rows and cols are kept.  Host code only.  AGX_ERR_INVALID: a truncated game, n_samples
+ * other than the game's count, a replacement that is no whole sample or whose move number differs from the old sample's, a game of another
+ * board than the buffer's. */
+int agx_game_buffer_add_reanalysed(AgxGameBuffer* out, const uint8_t* h_game, size_t size, int n_samples, const uint8_t* const* h_samples,
+		const int32_t* h_sizes);
+
+typedef struct AgxReanalyseOptions
+{
+	int chunk;        /* positions per searcher job; 0 = 16384 */
+	int serial_base;  /* position j of the pass (samples in (game, sample) order) is searched with serial serial_base + j */
+	int max_steps;    /* as agx_position_searcher_begin; <= 0: its default */
+} AgxReanalyseOptions;
+typedef struct AgxReanalyseStats
+{
+	int64_t games, samples;
+	int64_t replaced;     /* samples with status 0: their bytes are the fresh search's */
+	int64_t kept;         /* every other sample: the old bytes (a truncated search is no training target) */
+	int64_t status[4];    /* samples per AGX_POSSEARCH_STATUS_* (0 = searched) */
+	int64_t steps;        /* sum over the samples of the steps their slot spent on them */
+} AgxReanalyseStats;
+/* The whole pass over one fragment: `chunk` positions at a time agx_dataset_positions, agx_position_searcher_search_ex with a sink, one
+ * copy of sizes, status words, step counts and the used sample bytes into pinned memory; a game is handed to
+ * agx_game_buffer_add_reanalysed once all its samples are in.  The result does not depend on `chunk` or on the searcher's slot count.
+ * `options` NULL: all defaults; `stats` may be NULL.  AGX_ERR_INVALID before anything is launched: a null argument, a fragment that is
+ * not loaded, rules or board size of dataset, searcher and `out` that differ.  The call waits for `stream`. */
+int agx_dataset_reanalyse(AgxDataset* dataset, int fragment, AgxPositionSearcher* searcher, AgxNet* net, AgxGameBuffer* out,
+		const AgxReanalyseOptions* options, AgxReanalyseStats* stats, void* stream);
+
 /* Raw device-memory helpers so that non-HIP hosts (ctypes, cgo) can stage buffers. */
 int agx_malloc(void** d_ptr, size_t bytes);
 int agx_free(void* d_ptr);

@@ -640,6 +640,20 @@ namespace agx
 						stream));
 				return result;
 			}
+			/* the positions of the samples as PositionSearcher takes them: d_boards uint8[n][rows * cols], d_signs uint8[n]; one launch on `stream` */
+			void positions(const std::vector<AgxDatasetSample> &samples, uint8_t *d_boards, uint8_t *d_signs, void *stream = nullptr)
+			{
+				check(agx_dataset_positions(m_dataset, static_cast<int>(samples.size()), samples.data(), d_boards, d_signs, stream));
+			}
+			/* the samples of `fragment` searched again with `net` (searcher: PositionSearcher::handle()): the same games with fresh samples are
+			 * appended to `out`; waits for `stream` */
+			AgxReanalyseStats reanalyse(int fragment, AgxPositionSearcher *searcher, const AGNetwork &net, AgxGameBuffer *out, const AgxReanalyseOptions &options = { 0, 0, 0 },
+					void *stream = nullptr)
+			{
+				AgxReanalyseStats stats;
+				check(agx_dataset_reanalyse(m_dataset, fragment, searcher, net.handle(), out, &options, &stats, stream));
+				return stats;
+			}
 			AgxDataset* handle() const noexcept
 			{
 				return m_dataset;
@@ -768,6 +782,17 @@ namespace agx
 					int max_steps = 0, void *stream = nullptr)
 			{
 				check(agx_position_searcher_begin(m_searcher, n, d_boards, d_signs, d_serials, &out, max_pv, max_steps, stream));
+			}
+			/* ... with the root of every position as a format-201 sample: sink.d_bytes[i * sink.stride ...], sink.d_sizes[i] bytes of it */
+			void search(const AGNetwork &net, int n, const uint8_t *d_boards, const uint8_t *d_signs, const AgxPositionSearchOutputs &out, const AgxPositionSampleSink &sink,
+					const int32_t *d_serials = nullptr, int max_pv = 8, int max_steps = 0, void *stream = nullptr)
+			{
+				check(agx_position_searcher_search_ex(m_searcher, net.handle(), n, d_boards, d_signs, d_serials, &out, &sink, max_pv, max_steps, stream));
+			}
+			void begin(int n, const uint8_t *d_boards, const uint8_t *d_signs, const AgxPositionSearchOutputs &out, const AgxPositionSampleSink &sink,
+					const int32_t *d_serials = nullptr, int max_pv = 8, int max_steps = 0, void *stream = nullptr)
+			{
+				check(agx_position_searcher_begin_ex(m_searcher, n, d_boards, d_signs, d_serials, &out, &sink, max_pv, max_steps, stream));
 			}
 			void select_solve(void *stream = nullptr)
 			{
