@@ -1,50 +1,70 @@
 /*
- * nn_bottleneck.hip — the bottleneck towers (BottleneckPV / BottleneckPVraw / BottleneckPVQ, networks.cpp:170-361 of the reference) for any
- * board with 5 <= rows, cols <= 20, gfx950 (CDNA4).  A block (createBottleneckBlock_v3, blocks.cpp:84-97) is
+ * nn_any_board_kernel.hpp — the policy/value towers for any board with 5 <= rows, cols <= 20 (rows and cols independent), gfx950 (CDNA4): the residual
+ * networks (ResnetPV / PVraw / PVQ) and the bottleneck networks (BottleneckPV / BottleneckPVraw / BottleneckPVQ, networks.cpp:170-361 of the
+ * reference) in ONE kernel frame with the block as the only seam.
  *
- *     y = relu(W1 . x + b1)   1x1, F -> F/2        y = relu(W2 * y + b2)   3x3, F/2 -> F/2        x = relu(x + W3 * y + b3)   3x3, F/2 -> F
+ * nn_forward.hip carries a kernel per board (15x15, 20x20) with the shape as a template parameter.  This file is the general one: the board
+ * shape is a kernel ARGUMENT (struct Shape), compile-time are the filter count, the block kind and the head / input variants: twelve instantiations.
+ * The kernel template is this ONE text; its instantiations are made in two translation units, one per block kind (nn_any_board.hip: RESIDUAL and
+ * agx_any::launch(); nn_any_board_bottleneck.hip: BOTTLENECK).  In one module hipcc gives the six bottleneck instantiations another instruction
+ * order — the same optimised IR but for the place of one hoisted address — that is 0.4 - 0.8 % slower on 15x15 (profiles/nn_one_frame.txt); alone
+ * in their module they are, instruction for instruction, what they were as a file of their own.
  *
- * between the residual networks' input block and heads.  The kernel is the run-time-shaped one of nn_any_board.hip with another block:
- *
- *   - the board shape is a kernel argument (Shape), compile-time are the filter count and the head / input variants: six instantiations;
- *   - persistent grid, optional slot list with the count read on the device, one 8-wave workgroup carries a board through the whole network in
- *     ONE activation plane in LDS, computed in place: a layer's outputs stay in accumulators until every wave has read the plane;
- *   - plane layout, tiles, XOR chunk swizzle, tap offsets, magic division: nn_any_board.hip's.  The half-width activations keep the full-width
- *     position stride and use the first F/2 channels of a position (chunks 0 .. F/16 - 1 before the swizzle): the halo positions of the 3x3
- *     taps are never written and stay the zeros they are, and the stale upper channels of a position are never read;
- *   - the wave layout follows the OUTPUT width M of a layer (Lay<M>): M / 32 channel groups of two 16-channel tiles, 8 / (M / 32) position
- *     groups.  F = 128: full-width layers 4 x 2 (14 tiles per wave), half-width 2 x 4 (7 tiles); F = 64: 2 x 4 (7 tiles) and 1 x 8 (4 tiles).
- *     Every wave has two MFMAs per activation fragment it reads in every layer, and a half-width layer's accumulators are half the size;
- *   - the block input x waits in the per-workgroup global scratch of the in-place residual towers, in the accumulator layout of the full-width
- *     layers, written and read by the same lane: written by the input block / the third convolution, requested by the second convolution
- *     behind its k-loop, added to the bias when the third one's accumulators start;
- *   - every reduction order is fixed by the shape alone: results do not depend on grid, batch, slot list or launch width.
+ *   - Persistent grid, optional slot list with the count read on the device.  One workgroup (8 waves) carries a board through the whole network in
+ *     ONE activation plane in LDS, computed in place: a layer's outputs stay in accumulators until every wave has read the plane.  The plane is
+ *     sized for the largest board (20x20: 477 positions), so every shape fits.
+ *   - Row stride S = cols + 1, one spare row above and below, the spare column / rows / the last tile's overhang kept at zero: a 3x3 tap is
+ *     the offset dy * S + dx in the flattened position index.  Tiles are 16 consecutive positions; NT = ceil(rows * S / 16) of them.
+ *   - The wave layout follows the OUTPUT width M of a layer (Lay<M>): M / 32 channel groups of two 16-channel tiles, 8 / (M / 32) position groups,
+ *     the tiles dealt to the position groups in runs of ceil(NT / PG).  M = 128: 4 x 2 (14 accumulator tiles per wave), 64: 2 x 4 (7), 32: 1 x 8 (4);
+ *     the accumulators are sized for 20x20, tiles a shape does not have are skipped by wave-uniform branches.
+ *   - The k-loop is tap-major with the activation fragments of all tiles of a wave read per (tap, 32-channel chunk): a tile is 16 positions = a
+ *     whole period of the XOR chunk swizzle, so every LDS address is one per-lane base per tap + an immediate.  Nothing in the loop divides: the
+ *     only run-time divisions by S (cell of a position: the on-board mask, the input conv's plane index) are a multiply and a shift (Shape::magic).
+ *   - The blocks.  RESIDUAL: x = relu(x + W2 * relu(W1 * x + b1) + b2), both 3x3, F -> F.  BOTTLENECK (createBottleneckBlock_v3, blocks.cpp:84-97):
+ *         y = relu(W1 . x + b1)   1x1, F -> F/2        y = relu(W2 * y + b2)   3x3, F/2 -> F/2        x = relu(x + W3 * y + b3)   3x3, F/2 -> F
+ *     The half-width activations keep the full-width position stride and use the first F/2 channels of a position (chunks 0 .. F/16 - 1 before
+ *     the swizzle): the halo positions of the 3x3 taps are never written and stay the zeros they are, the stale upper channels are never read.
+ *   - The block input x waits in a per-workgroup global scratch, in the accumulator layout of the full-width layers, written and read by the same
+ *     lane: written by the input block / a block's last convolution, requested by the layer in front of the last one behind its k-loop, added to
+ *     the bias when the last one's accumulators start.
+ *   - mfma_settle() (nn_device.hpp) stands behind every tile loop.
+ *   - Every reduction order is fixed by the shape alone: results do not depend on grid, batch, slot list or launch width.
  *
  * Numerics: fp16 weights for everything that feeds the matrix cores, fp32 accumulation from the bias (+ the residual), one rounding to fp16
  * per stored activation behind the ReLU, the last 1x1 of policy / q and all biases in fp32, q's hidden activation tanh rounded to fp16.
- * The value head's dense layers run in value_head_kernel behind the tower (agx_res::launch, nn_forward.hip).
+ * The value head's dense layers run in value_head_kernel behind the tower (agx_res::launch, nn_forward.hip), K = 4 * rows * cols padded to 32.
+ * The types, the launch record and the helpers shared with nn_forward.hip are in nn_device.hpp.
+ *
+ * Slower per FLOP than the two specialised kernels (DESIGN.md 3.1 has the measured ratios): no row- or column-stationary reuse of
+ * activation fragments, one fragment read per (tap, tile) for two MFMAs.
  */
+#ifndef AGX_NN_ANY_BOARD_KERNEL_HPP_
+#define AGX_NN_ANY_BOARD_KERNEL_HPP_
+
 #include "nn_device.hpp"
 #include "nn_any_board.hpp"
-#include "nn_bottleneck.hpp"
 
 #include <cmath>
 
 namespace
 {
+	using agx_any::RESIDUAL;
+	using agx_any::BOTTLENECK;
+
 	struct Shape
 	{
 			int rows, cols;
 			int S;        // row stride in positions: cols + 1
 			int NT;       // 16-position tiles of the output: ceil(rows * S / 16)
-			int ntw_f;    // tiles per position group of a full-width layer: ceil(NT / Lay<F>::PG)
-			int ntw_h;    // of a half-width layer: ceil(NT / Lay<F / 2>::PG)
+			int ntw;      // tiles per position group of a full-width layer: ceil(NT / Lay<F>::PG)
+			int ntw_h;    // of a half-width layer: ceil(NT / Lay<F / 2>::PG) (read by the bottleneck instantiations only)
 			int HW;
 			int kpad;     // value-head dense input length (agx_res::Net::kpad()): 4 HW rounded up to 32
 			int plane16;  // 16-byte units of the activation plane: (1 + S + NT * 16 + S + 2) positions
 			int S5;       // row stride of the padded input plane: S + 4
 			int npos5;    // its positions: (rows + 4) * S5 + 4
-			int magic;    // position / S == (position * magic) >> 16 for every position of a plane
+			int magic;    // position / S == (position * magic) >> 16 for every position of a plane (65536 / S + 1: exact below 65536 / S)
 	};
 
 	constexpr int NT_MAX = (agx_any::MAX_SIDE * (agx_any::MAX_SIDE + 1) + 15) / 16; // 27
@@ -87,8 +107,18 @@ namespace
 	};
 	template<int F>
 	constexpr int SKIP_PER_WG = 8 * Lay<F>::MT * Lay<F>::NTW * 64; // half4 elements of residual scratch per workgroup
+	static_assert(Lay<128>::NTW >= Lay<64>::NTW && Lay<64>::NTW >= Lay<32>::NTW,
+			"the residual scratch is sized by the full-width layout: only full-width layers save to it, with either block kind");
 
-	/* what a wave owns in a layer: channels [mg * 32, mg * 32 + 32) of tiles n0 .. n0 + count - 1 (wave-uniform) */
+	/* What the block kind decides beside the block itself, both for the rate alone (profiles/nn_one_frame.txt).  The depth of the weight ring of
+	 * a 3x3 k-loop over K input channels; and whether a layer makes the per-lane part of its addresses its own (own(), nn_device.hpp), where the
+	 * residual instantiations otherwise keep them as kernel-wide constants in scratch. */
+	template<int BLOCK, int K>
+	constexpr int RING = (BLOCK == BOTTLENECK) ? 3 : ((K == 128) ? 4 : 2);
+	template<int BLOCK>
+	constexpr bool OWN = (BLOCK == RESIDUAL);
+
+	/* what a wave owns in a layer: channels [mg * 32, mg * 32 + 32) of tiles n0 .. n0 + count - 1 (wave-uniform, in scalar registers) */
 	struct WaveTiles
 	{
 			int mg, n0, count;
@@ -123,19 +153,6 @@ namespace
 		return bits;
 	}
 
-	/* A wave that leaves a tile loop right behind its last MFMA can read the accumulators too early: 16 wait states, and the
-	 * accumulators tied to a statement behind them. */
-	template<int M, int N>
-	__device__ __forceinline__ void mfma_settle(floatx4 (&acc)[M][N])
-	{
-		asm volatile("s_nop 15");
-#pragma unroll
-		for (int i = 0; i < M; i++)
-#pragma unroll
-			for (int n = 0; n < N; n++)
-				asm volatile("" : "+v"(acc[i][n]));
-	}
-
 	typedef BiasCarry<2> Bias2;
 	template<int M>
 	__device__ __forceinline__ void request_bias(const float *__restrict__ bias, const WaveTiles &wt, int lane, Bias2 &carry)
@@ -144,11 +161,34 @@ namespace
 		for (int i = 0; i < 2; i++)
 			carry.b[i] = *reinterpret_cast<const floatx4*>(bias + (wt.mg * 2 + i) * 16 + 4 * (lane >> 4));
 	}
+	template<int M>
+	__device__ __forceinline__ void start_from_bias(const Bias2 &bias, floatx4 (&acc)[2][Lay<M>::NTW])
+	{
+#pragma unroll
+		for (int i = 0; i < 2; i++)
+#pragma unroll
+			for (int n = 0; n < Lay<M>::NTW; n++)
+				acc[i][n] = bias.b[i];
+	}
 	template<int F>
 	struct SkipCarry
-	{ // the block input in the accumulator layout of a full-width layer, requested by the block's second layer behind its k-loop
+	{ // the block input in the accumulator layout of a full-width layer, requested by the layer in front of the block's last one behind its k-loop
 			uint2 v[2][Lay<F>::NTW];
 	};
+
+	typedef __attribute__((address_space(1))) half4 global_half4;
+	template<int F>
+	__device__ __forceinline__ global_half4* lane_skip(half4 *skip, int wave, int lane)
+	{ // this lane's part of the workgroup's residual scratch [wave][MT][NTW][lane]: scalar base + lane offset (+ immediates)
+		return (global_half4*) (skip + __builtin_amdgcn_readfirstlane(wave * Lay<F>::MT * Lay<F>::NTW * 64)) + lane;
+	}
+
+	/* the same for one layer: with OWN_ADDR the lane's part of the address is made again, the layer's own; without, the kernel-wide pointer serves */
+	template<int F, bool OWN_ADDR>
+	__device__ __forceinline__ global_half4* layer_skip(global_half4 *my_skip, half4 *skip, int wave, int lane)
+	{
+		return OWN_ADDR ? lane_skip<F>(skip, wave, own(lane)) : my_skip;
+	}
 
 	/* one k-step (32 input channels of one tap) for all tiles of a wave: activation fragments in groups of at most 8 tiles, two MFMAs each */
 	template<int F, int NTW>
@@ -181,10 +221,11 @@ namespace
 
 	/*
 	 * acc += the convolution of the first K channels of the plane (F filters: position stride and swizzle) to M channels, TAPS = 9 (3x3,
-	 * tap-major) or 1 (1x1): TAPS * K / 32 k-steps.  3x3: the weight fragments of a k-step are requested two steps ahead through a ring of three
-	 * (3 * K / 32 steps per tap row: the ring index is static in the unrolled row).  1x1: all K / 32 steps' fragments are requested at the top.
+	 * tap-major) or 1 (1x1): TAPS * K / 32 k-steps.  3x3: the weight fragments of a k-step are requested RING - 1 steps ahead through a ring
+	 * (3 * K / 32 steps per tap row, a multiple of RING: the ring index is static in the unrolled row).  1x1: all K / 32 steps' fragments are
+	 * requested at the top.
 	 */
-	template<int F, int K, int M, int TAPS>
+	template<int F, int K, int M, int TAPS, int RING = 1>
 	__device__ __forceinline__ void conv_mac(const char *src, const half8 *__restrict__ wpk, const Shape &sh, const WaveTiles &wt, int lane,
 			floatx4 (&acc)[2][Lay<M>::NTW])
 	{
@@ -213,7 +254,8 @@ namespace
 		}
 		else
 		{
-			constexpr int STEPS = 9 * KC, ROW = 3 * KC, RING = 3;
+			constexpr int STEPS = 9 * KC, ROW = 3 * KC;
+			static_assert(RING >= 2 && ROW % RING == 0, "static ring index inside the unrolled tap row");
 			half8 a_ring[RING][2];
 #pragma unroll
 			for (int u = 0; u < RING - 1; u++)
@@ -248,30 +290,13 @@ namespace
 		mfma_settle(acc);
 	}
 
-	template<int M>
-	__device__ __forceinline__ void start_from_bias(const Bias2 &bias, floatx4 (&acc)[2][Lay<M>::NTW])
-	{
-#pragma unroll
-		for (int i = 0; i < 2; i++)
-#pragma unroll
-			for (int n = 0; n < Lay<M>::NTW; n++)
-				acc[i][n] = bias.b[i];
-	}
-
-	typedef __attribute__((address_space(1))) half4 global_half4;
-	template<int F>
-	__device__ __forceinline__ global_half4* lane_skip(half4 *skip, int wave, int lane)
-	{ // this lane's part of the workgroup's residual scratch [wave][MT][NTW][lane]
-		return (global_half4*) (skip + __builtin_amdgcn_readfirstlane(wave * Lay<F>::MT * Lay<F>::NTW * 64)) + lane;
-	}
-
 	/*
 	 * The epilogue of a block layer with M output channels: ReLU, one rounding to fp16, cells that are not on the board — the spare column, the
 	 * last tile's overhang — masked to zero; with SAVE the values are also the next block's input (scratch); behind the barrier (every wave has
-	 * consumed the plane) the first M channels of the wave's positions are overwritten.  `fetch` (the block's second layer): the block input is
-	 * requested for the third layer while the accumulators are dead.
+	 * consumed the plane) the first M channels of the wave's positions are overwritten.  `fetch` (the layer in front of the block's last one): the
+	 * block input is requested for the last layer while the accumulators are dead, in flight through the barrier and the plane write.
 	 */
-	template<int F, int M, bool SAVE>
+	template<int F, int M, bool SAVE, bool OWN_ADDR>
 	__device__ __forceinline__ void store_relu(char *plane, floatx4 (&acc)[2][Lay<M>::NTW], const Shape &sh, const WaveTiles &wt, int lane, uint32_t valid_bits,
 			global_half4 *my_skip, SkipCarry<F> *fetch, const WaveTiles *fetch_tiles)
 	{
@@ -307,7 +332,7 @@ namespace
 					fetch->v[i][n] = (n < fetch_tiles->count) ? __builtin_bit_cast(uint2, my_skip[(i * Lay<F>::NTW + n) * 64]) : uint2 { 0u, 0u };
 		}
 		lds_barrier(); // every wave has consumed the plane: it can be overwritten now
-		const int index0 = 1 + sh.S + wt.n0 * 16 + r;
+		const int index0 = 1 + sh.S + wt.n0 * 16 + (OWN_ADDR ? own(r) : r);
 #pragma unroll
 		for (int i = 0; i < 2; i++)
 		{
@@ -321,12 +346,15 @@ namespace
 	}
 
 	/*
-	 * A head's 3x3 convolution F -> F over the plane, folded with its 1x1 convolution (conv3x3_layer modes 2 and 3 of nn_any_board.hip).
+	 * A head's 3x3 convolution F -> F over the plane, folded with its 1x1 convolution.
 	 * QHEAD false: policy conv + ReLU and the 1x1 F -> 1: per-channel-group partial logits into `ppart` [CG][PS].
 	 * QHEAD true: action-values conv + tanh and the 1x1 F -> 3: `ppart` is [3][PS], the channel groups add their partial sums one after the
-	 * other (a fixed order).  The bias is added behind the k-loop; `next_bias` is requested for the layer behind this one.
+	 * other (a fixed order: results do not depend on wave timing).  The bias is added behind the k-loop; `next_bias` is requested for the layer
+	 * behind this one.
+	 * (The head epilogues, the policy softmax and the value head's conv1x1 stand here a second time next to nn_forward.hip's on purpose: written
+	 *  once over a tile map, each of them moved the register allocation of the fixed-shape kernels — DESIGN.md 3.1.)
 	 */
-	template<int F, bool QHEAD>
+	template<int F, bool QHEAD, int RING>
 	__device__ __forceinline__ void head_layer(const char *plane, const half8 *__restrict__ wpk, Bias2 &bias_carry, const float *__restrict__ next_bias,
 			const float *__restrict__ wp2, float *ppart, const Shape &sh, const WaveTiles &wt, int lane)
 	{
@@ -340,7 +368,7 @@ namespace
 #pragma unroll
 			for (int n = 0; n < L::NTW; n++)
 				acc[i][n] = floatx4 { 0.0f, 0.0f, 0.0f, 0.0f };
-		conv_mac<F, F, F, 9>(plane, wpk, sh, wt, lane, acc);
+		conv_mac<F, F, F, 9, RING>(plane, wpk, sh, wt, lane, acc);
 		const Bias2 bias_now = bias_carry;
 		if (next_bias != nullptr)
 			request_bias<F>(next_bias, wt, lane, bias_carry);
@@ -433,17 +461,17 @@ namespace
 	}
 
 	/*
-	 * Input block (conv5x5_input of nn_any_board.hip): 5x5 convolution of the bit-unpacked padded input plane `in5` (stride S5; 32 channels: 64
-	 * bytes per position, chunk-swizzled by (index >> 2) & 3; RAW: 8 channels, 16 bytes per position, one k-step = four horizontal taps) + bias +
-	 * ReLU.  `in5` aliases the plane: the plane is cleared and written behind a barrier; the outputs are also the first block's input (scratch).
+	 * Input block: 5x5 convolution of the bit-unpacked padded input plane `in5` (stride S5; 32 channels: 64 bytes per position,
+	 * chunk-swizzled by (index >> 2) & 3; RAW: 8 channels, 16 bytes per position, one k-step = four horizontal taps) + bias + ReLU.
+	 * `in5` aliases the plane: the plane is cleared and written behind a barrier; the outputs are also the first block's input (scratch).
 	 */
-	template<int F, bool RAW>
+	template<int F, bool RAW, bool OWN_ADDR>
 	__device__ __forceinline__ void conv5x5_input(char *plane, const half8 *__restrict__ wpk, const float *__restrict__ bias, global_half4 *my_skip, const Shape &sh,
 			const WaveTiles &wt, int wave, int lane, uint32_t valid_bits)
 	{
 		typedef Cfg<F> C;
 		typedef Lay<F> L;
-		const int r = lane & 15;
+		const int r = OWN_ADDR ? own(lane & 15) : (lane & 15);
 		const int q4 = lane >> 4;
 		const char *in5 = plane;
 		floatx4 acc[2][L::NTW];
@@ -528,11 +556,41 @@ namespace
 		}
 	}
 
-	template<int F, bool QHEAD, bool RAW>
-	__global__ __launch_bounds__(512) void nn_bottleneck_kernel(NetParams p, Shape sh, const uint32_t *__restrict__ features, float *__restrict__ policy)
+	/* the policy of board `b` from the channel groups' partial logits: bias, softmax over the rows * cols real cells (one per thread) */
+	template<int F>
+	__device__ __forceinline__ void policy_softmax(const float *ppart, float *red, float bp2, const Shape &sh, int tid, int cell_pos, float *policy, int b)
+	{
+		float logit = -3.0e38f;
+		if (tid < sh.HW)
+			logit = bp2 + sum_partial_logits<Lay<F>::CG, Cfg<F>::PS>(ppart, cell_pos);
+		const float m = block_reduce_max(logit, red, tid);
+		const float e = (tid < sh.HW) ? __expf(logit - m) : 0.0f;
+		const float sum = block_reduce_sum(e, red, tid);
+		if (tid < sh.HW)
+			policy[static_cast<size_t>(b) * sh.HW + tid] = e / sum;
+	}
+
+	/* the action values of board `b` from the summed logits `qpart` [3][PS]: bias, softmax over the 3 per cell, (win, draw) stored */
+	template<int F>
+	__device__ __forceinline__ void q_output(const float *qpart, const NetParams &p, const Shape &sh, int tid, int cell_pos, int b)
+	{
+		typedef Cfg<F> C;
+		if (tid < sh.HW)
+		{
+			const float z0 = p.bq2[0] + qpart[cell_pos], z1 = p.bq2[1] + qpart[C::PS + cell_pos], z2 = p.bq2[2] + qpart[2 * C::PS + cell_pos];
+			const float2 win_draw = softmax3_win_draw(z0, z1, z2);
+			float *out = p.q + (static_cast<size_t>(b) * sh.HW + tid) * 2;
+			out[0] = win_draw.x;
+			out[1] = win_draw.y;
+		}
+	}
+
+	template<int F, int BLOCK, bool QHEAD, bool RAW>
+	__global__ __launch_bounds__(512) void nn_any_board_kernel(NetParams p, Shape sh, const uint32_t *__restrict__ features, float *__restrict__ policy)
 	{
 		typedef Cfg<F> C;
 		constexpr int FH = F / 2;
+		constexpr bool OWN_ADDR = OWN<BLOCK>;
 		__shared__ __attribute__((aligned(16))) char lds[C::LDS_BYTES];
 		char *plane = lds;
 		half8 *s_wv1f = reinterpret_cast<half8*>(lds + C::PLANE_MAX);     // [KC][64]: A fragments of the value head's conv1x1 (4 real units of 16)
@@ -545,12 +603,15 @@ namespace
 		const int tid = threadIdx.x;
 		const int wave = tid >> 6;
 		const int lane = tid & 63;
-		// half8 elements of the packed layers: W1 (1 tap, F -> F/2), W2 (F/2 -> F/2), W3 (F/2 -> F), a head's conv (F -> F)
+		// half8 elements of the packed layers: a 3x3 F -> F (a head's conv, a residual block's two), a bottleneck block's W1 (1 tap, F -> F/2),
+		// W2 (F/2 -> F/2) and W3 (F/2 -> F); floats of a block's biases
+		constexpr int HEAD_H8 = 9 * (F / 32) * (F / 16) * 64;
 		constexpr int W1_H8 = (F / 32) * (FH / 16) * 64, W2_H8 = 9 * (FH / 32) * (FH / 16) * 64, W3_H8 = 9 * (FH / 32) * (F / 16) * 64;
-		constexpr int BLOCK_H8 = W1_H8 + W2_H8 + W3_H8, HEAD_H8 = 9 * (F / 32) * (F / 16) * 64;
-		const WaveTiles wf = wave_tiles<F>(sh, sh.ntw_f, wave);   // full-width layers
-		const WaveTiles wh = wave_tiles<FH>(sh, sh.ntw_h, wave);  // half-width layers
-		global_half4 *my_skip = lane_skip<F>(p.skip + static_cast<size_t>(blockIdx.x) * SKIP_PER_WG<F>, wave, lane);
+		constexpr int BLOCK_H8 = (BLOCK == BOTTLENECK) ? (W1_H8 + W2_H8 + W3_H8) : 2 * HEAD_H8, BLOCK_BIAS = 2 * F;
+		const WaveTiles wf = wave_tiles<F>(sh, sh.ntw, wave);     // full-width layers
+		const WaveTiles wh = wave_tiles<FH>(sh, sh.ntw_h, wave);  // half-width layers (bottleneck blocks; dead code in the residual instantiations)
+		half4 *skip = p.skip + static_cast<size_t>(blockIdx.x) * SKIP_PER_WG<F>;
+		global_half4 *my_skip = lane_skip<F>(skip, wave, lane);
 
 		stage_head_weights<F, C::THREADS, QHEAD>(p.wv1, p.wp2, p.wq2, tid, s_wv1f, s_wp2, s_wq2);
 
@@ -558,7 +619,7 @@ namespace
 		const int cell_y = (tid < sh.HW) ? tid / sh.cols : 0, cell_x = (tid < sh.HW) ? tid - cell_y * sh.cols : 0;
 		const int cell_q5 = (cell_y + 2) * sh.S5 + (cell_x + 2);   // in the padded input plane
 		const int cell_pos = cell_y * sh.S + cell_x;               // position (stride S)
-		const uint32_t valid_f = on_board_bits(sh, wf, lane), valid_h = on_board_bits(sh, wh, lane);
+		const uint32_t valid_f = on_board_bits(sh, wf, lane), valid_h = (BLOCK == BOTTLENECK) ? on_board_bits(sh, wh, lane) : 0u;
 
 		const int batch = (p.count_ptr != nullptr) ? min(*p.count_ptr, p.batch) : p.batch;
 		uint32_t next_word = 0; // this thread's feature word of the board about to be staged
@@ -589,54 +650,80 @@ namespace
 				}
 			}
 			__syncthreads();
-			conv5x5_input<F, RAW>(plane, p.w_in, p.bias, my_skip, sh, wf, wave, lane, valid_f);
+			conv5x5_input<F, RAW, OWN_ADDR>(plane, p.w_in, p.bias, layer_skip<F, OWN_ADDR>(my_skip, skip, wave, lane), sh, wf, wave, lane, valid_f);
 			Bias2 bias_carry; // the next layer's bias values in that layer's wave layout: requested behind the k-loop of the layer in front of it
-			if (p.blocks > 0)
+			if (BLOCK == BOTTLENECK && p.blocks > 0)
 				request_bias<FH>(p.bias + F, wh, lane, bias_carry);
 			else
 				request_bias<F>(p.bias + F, wf, lane, bias_carry);
 			__syncthreads();
 
-			// ---- bottleneck blocks ----
+			// ---- the blocks ----
 			for (int blk = 0; blk < p.blocks; blk++)
 			{
-				const half8 *w1 = p.w_tower + static_cast<size_t>(blk) * BLOCK_H8, *w2 = w1 + W1_H8, *w3 = w2 + W2_H8;
-				const float *b1 = p.bias + F + blk * 2 * F; // b1 [F/2], b2 [F/2], b3 [F], then the next block's (or the policy conv's)
+				const half8 *w1 = p.w_tower + static_cast<size_t>(blk) * BLOCK_H8, *w2 = w1 + W1_H8, *w3 = w2 + W2_H8; // (w2, w3: bottleneck)
+				const float *b1 = p.bias + F + blk * BLOCK_BIAS; // this block's biases, then the next block's (or the policy conv's)
 				SkipCarry<F> x;
-				{ // 1x1, F -> F/2
-					floatx4 acc[2][Lay<FH>::NTW];
-					start_from_bias<FH>(bias_carry, acc);
-					conv_mac<F, F, FH, 1>(plane, w1, sh, wh, lane, acc);
-					request_bias<FH>(b1 + FH, wh, lane, bias_carry);
-					store_relu<F, FH, false>(plane, acc, sh, wh, lane, valid_h, my_skip, nullptr, nullptr);
-				}
-				lds_barrier();
-				{ // 3x3, F/2 -> F/2
-					floatx4 acc[2][Lay<FH>::NTW];
-					start_from_bias<FH>(bias_carry, acc);
-					conv_mac<F, FH, FH, 9>(plane, w2, sh, wh, lane, acc);
-					request_bias<F>(b1 + F, wf, lane, bias_carry);
-					store_relu<F, FH, false>(plane, acc, sh, wh, lane, valid_h, my_skip, &x, &wf);
-				}
-				lds_barrier();
-				{ // 3x3, F/2 -> F, + x
-					floatx4 acc[2][Lay<F>::NTW];
+				if constexpr (BLOCK == RESIDUAL)
+				{ // b1 [F], b2 [F]
+					{ // 3x3, F -> F
+						floatx4 acc[2][Lay<F>::NTW];
+						start_from_bias<F>(bias_carry, acc);
+						conv_mac<F, F, F, 9, RING<BLOCK, F>>(plane, w1, sh, wf, lane, acc);
+						request_bias<F>(b1 + F, wf, lane, bias_carry);
+						store_relu<F, F, false, OWN_ADDR>(plane, acc, sh, wf, lane, valid_f, layer_skip<F, OWN_ADDR>(my_skip, skip, wave, lane), &x, &wf);
+					}
+					lds_barrier();
+					{ // 3x3, F -> F, + x
+						floatx4 acc[2][Lay<F>::NTW];
 #pragma unroll
-					for (int i = 0; i < 2; i++)
+						for (int i = 0; i < 2; i++)
 #pragma unroll
-						for (int n = 0; n < Lay<F>::NTW; n++)
-							acc[i][n] = bias_plus_residual(x.v[i][n], bias_carry.b[i]);
-					conv_mac<F, FH, F, 9>(plane, w3, sh, wf, lane, acc);
-					if (blk + 1 < p.blocks)
-						request_bias<FH>(b1 + 2 * F, wh, lane, bias_carry);
-					else
+							for (int n = 0; n < Lay<F>::NTW; n++)
+								acc[i][n] = bias_plus_residual(x.v[i][n], bias_carry.b[i]);
+						conv_mac<F, F, F, 9, RING<BLOCK, F>>(plane, w1 + HEAD_H8, sh, wf, lane, acc);
 						request_bias<F>(b1 + 2 * F, wf, lane, bias_carry);
-					store_relu<F, F, true>(plane, acc, sh, wf, lane, valid_f, my_skip, nullptr, nullptr);
+						store_relu<F, F, true, OWN_ADDR>(plane, acc, sh, wf, lane, valid_f, layer_skip<F, OWN_ADDR>(my_skip, skip, wave, lane), nullptr, nullptr);
+					}
+					lds_barrier();
 				}
-				lds_barrier();
+				else
+				{ // b1 [F/2], b2 [F/2], b3 [F]
+					{ // 1x1, F -> F/2
+						floatx4 acc[2][Lay<FH>::NTW];
+						start_from_bias<FH>(bias_carry, acc);
+						conv_mac<F, F, FH, 1>(plane, w1, sh, wh, lane, acc);
+						request_bias<FH>(b1 + FH, wh, lane, bias_carry);
+						store_relu<F, FH, false, OWN_ADDR>(plane, acc, sh, wh, lane, valid_h, my_skip, nullptr, nullptr);
+					}
+					lds_barrier();
+					{ // 3x3, F/2 -> F/2
+						floatx4 acc[2][Lay<FH>::NTW];
+						start_from_bias<FH>(bias_carry, acc);
+						conv_mac<F, FH, FH, 9, RING<BLOCK, FH>>(plane, w2, sh, wh, lane, acc);
+						request_bias<F>(b1 + F, wf, lane, bias_carry);
+						store_relu<F, FH, false, OWN_ADDR>(plane, acc, sh, wh, lane, valid_h, my_skip, &x, &wf);
+					}
+					lds_barrier();
+					{ // 3x3, F/2 -> F, + x
+						floatx4 acc[2][Lay<F>::NTW];
+#pragma unroll
+						for (int i = 0; i < 2; i++)
+#pragma unroll
+							for (int n = 0; n < Lay<F>::NTW; n++)
+								acc[i][n] = bias_plus_residual(x.v[i][n], bias_carry.b[i]);
+						conv_mac<F, FH, F, 9, RING<BLOCK, FH>>(plane, w3, sh, wf, lane, acc);
+						if (blk + 1 < p.blocks)
+							request_bias<FH>(b1 + 2 * F, wh, lane, bias_carry);
+						else
+							request_bias<F>(b1 + 2 * F, wf, lane, bias_carry);
+						store_relu<F, F, true, OWN_ADDR>(plane, acc, sh, wf, lane, valid_f, layer_skip<F, OWN_ADDR>(my_skip, skip, wave, lane), nullptr, nullptr);
+					}
+					lds_barrier();
+				}
 			}
 			const half8 *w_heads = p.w_tower + static_cast<size_t>(p.blocks) * BLOCK_H8;
-			const float *b_heads = p.bias + F + p.blocks * 2 * F;
+			const float *b_heads = p.bias + F + p.blocks * BLOCK_BIAS;
 
 			// ---- value head, stage 1: conv1x1 F -> 4 + ReLU as one 16 x 16 MFMA tile per 16 positions (4 of the 16 units are real), the tiles dealt
 			//      round-robin to the waves; the dense layers run in value_head_kernel (nn_forward.hip) for all boards of the launch ----
@@ -669,7 +756,7 @@ namespace
 				}
 			}
 			// ---- policy head: conv3x3 + ReLU folded with the conv1x1 F -> 1 ----
-			head_layer<F, false>(plane, w_heads, bias_carry, QHEAD ? b_heads + F : nullptr, s_wp2, ppart, sh, wf, lane);
+			head_layer<F, false, RING<BLOCK, F>>(plane, w_heads, bias_carry, QHEAD ? b_heads + F : nullptr, s_wp2, ppart, sh, wf, lane);
 			__syncthreads();
 			// the next board's input: requested here, consumed by the staging at the top
 			if (bi + static_cast<int>(gridDim.x) < batch && tid < sh.HW)
@@ -677,77 +764,61 @@ namespace
 				const int nb = bi + static_cast<int>(gridDim.x);
 				next_word = features[static_cast<size_t>((p.slot_list != nullptr) ? p.slot_list[nb] : nb) * sh.HW + tid];
 			}
-			{ // bias, softmax over the rows * cols real cells (one per thread)
-				float logit = -3.0e38f;
-				if (tid < sh.HW)
-					logit = p.bp2 + sum_partial_logits<Lay<F>::CG, C::PS>(ppart, cell_pos);
-				const float m = block_reduce_max(logit, red, tid);
-				const float e = (tid < sh.HW) ? __expf(logit - m) : 0.0f;
-				const float sum = block_reduce_sum(e, red, tid);
-				if (tid < sh.HW)
-					policy[static_cast<size_t>(b) * sh.HW + tid] = e / sum;
-			}
+			policy_softmax<F>(ppart, red, p.bp2, sh, tid, cell_pos, policy, b);
 			// ---- action-values head: conv3x3 + tanh, conv1x1 F -> 3 + bias, softmax over the 3 per cell ----
 			if (QHEAD)
 			{
 				__syncthreads(); // the policy head is done with the partial-sum buffers
-				head_layer<F, true>(plane, w_heads + HEAD_H8, bias_carry, nullptr, s_wq2, qpart, sh, wf, lane);
-				if (tid < sh.HW)
-				{
-					const float z0 = p.bq2[0] + qpart[cell_pos], z1 = p.bq2[1] + qpart[C::PS + cell_pos], z2 = p.bq2[2] + qpart[2 * C::PS + cell_pos];
-					const float2 win_draw = softmax3_win_draw(z0, z1, z2);
-					float *out = p.q + (static_cast<size_t>(b) * sh.HW + tid) * 2;
-					out[0] = win_draw.x;
-					out[1] = win_draw.y;
-				}
+				head_layer<F, true, RING<BLOCK, F>>(plane, w_heads + HEAD_H8, bias_carry, nullptr, s_wq2, qpart, sh, wf, lane);
+				q_output<F>(qpart, p, sh, tid, cell_pos, b);
 			}
 		}
 	}
 
-	template<int F>
-	Shape make_shape(int rows, int cols, int kpad)
+	Shape make_shape(int rows, int cols, int filters, int kpad)
 	{
+		const int pg = 8 / (filters / 32), pg_h = 8 / (filters / 64); // Lay<F>::PG, Lay<F / 2>::PG
 		Shape sh;
 		sh.rows = rows;
 		sh.cols = cols;
 		sh.S = cols + 1;
 		sh.NT = (rows * sh.S + 15) / 16;
-		sh.ntw_f = (sh.NT + Lay<F>::PG - 1) / Lay<F>::PG;
-		sh.ntw_h = (sh.NT + Lay<F / 2>::PG - 1) / Lay<F / 2>::PG;
+		sh.ntw = (sh.NT + pg - 1) / pg;
+		sh.ntw_h = (sh.NT + pg_h - 1) / pg_h;
 		sh.HW = rows * cols;
 		sh.kpad = kpad;
-		sh.plane16 = (1 + sh.S + sh.NT * 16 + sh.S + 2) * Cfg<F>::POS_BYTES / 16;
+		sh.plane16 = (1 + sh.S + sh.NT * 16 + sh.S + 2) * (filters * 2) / 16;
 		sh.S5 = sh.S + 4;
 		sh.npos5 = (rows + 4) * sh.S5 + 4;
 		sh.magic = 65536 / sh.S + 1;
 		return sh;
 	}
-}
 
-namespace agx_btl
-{
-	size_t skip_bytes_per_workgroup(int filters)
+	/* the six instantiations of one block kind, launched for a record that agx_any::launch() has checked */
+	template<int BLOCK>
+	int launch_block(const NetParams &p, int rows, int cols, int filters, bool raw, int grid, int kpad, const uint32_t *d_features, float *d_policy, hipStream_t stream)
 	{
-		return sizeof(half4) * static_cast<size_t>((filters == 128) ? SKIP_PER_WG<128> : SKIP_PER_WG<64>);
-	}
-
-	int launch(const NetParams &p, int rows, int cols, int filters, bool raw, int grid, int kpad, const uint32_t *d_features, float *d_policy, hipStream_t stream)
-	{
-		AGX_REQUIRE(rows >= agx_any::MIN_SIDE && rows <= agx_any::MAX_SIDE && cols >= agx_any::MIN_SIDE && cols <= agx_any::MAX_SIDE && (filters == 64 || filters == 128),
-				AGX_ERR_UNSUPPORTED, "agx_nn_forward: no bottleneck kernel for a %dx%d board with %d filters", rows, cols, filters);
-		AGX_REQUIRE(p.skip != nullptr && p.vhead_x != nullptr && grid > 0, AGX_ERR_STATE, "agx_nn_forward: launch scratch missing");
 		const bool qhead = (p.q != nullptr);
-		AGX_REQUIRE(!(qhead && raw), AGX_ERR_UNSUPPORTED, "agx_nn_forward: no action-values head on an 8-channel network");
 		const dim3 g(grid), t(512);
-#define AGX_BTL_TOWER(FF, QH, RW) hipLaunchKernelGGL((nn_bottleneck_kernel<FF, QH, RW>), g, t, 0, stream, p, make_shape<FF>(rows, cols, kpad), d_features, d_policy)
-#define AGX_BTL_VARIANTS(FF) do { if (qhead) AGX_BTL_TOWER(FF, true, false); else if (raw) AGX_BTL_TOWER(FF, false, true); else AGX_BTL_TOWER(FF, false, false); } while (0)
+		const Shape sh = make_shape(rows, cols, filters, kpad);
+#define AGX_ANY_TOWER(FF, QH, RW) hipLaunchKernelGGL((nn_any_board_kernel<FF, BLOCK, QH, RW>), g, t, 0, stream, p, sh, d_features, d_policy)
+#define AGX_ANY_HEADS(FF) do { if (qhead) AGX_ANY_TOWER(FF, true, false); else if (raw) AGX_ANY_TOWER(FF, false, true); else AGX_ANY_TOWER(FF, false, false); } while (0)
 		if (filters == 128)
-			AGX_BTL_VARIANTS(128);
+			AGX_ANY_HEADS(128);
 		else
-			AGX_BTL_VARIANTS(64);
-#undef AGX_BTL_VARIANTS
-#undef AGX_BTL_TOWER
+			AGX_ANY_HEADS(64);
+#undef AGX_ANY_HEADS
+#undef AGX_ANY_TOWER
 		AGX_HIP_CHECK(hipGetLastError());
 		return AGX_OK;
 	}
 }
+
+namespace agx_any
+{
+	/* launch_block<BOTTLENECK> (nn_any_board_bottleneck.hip), called by launch() */
+	int launch_bottleneck(const agx_nn::NetParams &p, int rows, int cols, int filters, bool raw, int grid, int kpad, const uint32_t *d_features, float *d_policy,
+			hipStream_t stream);
+}
+
+#endif /* AGX_NN_ANY_BOARD_KERNEL_HPP_ */

@@ -117,38 +117,6 @@ namespace
 			int mg, pg, n0, count;
 	};
 
-	/* A lane index as this use's own value: per-lane addresses made from lane indices the compiler can see are kernel-wide constants to it, computed
-	 * once in front of the board loop for every tile of every layer and kept in scratch (hundreds of registers: nn_any_board.hip has the same) */
-	__device__ __forceinline__ int own(int v)
-	{
-		asm volatile("" : "+v"(v));
-		return v;
-	}
-
-	/* Behind a tile loop and in front of the first VALU read of its accumulators.  A wave with fewer tiles than the accumulator array leaves the
-	 * loop by a branch straight behind its last MFMA; measured on MI355X with 64 filters on an 8x8 board (one tile per wave), the epilogue
-	 * then read the last two registers of the MFMA issued last before they were written: the wait states between an MFMA and a VALU read of
-	 * its result are software's to keep, and on that path the pad was one state.  16 states, then every accumulator as an operand of an (empty)
-	 * statement behind them, so that no read is scheduled in front of the pad. */
-	template<int N>
-	__device__ __forceinline__ void mfma_settle(floatx4 (&acc)[N])
-	{
-		asm volatile("s_nop 15");
-#pragma unroll
-		for (int n = 0; n < N; n++)
-			asm volatile("" : "+v"(acc[n]));
-	}
-	template<int M, int N>
-	__device__ __forceinline__ void mfma_settle(floatx4 (&acc)[M][N])
-	{
-		asm volatile("s_nop 15");
-#pragma unroll
-		for (int i = 0; i < M; i++)
-#pragma unroll
-			for (int n = 0; n < N; n++)
-				asm volatile("" : "+v"(acc[i][n]));
-	}
-
 	__device__ __forceinline__ half_t relu_half(float v)
 	{ // a ReLU output as it would be stored
 		return static_cast<half_t>(fmaxf(v, 0.0f));

@@ -1,7 +1,8 @@
 /*
- * nn_device.hpp — the device code that the two network kernel files share: nn_forward.hip (the 15x15 and 20x20 towers, the value head's
- * dense layers, the residual towers' host side) and nn_any_board.hip (the run-time-shaped tower).  The vector types, the launch record NetParams, the small
- * helpers of the layers (LDS barrier, fp16 + fp32 add, carried bias values, workgroup reductions) and the pieces both towers run word for
+ * nn_device.hpp — the device code that the network kernel files share: nn_forward.hip (the 15x15 and 20x20 towers, the value head's
+ * dense layers, the residual towers' host side), nn_any_board.hip (the run-time-shaped towers, residual and bottleneck blocks) and, for the
+ * types and mfma_settle() / own(), nn_convnext.hip.  The vector types, the launch record NetParams, the small
+ * helpers of the layers (LDS barrier, MFMA settle, fp16 + fp32 add, carried bias values, workgroup reductions) and the pieces both towers run word for
  * word: the unpacking of a feature byte, the staging of the heads' 1x1 weights, the action-values softmax.  The functions are in the unnamed
  * namespace and forced inline: each .hip file gets its own copy, exactly as if the text stood there.  The types are in agx_nn: NetParams
  * crosses from one file to the other (agx_any::launch), and a function over a type of the unnamed namespace cannot be linked.
@@ -61,6 +62,38 @@ namespace
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
 		__builtin_amdgcn_s_barrier();
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+	}
+
+	/* A lane index as this use's own value: per-lane addresses made from lane indices the compiler can see are kernel-wide constants to it, computed
+	 * once in front of the board loop for every tile of every layer and kept in scratch (hundreds of registers) */
+	__device__ __forceinline__ int own(int v)
+	{
+		asm volatile("" : "+v"(v));
+		return v;
+	}
+
+	/* Behind a tile loop and in front of the first VALU read of its accumulators.  A wave with fewer tiles than the accumulator
+	 * array leaves the loop by a branch straight behind its last MFMA; measured on MI355X with 64 filters on an 8x8 board (one tile per wave), the
+	 * epilogue then read the last two registers of the MFMA issued last before they were written: the wait states between an MFMA and a VALU read
+	 * of its result are software's to keep, and on that path the pad was one state.  16 states, then every accumulator as an operand of an (empty)
+	 * statement behind them, so that no read is scheduled in front of the pad. */
+	template<int N>
+	__device__ __forceinline__ void mfma_settle(floatx4 (&acc)[N])
+	{
+		asm volatile("s_nop 15");
+#pragma unroll
+		for (int n = 0; n < N; n++)
+			asm volatile("" : "+v"(acc[n]));
+	}
+	template<int M, int N>
+	__device__ __forceinline__ void mfma_settle(floatx4 (&acc)[M][N])
+	{
+		asm volatile("s_nop 15");
+#pragma unroll
+		for (int i = 0; i < M; i++)
+#pragma unroll
+			for (int n = 0; n < N; n++)
+				asm volatile("" : "+v"(acc[i][n]));
 	}
 
 	/* (float) one half of a packed pair + addend as ONE instruction: v_fma_mix_f32 widens the fp16 operand itself (h * 1.0 + b rounds once,

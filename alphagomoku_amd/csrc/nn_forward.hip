@@ -44,7 +44,6 @@
 #include "nn_device.hpp"
 #include "nn_pack.hpp"
 #include "nn_any_board.hpp"
-#include "nn_bottleneck.hpp"
 #include "nn_resnet.hpp"
 
 #include <vector>
@@ -1826,7 +1825,7 @@ namespace agx_res
 			float bv3[3] = { 0, 0, 0 };
 			float bq2[3] = { 0, 0, 0 };
 			bool inplace = false;
-			bool bottleneck = false; // bottleneck blocks (nn_bottleneck.hip: one run-time-shaped kernel for every shape) between the same input block and heads
+			bool bottleneck = false; // bottleneck blocks (a block kind of the run-time-shaped kernel, which then runs every shape) between the same input block and heads
 			bool any_board = false; // the run-time-shaped kernel (nn_any_board.hip): every shape but 15x15 / 20x20, or AGX_NN_ANY_BOARD=1
 			size_t skip_bytes = 0;
 			// single-plane variant: residual scratch, one slice per workgroup of the persistent grid.  Launches on DIFFERENT streams may run
@@ -1987,7 +1986,7 @@ namespace agx_res
 		const char *force = getenv("AGX_NN_SINGLE_PLANE");
 		net->inplace = net->any_board || board20 || (force != nullptr && force[0] == '1');
 		if (net->any_board) // (one plane for every shape; its residual scratch is sized for the largest board)
-			net->skip_bytes = (bottleneck ? agx_btl::skip_bytes_per_workgroup(F) : agx_any::skip_bytes_per_workgroup(F)) * static_cast<size_t>(num_cus);
+			net->skip_bytes = agx_any::skip_bytes_per_workgroup(F) * static_cast<size_t>(num_cus);
 		else if (net->inplace)
 		{
 			const size_t per_wg = board20 ? ((F == 128) ? Geometry<128, 20, 20>::SKIP_PER_WG : Geometry<64, 20, 20>::SKIP_PER_WG)
@@ -2072,8 +2071,8 @@ namespace agx_res
 		else AGX_LAUNCH_TOWER(FF, NN, IP, false, false); } while (0)
 		if (net->any_board)
 		{
-			const int status = net->bottleneck ? agx_btl::launch(p, net->desc.rows, net->desc.cols, net->desc.filters, raw, grid, kpad, d_features, d_policy, s)
-					: agx_any::launch(p, net->desc.rows, net->desc.cols, net->desc.filters, raw, grid, kpad, d_features, d_policy, s);
+			const int status = agx_any::launch(p, net->bottleneck ? agx_any::BOTTLENECK : agx_any::RESIDUAL, net->desc.rows, net->desc.cols, net->desc.filters, raw, grid,
+					kpad, d_features, d_policy, s);
 			if (status != AGX_OK)
 				return status;
 		}

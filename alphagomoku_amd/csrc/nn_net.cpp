@@ -1,7 +1,7 @@
 /*
  * nn_net.cpp — AgxNet and every network entry point of the C ABI (include/agx.h): the small thing above the towers.  An architecture is a
  * namespace with supported / blob_floats / load / destroy / launch over an opaque Net: agx_res (nn_resnet.hpp; the kernels and their host
- * side are in nn_forward.hip; the bottleneck towers are a block kind of the same Net, kernel in nn_bottleneck.hip) and agx_cnx (nn_convnext.hpp, nn_convnext.hip).  Each function below checks its arguments once and forks on
+ * side are in nn_forward.hip; the bottleneck towers are a block kind of the same Net and of the run-time-shaped kernel, nn_any_board.hip) and agx_cnx (nn_convnext.hpp, nn_convnext.hip).  Each function below checks its arguments once and forks on
  * the architecture in one place.
  */
 #include "agx_internal.hpp"

@@ -1,7 +1,7 @@
 /*
  * nn_resnet.hpp — the residual towers (nn_forward.hip: the 15x15 and 20x20 kernels, the run-time-shaped one of nn_any_board.hip behind them, the
  * value head's dense layers) as nn_net.cpp sees them: the entry points of the C ABI dispatch here for an AgxNet whose architecture is
- * AGX_ARCH_RESNET — and, as a block kind of the same Net, the bottleneck towers (AGX_ARCH_BOTTLENECK: the kernel of nn_bottleneck.hip between the
+ * AGX_ARCH_RESNET — and, as a block kind of the same Net, the bottleneck towers (AGX_ARCH_BOTTLENECK: the bottleneck block of nn_any_board.hip's kernel between the
  * residual networks' input block and heads; `bottleneck` below).
  */
 #ifndef AGX_NN_RESNET_HPP_

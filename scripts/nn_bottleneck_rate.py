@@ -1,4 +1,4 @@
-"""Rate of the bottleneck tower (csrc/nn_bottleneck.hip), reported and not gated: stand-alone launches timed one by one with HIP events, BottleneckPVQ
+"""Rate of the bottleneck tower (the bottleneck block of csrc/nn_any_board.hip), reported and not gated: stand-alone launches timed one by one with HIP events, BottleneckPVQ
 6 x 128 and 10 x 128 on 15x15 and 10 x 128 on 20x20, batches of 1 664 and 6 656 positions, on 64 compute units through a CU-masked stream
 (launch width 64) and on the whole chip; after 3 warm-up launches the median of 21.  Next to every line the residual tower (ResnetPVQ) of the
 same blocks x filters from the same process.  TFLOP/s count 2 x the multiply-adds of the convolutions per position (input 25 Cin F, a

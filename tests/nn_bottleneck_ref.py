@@ -1,6 +1,6 @@
 """References, exact networks and cases of the bottleneck network tests (helper module of test_nn_bottleneck_cpu.py / test_nn_bottleneck_gpu.py).
 
-BottleneckPV / BottleneckPVraw / BottleneckPVQ (csrc/nn_bottleneck.hip) are the residual networks with another block (blob layout of
+BottleneckPV / BottleneckPVraw / BottleneckPVQ (the bottleneck block of csrc/nn_any_board.hip) are the residual networks with another block (blob layout of
 include/agx.h):
 
     y = relu(W1 . x + b1)   1x1, F -> F/2      y = relu(W2 * y + b2)   3x3, F/2 -> F/2      x = relu(x + W3 * y + b3)   3x3, F/2 -> F

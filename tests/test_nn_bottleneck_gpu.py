@@ -1,9 +1,10 @@
-"""The bottleneck towers (csrc/nn_bottleneck.hip: BottleneckPV / BottleneckPVraw / BottleneckPVQ) on the GPU.
+"""The bottleneck towers (the bottleneck block of csrc/nn_any_board.hip: BottleneckPV / BottleneckPVraw / BottleneckPVQ) on the GPU.
 
   * exact parity with the float64 reference of nn_bottleneck_ref.py on networks that round nowhere before the softmax
     (test_nn_bottleneck_cpu.py proves it for every case here): 5x5 (waves without tiles), 8x8 (one tile per wave at F = 64), 6x20 / 20x6,
     7x19, 15x15, 20x20, each with both filter counts, blocks 0 / 1 / 3, pv / raw / pvq, random and transparent heads.  Logit differences are
     recovered from the softmax outputs (nn_exact.logit_deviation) and must stay within a quarter of the head's grid step.
+  * a network without blocks equals the residual network without blocks bit for bit: the two block kinds run one kernel frame.
   * the entry points: slot list, narrowed launch, batch sizes, NULL q buffer, refusals.
   * He-init networks against the storage-rounding restatement, bound derived on the CPU (nn_bottleneck_ref.tolerance).
   * the network in a pool, under a position evaluator, from / under the trainer, and through the compiled classes.
@@ -16,6 +17,7 @@ import sys
 import numpy as np
 import pytest
 
+import nn_any_board as ab
 import nn_bottleneck_ref as br
 import nn_exact as nx
 from alphagomoku_amd import synthetic
@@ -68,6 +70,30 @@ def test_exact_networks(agx_lib, rows, cols, filters, kind, blocks, heads, seed)
     finally:
         net.close()
     assert_exact(out, desc, blob, ref, "%s %s heads seed %d" % (br.describe(desc), heads, seed))
+
+
+# 5x5: waves without tiles; 8x8: one tile per wave at F = 64; 7x19: several tiles per wave and a ragged last tile
+@pytest.mark.parametrize("kind", br.KINDS)
+@pytest.mark.parametrize("filters", [64, 128])
+@pytest.mark.parametrize("rows,cols", [(5, 5), (8, 8), (7, 19)])
+def test_no_blocks_equals_the_residual_network_bit_for_bit(agx_lib, rows, cols, filters, kind):
+    """input block, heads and everything around them are ONE frame for the two block kinds: with blocks = 0 and the same exact weights the
+    bottleneck network and the residual network return the same bits in policy, value and q, on the directed boards"""
+    desc = br.make_desc(rows, cols, filters, kind, 0)
+    blob = br.exact_weights(desc, 1)
+    assert np.array_equal(blob, nx.exact_weights(br.resnet_desc(desc), 1, "random"))   # (without blocks the two blob layouts are one)
+    f = ab.directed_boards(rows, cols)[0]
+    outputs = []
+    for d in (desc, br.resnet_desc(desc)):
+        net = load(d, blob)
+        try:
+            outputs.append(net.forward(f))
+        finally:
+            net.close()
+    assert len(outputs[0]) == len(outputs[1]) == (3 if kind == "pvq" else 2)
+    for name, a, b in zip(("policy", "value", "q"), *outputs):
+        assert a.shape == b.shape and np.isfinite(a).all(), name
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (name, int((a.view(np.uint32) != b.view(np.uint32)).sum()))
 
 
 # ------------------------------------------------------------------------------------------------------------------------ entry points
