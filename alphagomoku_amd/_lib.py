@@ -455,12 +455,22 @@ def sample_stride(cells):
     return (16 + 6 * cells + 3) // 4 * 4
 
 
+class AgxPlayerSearch(ctypes.Structure):
+    _fields_ = [("max_simulations", ctypes.c_int), ("max_batch_size", ctypes.c_int), ("exploration_constant", ctypes.c_float),
+                ("exploration_scaling", ctypes.c_float), ("init_to", ctypes.c_int), ("information_leak_threshold", ctypes.c_float),
+                ("max_children", ctypes.c_int), ("policy_expansion_threshold", ctypes.c_float), ("policy_temperature", ctypes.c_float),
+                ("tss_max_positions", ctypes.c_int), ("final_selector", ctypes.c_int), ("action_values", ctypes.c_int)]
+
+
 _declare_searcher = _declare
 
 
 def _declare(c):  # noqa: F811
     _declare_searcher(c)
     vp, ci, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+    c.agx_engine_player_search.argtypes = [vp, ci, ctypes.POINTER(AgxPlayerSearch)]
+    c.agx_engine_set_player_search.argtypes = [vp, ci, ctypes.POINTER(AgxPlayerSearch)]
+    c.agx_engine_match_summary.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong), vp]
     outputs, sink = ctypes.POINTER(AgxPositionSearchOutputs), ctypes.POINTER(AgxPositionSampleSink)
     c.agx_position_searcher_begin_ex.argtypes = [vp, ci, vp, vp, vp, outputs, sink, ci, ci, vp]
     c.agx_position_searcher_search_ex.argtypes = [vp, vp, ci, vp, vp, vp, outputs, sink, ci, ci, vp]

@@ -34,6 +34,28 @@ namespace agx
 			E.ht_cap = E.games[g].ht_cap;
 		}
 
+		/* Evaluation matches whose players search with settings of their own (AgxPlayerSearch; evaluation/Player.cpp:64-81): a merged match
+		 * launch covers both players' trees, so a kernel that works on tree g overrides the search settings in its by-value copy of E with
+		 * those of g's player before calling anything below — like use_game_arenas.  g is wave-uniform everywhere this is called, so each
+		 * field is one scalar select between two kernel arguments.  Only merged launches call it (E.match_merged; the persistent search
+		 * kernel, k_expand and k_advance have a variant of their own for them): every other launch reads the plain kernel arguments. */
+		__device__ __forceinline__ void use_player_search(EngineDev &E, int g)
+		{
+			const bool second = g >= (E.n_games >> 1);
+			E.max_sims = second ? E.player[1].max_sims : E.player[0].max_sims;
+			E.batch_limit = second ? E.player[1].batch_limit : E.player[0].batch_limit;
+			E.c_puct = second ? E.player[1].c_puct : E.player[0].c_puct;
+			E.c_scale = second ? E.player[1].c_scale : E.player[0].c_scale;
+			E.init_to = second ? E.player[1].init_to : E.player[0].init_to;
+			E.leak_threshold = second ? E.player[1].leak_threshold : E.player[0].leak_threshold;
+			E.expansion_threshold = second ? E.player[1].expansion_threshold : E.player[0].expansion_threshold;
+			E.max_children = second ? E.player[1].max_children : E.player[0].max_children;
+			E.policy_temperature = second ? E.player[1].policy_temperature : E.player[0].policy_temperature;
+			E.tss_max_nodes = second ? E.player[1].tss_max_nodes : E.player[0].tss_max_nodes;
+			E.final_selector = second ? E.player[1].final_selector : E.player[0].final_selector;
+			E.has_q = second ? E.player[1].has_q : E.player[0].has_q;
+		}
+
 		/* NodeCache::seek (NodeCache.cpp:250-264): hash, side to move and the FULL (compressed) board must match */
 		__device__ inline int cache_seek(const EngineDev &E, const DNode *nodes, const int *ht, u64 hash, const u64 *cboard, int sign, int lane)
 		{

@@ -216,6 +216,8 @@ namespace
 		if (!gs.active || gs.error != 0 || gs.outcome != 0 || gs.grow_pending)
 			return; // (grow_pending: the previous batch still waits for its expansion in larger arenas)
 		use_game_arenas(E, tg);
+		if (E.match_merged)
+			use_player_search(E, g);
 		for (int i = lane; i < 3 * (1 + E.hw); i += 64)
 			sh_keys[i] = E.nc_keys[i];
 		if (!E.shared_tree)
@@ -685,6 +687,8 @@ namespace
 		typedef SolverSharedT<(NFIX != 0) ? NFIX : MAXN> SH;
 		__shared__ SH sh;
 		const int g = E.g0 + blockIdx.x, lane = threadIdx.x;
+		if (E.match_merged)
+			use_player_search(E, g);
 		if (FUSED)
 		{
 			static_assert(offsetof(SH, act) % 8 == 0 && offsetof(SH, frames) == offsetof(SH, act) + sizeof(sh.act) && offsetof(SH, ptype) == offsetof(SH, frames) + sizeof(sh.frames)
@@ -991,7 +995,11 @@ namespace
                                nothing — at 12 waves per unit the 128-register kernel is as fast as the 168-register one —, and with 16 the launch is 8.6 % shorter */
 #endif
 	constexpr int spec_waves_per_simd(int nfix) { return (nfix == 15) ? AGX_SPEC_WAVES_15 : AGX_SPEC_WAVES; }
-	template<bool RENJU, int NFIX>
+	/* MERGED: the launch covers both players' trees of a match pool (agx_engine_select_solve_match) and every game / work item takes its
+	 * player's search settings (use_player_search).  A variant of its own, not a branch: this kernel runs at its register cap with scalar
+	 * registers spilled, and the choice as a never-taken branch cost the self-play launch 0.4 % (DESIGN: "Players with their own search
+	 * settings") — the other launches run the code they ran before. */
+	template<bool RENJU, int NFIX, bool MERGED>
 	__global__ __launch_bounds__(64, spec_waves_per_simd(NFIX)) void k_search_spec(EngineDev E, int count)
 	{
 		if (NFIX != 0)
@@ -1047,6 +1055,8 @@ namespace
 					keys_loaded = true;
 				}
 				use_game_arenas(E, E.shared_tree ? 0 : g);
+				if constexpr (MERGED)
+					use_player_search(E, g);
 				const int first = gs.solve_pending ? gs.solve_pos : 0; // a deferred game: no new descents, its batch goes on behind the committed leaves
 				if (!gs.solve_pending && !E.shared_tree)
 					select_batch(E, g, g, lane, &sh.board[0], &sh.lines[0], sel_keys);
@@ -1217,6 +1227,8 @@ namespace
 				speculative = true;
 			}
 			const int slot = g * E.batch + k;
+			if constexpr (MERGED)
+				use_player_search(E, g); // (the solver's node budget is the searching player's; the leaves of many games pass through one wave)
 			DTask &t = E.tasks[slot];
 			const uint32_t flags0 = t.flags;
 			const float moves_left0 = t.moves_left;
@@ -1267,6 +1279,7 @@ namespace
 #ifndef AGX_WIDE_BACKUP
 #define AGX_WIDE_BACKUP 1 /* Tree::backup with all levels of a path in flight at once (k_expand); 0: level by level */
 #endif
+	template<bool MERGED> // (MERGED: as k_search_spec's)
 	__global__ __launch_bounds__(64) void k_expand(EngineDev E)
 	{
 		__shared__ float e_prior[MAXHW], e_win[MAXHW], e_draw[MAXHW];
@@ -1279,6 +1292,8 @@ namespace
 		if (!gs.active || gs.error != 0 || gs.outcome != 0 || (!E.shared_tree && gs.solve_pending) || gs.grow_pending == 1 || gs.grow_pending == 3)
 			return;
 		use_game_arenas(E, tg);
+		if constexpr (MERGED)
+			use_player_search(E, g0);
 		DNode *nodes = nodes_of(E, tg, gs.arena);
 		DEdge *edges = edges_of(E, tg, gs.arena);
 		int *ht = ht_of(E, tg);
@@ -2082,6 +2097,7 @@ namespace
 	 * load -> store rounds per wave, so its duration falls with the number of waves that copy (256 -> 1024 threads: k_advance 0.36 -> see
 	 * DESIGN 6.1); the other games' workgroups leave at once. */
 	constexpr int ADV_THREADS = 1024;
+	template<bool MERGED> // (MERGED: as k_search_spec's)
 	__global__ __launch_bounds__(ADV_THREADS) void k_advance(EngineDev E)
 	{
 		constexpr int TPB = ADV_THREADS, WAVES = ADV_THREADS / 64;
@@ -2097,6 +2113,8 @@ namespace
 		if (!gs.active || gs.error != 0 || !gs.need_move || gs.solve_pending || gs.grow_pending)
 			return;
 		use_game_arenas(E, g);
+		if constexpr (MERGED)
+			use_player_search(E, g); // (the final selector is the moving player's; its partner's tree is only rebased)
 		DNode *nodes = nodes_of(E, g, gs.arena);
 		DEdge *edges = edges_of(E, g, gs.arena);
 		const int n = E.n;
@@ -2989,6 +3007,33 @@ namespace
 		out[1] = proven;
 		out[2] = gs.n_nodes;
 		out[3] = gs.error;
+	}
+	/* agx_engine_match_summary: the pairs' match scores and finished games added up by one workgroup (what EvaluationManager sums per player,
+	 * evaluation/EvaluationManager.cpp), 32 bytes for a polling loop instead of every pair's GameState.  out[0..2] = games won / drawn / lost
+	 * by the first player, out[3] = games finished.  The pairs' records are the first n_games / 2 (the first players' trees). */
+	__global__ __launch_bounds__(256) void k_match_summary(EngineDev E, long long *out)
+	{
+		__shared__ long long part[4][4]; // [wave][sum]
+		const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, pairs = E.n_games / 2;
+		long long sum[4] = { 0, 0, 0, 0 };
+		for (int i = tid; i < pairs; i += 256)
+		{
+			const GameState &gs = E.games[i];
+			sum[0] += gs.match_score[0];
+			sum[1] += gs.match_score[1];
+			sum[2] += gs.match_score[2];
+			sum[3] += gs.games_done;
+		}
+		for (int k = 0; k < 4; k++)
+		{
+			for (int o = 32; o > 0; o >>= 1)
+				sum[k] += __shfl_down(sum[k], o, 64);
+			if (lane == 0)
+				part[wave][k] = sum[k];
+		}
+		__syncthreads();
+		if (tid < 4)
+			out[tid] = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
 	}
 
 	/* Tree::getInfo(moves) / the principal variation (agx_engine_node_info / agx_engine_principal_variation): read-only walks over one tree's
@@ -3944,6 +3989,10 @@ struct AgxEngine
 		bool sizing_only = false; // agx_engine_estimate_device_bytes: dev_alloc only adds up, nothing touches a device
 		int sizing_cus = 0;
 		int *summary_dev = nullptr, *summary_host = nullptr; // agx_engine_root_summary: four words on their way back (device, pinned host)
+		long long *match_sum_dev = nullptr, *match_sum_host = nullptr; // agx_engine_match_summary: its four sums, the same way
+		// match pools: what each player searches with (agx_engine_set_player_search; both start as the pool's configuration).  dev's own
+		// fields stay the pool's: has_q and tss_max_nodes there are what the pool was ALLOCATED for, the upper bounds of a player's
+		PlayerSearchDev player[2];
 		// agx_engine_node_info / agx_engine_principal_variation: the paths on their way to the device and the answers on their way back, one
 		// staging buffer each side (grown on demand)
 		uint8_t *query_dev = nullptr, *query_host = nullptr;
@@ -4100,19 +4149,58 @@ int agx_engine_default_config(AgxEngineConfig *cfg)
 #endif
 /* the instantiation of k_search_spec a pool of these rules and board size launches */
 typedef void (*SpecKernel)(EngineDev, int);
-static SpecKernel spec_kernel(int rules, int n)
-{
+static SpecKernel spec_kernel(int rules, int n, bool merged = false)
+{ // merged: the variant for a match pool's launch over both players' trees (k_search_spec's MERGED)
 #ifdef AGX_QUICK
 	(void) rules;
 	(void) n;
-	return k_search_spec<AGX_QUICK_RENJU, 15>;
+	return merged ? k_search_spec<AGX_QUICK_RENJU, 15, true> : k_search_spec<AGX_QUICK_RENJU, 15, false>;
 #else
 	if (rules == AGX_RENJU)
-		return (n == 15) ? k_search_spec<true, 15> : k_search_spec<true, 0>;
+	{
+		if (n == 15)
+			return merged ? k_search_spec<true, 15, true> : k_search_spec<true, 15, false>;
+		return merged ? k_search_spec<true, 0, true> : k_search_spec<true, 0, false>;
+	}
 	if (n == 15)
-		return k_search_spec<false, 15>;
-	return (n == 20) ? k_search_spec<false, 20> : k_search_spec<false, 0>;
+		return merged ? k_search_spec<false, 15, true> : k_search_spec<false, 15, false>;
+	if (n == 20)
+		return merged ? k_search_spec<false, 20, true> : k_search_spec<false, 20, false>;
+	return merged ? k_search_spec<false, 0, true> : k_search_spec<false, 0, false>;
 #endif
+}
+/* a player's search settings <-> the plain fields of a launch's EngineDev (what the kernels read) */
+static PlayerSearchDev player_of(const EngineDev &d)
+{
+	PlayerSearchDev p;
+	p.max_sims = d.max_sims;
+	p.batch_limit = d.batch_limit;
+	p.c_puct = d.c_puct;
+	p.c_scale = d.c_scale;
+	p.init_to = d.init_to;
+	p.leak_threshold = d.leak_threshold;
+	p.expansion_threshold = d.expansion_threshold;
+	p.max_children = d.max_children;
+	p.policy_temperature = d.policy_temperature;
+	p.tss_max_nodes = d.tss_max_nodes;
+	p.final_selector = d.final_selector;
+	p.has_q = d.has_q;
+	return p;
+}
+static void use_player(EngineDev &d, const PlayerSearchDev &p)
+{
+	d.max_sims = p.max_sims;
+	d.batch_limit = p.batch_limit;
+	d.c_puct = p.c_puct;
+	d.c_scale = p.c_scale;
+	d.init_to = p.init_to;
+	d.leak_threshold = p.leak_threshold;
+	d.expansion_threshold = p.expansion_threshold;
+	d.max_children = p.max_children;
+	d.policy_temperature = p.policy_temperature;
+	d.tss_max_nodes = p.tss_max_nodes;
+	d.final_selector = p.final_selector;
+	d.has_q = p.has_q;
 }
 /* how many of its one-wave workgroups a compute unit keeps resident (LDS state and registers of that instantiation; asked of the runtime, 12 if it will not say) */
 static int spec_resident_waves_per_cu(int rules, int n)
@@ -4305,6 +4393,7 @@ static int engine_create(const AgxEngineConfig *cfg, AgxEngine **out, int sizing
 	d.grp_first = 0;
 	d.grp_count = static_cast<int>(G);
 	d.policy_temperature = cfg->policy_temperature;
+	e->player[0] = e->player[1] = player_of(d);
 	AGX_TRY(dev_alloc(e, &d.nn_q, d.has_q ? G * d.batch * d.hw * 2 : 1));
 	AGX_TRY(dev_alloc(e, &d.noise, d.noise_type ? G * d.hw : 1));
 	AGX_TRY(dev_alloc(e, &d.nn_list, G * d.batch));
@@ -4403,6 +4492,8 @@ int agx_engine_destroy(AgxEngine *e)
 		(void) hipEventDestroy(ev);
 	if (e->summary_host != nullptr)
 		(void) hipHostFree(e->summary_host);
+	if (e->match_sum_host != nullptr)
+		(void) hipHostFree(e->match_sum_host);
 	if (e->query_host != nullptr)
 		(void) hipHostFree(e->query_host);
 	delete e;
@@ -4475,6 +4566,8 @@ static int group_range(const AgxEngine *e, int group, int n_groups, EngineDev &d
 			"a tournament-search pool (search_threads) is one tree: it is stepped as a whole, or buffer by buffer (2 groups) when search_buffers = 2 — not in %d groups", n_groups);
 	d.grp_first = d.g0;
 	d.grp_count = count;
+	if (d.match_mode) // a group of a match pool is one player's trees: the launch searches with that player's settings (agx_engine_set_player_search)
+		use_player(d, e->player[(d.g0 >= d.n_games / 2) ? 1 : 0]);
 	return AGX_OK;
 }
 
@@ -4515,7 +4608,7 @@ static void launch_search_spec(EngineDev d, int count, int group, int waves, hip
 	d.spec_group = group;
 	d.spec_waves = waves;
 	const dim3 grid(waves), block(64);
-	hipLaunchKernelGGL(spec_kernel(d.rules, d.n), grid, block, 0, s, d, count);
+	hipLaunchKernelGGL(spec_kernel(d.rules, d.n, d.match_merged != 0), grid, block, 0, s, d, count);
 }
 static void launch_solve(const EngineDev &d, int count, hipStream_t s, bool with_select = false)
 {
@@ -4644,6 +4737,9 @@ static int match_launch(AgxEngine *e, EngineDev &d)
 	d.nn_counter = 16;
 	d.yield_counter = 32;
 	d.match_merged = 1;
+	d.player[0] = e->player[0]; // the kernels pick a tree's settings by its half of the pool (dev::use_player_search)
+	d.player[1] = e->player[1];
+	use_player(d, e->player[0]);
 	return AGX_OK;
 }
 int agx_engine_select_solve_match(AgxEngine *e, void *stream)
@@ -4689,12 +4785,12 @@ int agx_engine_expand_backup_match(AgxEngine *e, void *stream)
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	{
 		KernelTimer t(e, s, 2);
-		hipLaunchKernelGGL(k_expand, dim3(d.n_games), dim3(64), 0, s, d);
+		hipLaunchKernelGGL(k_expand<true>, dim3(d.n_games), dim3(64), 0, s, d);
 	}
 	{
 		KernelTimer t(e, s, 3);
 		// a moving tree's workgroup also rebases its partner's tree; the partner's own workgroup has nothing to do (it is not searching)
-		hipLaunchKernelGGL(k_advance, dim3(d.n_games), dim3(ADV_THREADS), 0, s, d);
+		hipLaunchKernelGGL(k_advance<true>, dim3(d.n_games), dim3(ADV_THREADS), 0, s, d);
 		hipLaunchKernelGGL(k_arena_service, dim3(1), dim3(1024), 0, s, d, d.n_games, 0);
 		hipLaunchKernelGGL(k_arena_copy, dim3(d.n_games * CLEAR_PARTS), dim3(256), 0, s, d, CLEAR_PARTS); // (its last part per game commits)
 		hipLaunchKernelGGL(k_assign_openings, dim3(1), dim3(1024), 0, s, d, d.n_games / 2);
@@ -4706,6 +4802,19 @@ int agx_engine_expand_backup_match(AgxEngine *e, void *stream)
 }
 int agx_engine_step_match(AgxEngine *e, AgxNet *first_net, AgxNet *second_net, void *stream)
 {
+	if (e != nullptr && e->dev.match_mode && first_net != nullptr && second_net != nullptr)
+	{ // a network without the head a player asks for is refused before anything is launched, not between the two players' forwards
+		AgxNet *nets[2] = { first_net, second_net };
+		for (int p = 0; p < 2; p++)
+		{
+			AgxNetDesc desc;
+			const int ds = agx_net_description(nets[p], &desc);
+			if (ds != AGX_OK)
+				return ds;
+			AGX_REQUIRE(!e->player[p].has_q || desc.action_values, AGX_ERR_INVALID,
+					"agx_engine_step_match: the %s player is configured for a 'pvq' network but its network has no action-values head", p == 0 ? "first" : "second");
+		}
+	}
 	int st = agx_engine_select_solve_match(e, stream);
 	if (st == AGX_OK)
 		st = agx_engine_evaluate_group(e, first_net, 0, 2, stream);
@@ -4756,7 +4865,7 @@ static int expand_stage(AgxEngine *e, int group, int n_groups, void *stream, boo
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	{
 		KernelTimer t(e, s, 2);
-		hipLaunchKernelGGL(k_expand, dim3(d.shared_tree ? 1 : count), dim3(64), 0, s, d);
+		hipLaunchKernelGGL(k_expand<false>, dim3(d.shared_tree ? 1 : count), dim3(64), 0, s, d);
 	}
 	if (service_arenas && e->external_moves && !d.match_mode)
 	{ // a caller that makes the moves itself (set_board) never runs the advance stage: the trees that asked for larger arenas get them here
@@ -4795,7 +4904,7 @@ int agx_engine_advance_group(AgxEngine *e, int group, int n_groups, void *stream
 			d.g0 = 0;
 			count = d.n_games;
 		}
-		hipLaunchKernelGGL(k_advance, dim3(trees), dim3(ADV_THREADS), 0, s, d);
+		hipLaunchKernelGGL(k_advance<false>, dim3(trees), dim3(ADV_THREADS), 0, s, d);
 		// four launches behind k_advance instead of seven (round 6): the openings are assigned by the service workgroup, a game's last copy part
 		// commits its larger arenas, a game's last clear part restarts it
 		hipLaunchKernelGGL(k_arena_service, dim3(1), dim3(1024), 0, s, d, trees, d.match_mode ? 0 : trees);
@@ -4980,6 +5089,7 @@ int agx_engine_set_batch_size(AgxEngine *e, int batch_size)
 	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_engine_set_batch_size: null engine");
 	AGX_REQUIRE(batch_size >= 1 && batch_size <= e->dev.batch, AGX_ERR_INVALID, "agx_engine_set_batch_size: %d outside [1, max_batch_size = %d]", batch_size, e->dev.batch);
 	e->dev.batch_limit = batch_size;
+	e->player[0].batch_limit = e->player[1].batch_limit = batch_size; // (a match pool: both players, as before; agx_engine_set_player_search sets one)
 	return AGX_OK;
 }
 int agx_engine_root_summary(AgxEngine *e, int game, void *stream, int *out4)
@@ -5157,6 +5267,83 @@ int agx_engine_set_max_simulations(AgxEngine *e, int max_simulations)
 	AGX_REQUIRE(e != nullptr && max_simulations > 0, AGX_ERR_INVALID, "agx_engine_set_max_simulations: invalid argument");
 	e->dev.max_sims = max_simulations;
 	e->cfg.max_simulations = max_simulations;
+	e->player[0].max_sims = e->player[1].max_sims = max_simulations; // (a match pool: both players, as before; agx_engine_set_player_search sets one)
+	return AGX_OK;
+}
+
+/* ---- match pools: search settings per player (evaluation/Player.cpp:64-81 takes them from the player's own SelfplayConfig) ---- */
+int agx_engine_player_search(AgxEngine *e, int player, AgxPlayerSearch *out)
+{
+	AGX_REQUIRE(e != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_engine_player_search: null argument");
+	AGX_REQUIRE(e->dev.match_mode, AGX_ERR_STATE, "agx_engine_player_search: the engine was not created with match_mode");
+	AGX_REQUIRE(player == 0 || player == 1, AGX_ERR_INVALID, "agx_engine_player_search: player must be 0 (first) or 1 (second), not %d", player);
+	const PlayerSearchDev &p = e->player[player];
+	out->max_simulations = p.max_sims;
+	out->max_batch_size = p.batch_limit;
+	out->exploration_constant = p.c_puct;
+	out->exploration_scaling = p.c_scale;
+	out->init_to = p.init_to;
+	out->information_leak_threshold = p.leak_threshold;
+	out->max_children = (p.max_children == 0x7FFFFFFF) ? 0 : p.max_children;
+	out->policy_expansion_threshold = p.expansion_threshold;
+	out->policy_temperature = p.policy_temperature;
+	out->tss_max_positions = p.tss_max_nodes;
+	out->final_selector = p.final_selector;
+	out->action_values = p.has_q;
+	return AGX_OK;
+}
+int agx_engine_set_player_search(AgxEngine *e, int player, const AgxPlayerSearch *in)
+{
+	AGX_REQUIRE(e != nullptr && in != nullptr, AGX_ERR_INVALID, "agx_engine_set_player_search: null argument");
+	AGX_REQUIRE(e->dev.match_mode, AGX_ERR_STATE, "agx_engine_set_player_search: the engine was not created with match_mode");
+	AGX_REQUIRE(player == 0 || player == 1, AGX_ERR_INVALID, "agx_engine_set_player_search: player must be 0 (first) or 1 (second), not %d", player);
+	// (max_simulations below 50: the move rule's threshold can exceed what select ever reaches, AgxEngineConfig.max_simulations.  The pool-wide
+	// agx_engine_set_max_simulations keeps accepting any positive value, as before; a player left below 50 by it has to be given a
+	// max_simulations >= 50 along with whatever else this call changes)
+	AGX_REQUIRE(in->max_simulations >= 50, AGX_ERR_INVALID, "agx_engine_set_player_search: max_simulations must be at least 50, not %d", in->max_simulations);
+	AGX_REQUIRE(in->max_batch_size >= 1 && in->max_batch_size <= e->dev.batch, AGX_ERR_INVALID, "agx_engine_set_player_search: max_batch_size %d outside [1, max_batch_size = %d]",
+			in->max_batch_size, e->dev.batch);
+	AGX_REQUIRE(in->init_to >= 0 && in->init_to <= 3, AGX_ERR_INVALID, "agx_engine_set_player_search: init_to must be 0..3");
+	AGX_REQUIRE(in->tss_max_positions >= 1 && in->tss_max_positions <= e->dev.tss_max_nodes, AGX_ERR_INVALID,
+			"agx_engine_set_player_search: tss_max_positions must be in [1, %d] (the pool's)", e->dev.tss_max_nodes);
+	AGX_REQUIRE(in->final_selector >= 0 && in->final_selector <= 5, AGX_ERR_INVALID, "agx_engine_set_player_search: final_selector must be 0..5");
+	AGX_REQUIRE(in->policy_temperature >= 0.0f, AGX_ERR_INVALID, "agx_engine_set_player_search: policy_temperature must not be negative");
+	AGX_REQUIRE(in->action_values == 0 || in->action_values == 1, AGX_ERR_INVALID, "agx_engine_set_player_search: action_values must be 0 or 1");
+	AGX_REQUIRE(in->action_values == 0 || e->dev.has_q, AGX_ERR_INVALID,
+			"agx_engine_set_player_search: action_values = 1 needs a pool created with action_values = 1 (it has no action-values exchange buffer)");
+	PlayerSearchDev &p = e->player[player];
+	p.max_sims = in->max_simulations;
+	p.batch_limit = in->max_batch_size;
+	p.c_puct = in->exploration_constant;
+	p.c_scale = in->exploration_scaling;
+	p.init_to = in->init_to;
+	p.leak_threshold = in->information_leak_threshold;
+	p.max_children = (in->max_children > 0) ? in->max_children : 0x7FFFFFFF;
+	p.expansion_threshold = in->policy_expansion_threshold;
+	p.policy_temperature = in->policy_temperature;
+	p.tss_max_nodes = in->tss_max_positions;
+	p.final_selector = in->final_selector;
+	p.has_q = in->action_values;
+	return AGX_OK;
+}
+int agx_engine_match_summary(AgxEngine *e, long long out[4], void *stream)
+{
+	AGX_REQUIRE(e != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_engine_match_summary: null argument");
+	AGX_REQUIRE(e->dev.match_mode, AGX_ERR_STATE, "agx_engine_match_summary: the engine was not created with match_mode");
+	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_match_summary: agx_engine_begin has not been called");
+	if (e->match_sum_dev == nullptr)
+	{
+		AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->match_sum_dev), 4 * sizeof(long long)));
+		e->allocations.push_back(e->match_sum_dev);
+	}
+	if (e->match_sum_host == nullptr) // (on its own: a call whose second allocation failed must not leave the next one a null pointer)
+		AGX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e->match_sum_host), 4 * sizeof(long long), hipHostMallocDefault));
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	hipLaunchKernelGGL(k_match_summary, dim3(1), dim3(256), 0, s, e->dev, e->match_sum_dev);
+	AGX_HIP_CHECK(hipGetLastError());
+	AGX_HIP_CHECK(hipMemcpyAsync(e->match_sum_host, e->match_sum_dev, 4 * sizeof(long long), hipMemcpyDeviceToHost, s));
+	AGX_HIP_CHECK(hipStreamSynchronize(s));
+	std::memcpy(out, e->match_sum_host, 4 * sizeof(long long));
 	return AGX_OK;
 }
 int agx_engine_speculative_waves(AgxEngine *e, int *waves)

@@ -200,6 +200,19 @@ namespace agx
 		ERR_OVERLAY = 100 // internal to speculative solves (overlay full): never reported, the task is solved again serially
 	};
 
+	/* The search settings a match player owns (AgxPlayerSearch, evaluation/Player.cpp:64-81): the same fields, under the same names, as
+	 * EngineDev's pool-wide ones.  max_children is kept in its device form (0x7FFFFFFF = unlimited). */
+	struct PlayerSearchDev
+	{
+			int max_sims, batch_limit;
+			float c_puct, c_scale;
+			int init_to;
+			float leak_threshold, expansion_threshold;
+			int max_children;
+			float policy_temperature;
+			int tss_max_nodes, final_selector, has_q;
+	};
+
 	struct EngineDev
 	{
 			// configuration
@@ -293,6 +306,10 @@ namespace agx
 			DEdge *record_edges;
 			uint8_t *samples;      // format-201 bytes, one 4-byte aligned block per recorded move
 			GameEndRecord *game_ends;
+			// match mode, merged launches only (match_merged): the settings of the first and the second player.  A kernel that works on tree g
+			// overrides the plain fields above in its by-value copy of E with player[g >= n_games / 2] (dev::use_player_search); every other
+			// launch — self-play, tournament, position search, a match pool stepped group by group — reads the plain fields as the host wrote them
+			PlayerSearchDev player[2];
 	};
 }
 

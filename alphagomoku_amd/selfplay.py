@@ -8,9 +8,10 @@ import ctypes
 import numpy as np
 
 from ._lib import (lib, check, AgxEngineConfig, AgxEngineBuffers, AgxEngineStats, AgxGameInfo, AgxEdgeView, AgxMoveRecord, AgxGameEnd, AgxSavedGame,
-                   AgxRecordCounts, AgxGameBufferStats, AgxNodeView)
+                   AgxRecordCounts, AgxGameBufferStats, AgxNodeView, AgxPlayerSearch)
 
 OPENING_CAP = 32
+PLAYER_SEARCH_FIELDS = tuple(name for name, _ in AgxPlayerSearch._fields_)
 
 
 def default_config(**overrides):
@@ -384,6 +385,30 @@ class GeneratorPool:
         out = np.zeros((self.cfg.n_games // 2, 4), np.int32)
         check(lib.agx_engine_match_results(self._h, out.ctypes.data_as(ctypes.c_void_p), out.shape[0]))
         return out
+
+    def match_summary(self, stream=None):
+        """dict(wins, draws, losses, games): the first player's results over all pairs and the games finished, summed on the device (one
+        small launch and 32 bytes behind `stream`: what a polling loop reads instead of match_results())"""
+        out = (ctypes.c_longlong * 4)()
+        check(lib.agx_engine_match_summary(self._h, out, stream))
+        return dict(wins=int(out[0]), draws=int(out[1]), losses=int(out[2]), games=int(out[3]))
+
+    def player_search(self, player):
+        """what player 0 (first) / 1 (second) of a match_mode pool searches with now: a dict of the AgxPlayerSearch fields"""
+        p = AgxPlayerSearch()
+        check(lib.agx_engine_player_search(self._h, int(player), ctypes.byref(p)))
+        return {name: getattr(p, name) for name, _ in p._fields_}
+
+    def set_player_search(self, player, **fields):
+        """gives one player of a match_mode pool search settings of its own from the next step on (evaluation/Player.cpp:64-81: every player
+        has its own SelfplayConfig); fields that are not named keep their current value"""
+        p = AgxPlayerSearch()
+        check(lib.agx_engine_player_search(self._h, int(player), ctypes.byref(p)))
+        for k, v in fields.items():
+            if k not in PLAYER_SEARCH_FIELDS:
+                raise KeyError(k)
+            setattr(p, k, v)
+        check(lib.agx_engine_set_player_search(self._h, int(player), ctypes.byref(p)))
 
     def add_openings(self, packed_openings):
         """appends openings (pack_openings layout) for the games that finish from now on"""

@@ -544,6 +544,42 @@ int agx_engine_expand_backup_match(AgxEngine* engine, void* stream); /* agx_engi
 /* Match mode: h_results int[n_games / 2][4] = games won / drawn / lost by the FIRST player of each pair and the games the pair has
  * finished (what EvaluationManager sums per player, evaluation/EvaluationManager.cpp); the moves of every game are in the records. */
 int agx_engine_match_results(AgxEngine* engine, int* h_results, int pair_capacity);
+/* The same totals over all pairs, added up on the device by one small launch behind the work `stream` holds: out[0..2] = games won / drawn /
+ * lost by the first player, out[3] = games finished.  Waits for THAT stream only and copies 32 bytes — what a loop that polls "are all
+ * games played?" wants instead of agx_engine_match_results' device-wide synchronise and its copy of every pair's record. */
+int agx_engine_match_summary(AgxEngine* engine, long long out[4], void* stream);
+/* Match mode: each player with search settings of its own.  The reference hands every player of an evaluation game a SelfplayConfig
+ * (EvaluationGame::setFirstPlayer / setSecondPlayer; evaluation/Player.cpp:64-81 takes search_config, final_selector,
+ * constraints.max_simulations and max_batch_size from it), which is how tuning_launcher plays a base configuration against a tested one on
+ * one network.  Both players of a pool start with the pool's AgxEngineConfig; agx_engine_set_player_search replaces one player's settings
+ * from the next stage launch on (call it between two steps), agx_engine_player_search reports what a player searches with now.  player 0 is
+ * the first player (trees 0 .. n_games/2 - 1), player 1 the second.  agx_engine_set_max_simulations / agx_engine_set_batch_size keep their
+ * meaning: they set that field for BOTH players; the last call wins.  Root noise, use_symmetries and the seeds, the table and arena sizes,
+ * draw_after, the yield / speculative settings and the pruned root stay the pool's.
+ * Status: AGX_ERR_STATE on a pool without match_mode; AGX_ERR_INVALID (agx_last_error names the field and its range) for a null argument, a
+ * player other than 0 / 1 and a field outside the range given below — the call then changes nothing. */
+typedef struct AgxPlayerSearch
+{
+	int max_simulations;              /* Constraints::max_simulations of this player, >= 50 (see AgxEngineConfig.max_simulations).  NB the pool and
+	                                     agx_engine_set_max_simulations only ADVISE >= 50 and accept any positive value: a player they left below
+	                                     50 is reported as it is, and a set call for that player must raise max_simulations to >= 50 too */
+	int max_batch_size;               /* Search::setBatchSize: 1 .. the pool's max_batch_size (the task buffers keep the pool's stride) */
+	float exploration_constant;
+	float exploration_scaling;
+	int init_to;                      /* 0..3 as AgxEngineConfig */
+	float information_leak_threshold;
+	int max_children;                 /* 0 = unlimited */
+	float policy_expansion_threshold;
+	float policy_temperature;         /* >= 0 */
+	int tss_max_positions;            /* 1 .. the pool's tss_max_positions (allocations and the speculative decision stay the pool's) */
+	int final_selector;               /* 0..5 as AgxEngineConfig */
+	int action_values;                /* 0: this player's network is a 'pv' network, its new edges start at (0, 0); 1: a 'pvq' network — only in a
+	                                     pool created with action_values = 1 (the action-values exchange buffer exists).  agx_engine_evaluate_group /
+	                                     agx_engine_step_match run the 'pvq' forward for a player that asks for it and refuse a network without the
+	                                     head for that player only: a 'pv' generation can be gated against the 'pvq' one that replaces it. */
+} AgxPlayerSearch;
+int agx_engine_player_search(AgxEngine* engine, int player, AgxPlayerSearch* out);
+int agx_engine_set_player_search(AgxEngine* engine, int player, const AgxPlayerSearch* in);
 /* Appends openings to the pool's list.  Finished games take the next unused opening in game order after every step; games that
  * found none left wait and pick one up here (the reference's generators produce openings on demand, GameGenerator.cpp:54-77). */
 int agx_engine_add_openings(AgxEngine* engine, const uint16_t* h_openings, int n_openings);

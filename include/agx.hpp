@@ -16,6 +16,7 @@
 #include "agx.h"
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -410,6 +411,26 @@ namespace agx
 				std::vector<int> out(static_cast<size_t>(m_buffers.slots) * 4);
 				check(agx_engine_match_results(m_engine, out.data(), static_cast<int>(out.size() / 4)));
 				return out;
+			}
+			/* the same totals over all pairs — { won, drawn, lost by the first player, games finished } — summed on the device behind the
+			 * work `stream` holds: 32 bytes for a polling loop (agx_engine_match_summary) */
+			std::array<long long, 4> matchSummary(void *stream = nullptr) const
+			{
+				std::array<long long, 4> out { };
+				check(agx_engine_match_summary(m_engine, out.data(), stream));
+				return out;
+			}
+			/* what player 0 (first) / 1 (second) of an evaluation pool searches with (evaluation/Player.cpp:64-81: every Player takes these from
+			 * its own SelfplayConfig); both start with the pool's configuration.  setPlayerSearch holds from the next generate() on. */
+			AgxPlayerSearch playerSearch(int player) const
+			{
+				AgxPlayerSearch out { };
+				check(agx_engine_player_search(m_engine, player, &out));
+				return out;
+			}
+			void setPlayerSearch(int player, const AgxPlayerSearch &search)
+			{
+				check(agx_engine_set_player_search(m_engine, player, &search));
 			}
 			/* the three stages separately (Search::select+solve+scheduleToNN / NNEvaluator::evaluateGraph / generateEdges+expand+backup) */
 			void selectSolveSchedule(void *stream = nullptr)
