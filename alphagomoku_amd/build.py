@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libagx.so")
 
 INCLUDE = os.path.join(HERE, "..", "include")
-SOURCES = ["agx_api.hip", "nn_forward.hip", "nn_any_board.hip", "nn_any_board_bottleneck.hip", "nn_convnext.hip", "engine.hip", "training_batch.hip", "net_score.hip", "head_loss.hip", "position_eval.hip", "nn_net.cpp", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
+SOURCES = ["agx_api.hip", "nn_forward.hip", "nn_any_board.hip", "nn_any_board_bottleneck.hip", "nn_layered.hip", "nn_convnext.hip", "engine.hip", "training_batch.hip", "net_score.hip", "head_loss.hip", "position_eval.hip", "nn_net.cpp", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
 DRIVER = os.path.join(HERE, "agx_selfplay")
 AG_LIB = os.path.join(HERE, "libagx_ag.so")               # the reference-named C++ classes (include/alphagomoku_agx/) over the C ABI
 BOUNDARY_TEST = os.path.join(HERE, "agx_boundary_test")  # tests/cpp/boundary_main.cpp: the reference's call chain on those classes
@@ -31,6 +31,8 @@ CONVNEXT_TEST = os.path.join(HERE, "agx_convnext_test")  # tests/cpp/convnext_ma
 CONVNEXT_SRC = os.path.join(HERE, "..", "tests", "cpp", "convnext_main.cpp")
 BOTTLENECK_TEST = os.path.join(HERE, "agx_bottleneck_test")  # tests/cpp/bottleneck_main.cpp: the bottleneck architectures through ag::AGNetwork, container included
 BOTTLENECK_SRC = os.path.join(HERE, "..", "tests", "cpp", "bottleneck_main.cpp")
+LAYERED_TEST = os.path.join(HERE, "agx_layered_test")  # tests/cpp/layered_main.cpp: a 256-filter residual network through ag::AGNetwork, container included
+LAYERED_SRC = os.path.join(HERE, "..", "tests", "cpp", "layered_main.cpp")
 # the host test programs: (target, source, libraries, depends on libagx_ag.so); one without the reference-named classes is relinked with libagx.so
 HOST_TESTS = [
     (BOUNDARY_TEST, BOUNDARY_SRC, ["-lagx_ag", "-lagx"], True),
@@ -40,6 +42,7 @@ HOST_TESTS = [
     (TARGETS_TEST, TARGETS_SRC, ["-lagx"], False),
     (CONVNEXT_TEST, CONVNEXT_SRC, ["-lagx_ag", "-lagx"], True),
     (BOTTLENECK_TEST, BOTTLENECK_SRC, ["-lagx_ag", "-lagx"], True),
+    (LAYERED_TEST, LAYERED_SRC, ["-lagx_ag", "-lagx"], True),
 ]
 HOST_ONLY = ("ag_classes.cpp", "selfplay_main.cpp")  # plain g++ sources in csrc/ (not part of libagx.so)
 

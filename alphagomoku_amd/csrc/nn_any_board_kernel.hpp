@@ -33,7 +33,7 @@
  *
  * Numerics: fp16 weights for everything that feeds the matrix cores, fp32 accumulation from the bias (+ the residual), one rounding to fp16
  * per stored activation behind the ReLU, the last 1x1 of policy / q and all biases in fp32, q's hidden activation tanh rounded to fp16.
- * The value head's dense layers run in value_head_kernel behind the tower (agx_res::launch, nn_forward.hip), K = 4 * rows * cols padded to 32.
+ * The value head's dense layers run in value_head_kernel (nn_device.hpp) behind the tower (agx_res::launch, nn_forward.hip), K = 4 * rows * cols padded to 32.
  * The types, the launch record and the helpers shared with nn_forward.hip are in nn_device.hpp.
  *
  * Slower per FLOP than the two specialised kernels (DESIGN.md 3.1 has the measured ratios): no row- or column-stationary reuse of
@@ -726,7 +726,7 @@ namespace
 			const float *b_heads = p.bias + F + p.blocks * BLOCK_BIAS;
 
 			// ---- value head, stage 1: conv1x1 F -> 4 + ReLU as one 16 x 16 MFMA tile per 16 positions (4 of the 16 units are real), the tiles dealt
-			//      round-robin to the waves; the dense layers run in value_head_kernel (nn_forward.hip) for all boards of the launch ----
+			//      round-robin to the waves; the dense layers run in value_head_kernel (nn_device.hpp) for all boards of the launch ----
 			{
 				const int r = lane & 15, q4 = lane >> 4;
 				for (int n = wave; n < sh.NT; n += C::THREADS / 64)

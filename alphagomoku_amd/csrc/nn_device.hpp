@@ -1,9 +1,9 @@
 /*
  * nn_device.hpp — the device code that the network kernel files share: nn_forward.hip (the 15x15 and 20x20 towers, the value head's
  * dense layers, the residual towers' host side), nn_any_board.hip (the run-time-shaped towers, residual and bottleneck blocks) and, for the
- * types and mfma_settle() / own(), nn_convnext.hip.  The vector types, the launch record NetParams, the small
+ * types and mfma_settle() / own(), nn_convnext.hip; nn_layered.hip (the layered towers) takes the types, the helpers and value_head_kernel.  The vector types, the launch record NetParams, the small
  * helpers of the layers (LDS barrier, MFMA settle, fp16 + fp32 add, carried bias values, workgroup reductions) and the pieces both towers run word for
- * word: the unpacking of a feature byte, the staging of the heads' 1x1 weights, the action-values softmax.  The functions are in the unnamed
+ * word: the unpacking of a feature byte, the staging of the heads' 1x1 weights, the action-values softmax, the value head's dense kernel.  The functions are in the unnamed
  * namespace and forced inline: each .hip file gets its own copy, exactly as if the text stood there.  The types are in agx_nn: NetParams
  * crosses from one file to the other (agx_any::launch), and a function over a type of the unnamed namespace cannot be linked.
  */
@@ -210,6 +210,75 @@ namespace
 			return (ppart[idx] + ppart[PS + idx]) + (ppart[2 * PS + idx] + ppart[3 * PS + idx]);
 		else
 			return ppart[idx] + ppart[PS + idx];
+	}
+
+	/*
+	 * Value head behind the tower, for every board of a launch: hidden = ReLU(W2^T x + b2) (4 HW -> D), out = softmax(W3^T hidden + b3)
+	 * (createValueHead, blocks.cpp:108-118).  One workgroup = 16 boards (one MFMA position tile) x all D hidden units: wave w owns the
+	 * 16-unit tiles w * D/64 .. and walks K in 32-input steps (weights pre-packed in A-fragment order: pack_value_dense, nn_pack.hpp; the
+	 * boards' inputs are rows of kpad halves: value_kpad()).  3.1 GFLOP for a whole self-play batch — microseconds.  The one kernel behind every
+	 * tower — the fixed-shape ones, the run-time-shaped one and the layered one (nn_layered.hip): the input length is an argument.
+	 */
+	template<int D>
+	__global__ __launch_bounds__(256) void value_head_kernel(const half_t *__restrict__ x, const half8 *__restrict__ w2, const float *__restrict__ b2,
+			const float *__restrict__ w3, float b30, float b31, float b32, const int *__restrict__ slot_list, const int *__restrict__ count_ptr, int batch_cap,
+			int kpad, float *__restrict__ value)
+	{
+		constexpr int MTW = D / 64; // 16-unit tiles per wave
+		__shared__ float hid[16][D + 1];
+		const int batch = (count_ptr != nullptr) ? min(*count_ptr, batch_cap) : batch_cap;
+		const int b0 = blockIdx.x * 16;
+		if (b0 >= batch)
+			return;
+		const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q4 = lane >> 4;
+		const int board = min(b0 + r, batch - 1); // the tail tile repeats the last board (never stored)
+		floatx4 acc[MTW];
+#pragma unroll
+		for (int i = 0; i < MTW; i++)
+			acc[i] = floatx4 { 0.0f, 0.0f, 0.0f, 0.0f };
+		const half8 *xb = reinterpret_cast<const half8*>(x + static_cast<size_t>(board) * kpad) + q4;
+		const half8 *wp = w2 + (wave * MTW) * 64 + lane;
+		const int ksteps = kpad / 32;
+		for (int kc = 0; kc < ksteps; kc++)
+		{
+			const half8 bfrag = xb[kc * 4];
+#pragma unroll
+			for (int i = 0; i < MTW; i++)
+				acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wp[(kc * (D / 16) + i) * 64], bfrag, acc[i], 0, 0, 0);
+		}
+		// lane holds hidden units 4 * q4 .. + 3 of tile i for board r
+#pragma unroll
+		for (int i = 0; i < MTW; i++)
+		{
+			const int u = (wave * MTW + i) * 16 + 4 * q4;
+#pragma unroll
+			for (int e = 0; e < 4; e++)
+				hid[r][u + e] = fmaxf(acc[i][e] + b2[u + e], 0.0f);
+		}
+		__syncthreads();
+		// 16 boards x 3 outputs: threads 0 .. 47 each reduce one (board, output) pair in a fixed order
+		__shared__ float logits[16][3];
+		if (tid < 48)
+		{
+			const int bb = tid / 3, o = tid % 3;
+			float sacc = 0.0f;
+			for (int j = 0; j < D; j++)
+				sacc += hid[bb][j] * w3[j * 3 + o];
+			logits[bb][o] = sacc + ((o == 0) ? b30 : ((o == 1) ? b31 : b32));
+		}
+		__syncthreads();
+		if (tid < 16 && b0 + tid < batch)
+		{
+			const int bi = b0 + tid;
+			const int slot = (slot_list != nullptr) ? slot_list[bi] : bi;
+			const float z0 = logits[tid][0], z1 = logits[tid][1], z2 = logits[tid][2];
+			const float m = fmaxf(z0, fmaxf(z1, z2));
+			const float e0 = __expf(z0 - m), e1 = __expf(z1 - m), e2 = __expf(z2 - m);
+			const float inv = 1.0f / (e0 + e1 + e2);
+			value[static_cast<size_t>(slot) * 3 + 0] = e0 * inv;
+			value[static_cast<size_t>(slot) * 3 + 1] = e1 * inv;
+			value[static_cast<size_t>(slot) * 3 + 2] = e2 * inv;
+		}
 	}
 }
 

@@ -1700,74 +1700,7 @@ namespace
 		}
 	}
 
-	/*
-	 * Value head behind the tower, for every board of a launch: hidden = ReLU(W2^T x + b2) (4 HW -> D), out = softmax(W3^T hidden + b3)
-	 * (createValueHead, blocks.cpp:108-118).  One workgroup = 16 boards (one MFMA position tile) x all D hidden units: wave w owns the
-	 * 16-unit tiles w * D/64 .. and walks K in 32-input steps (weights pre-packed in A-fragment order, the boards' inputs are rows of
-	 * kpad halves: agx_res::Net::kpad()).  3.1 GFLOP for a whole self-play batch — microseconds.  The one kernel behind every tower, the
-	 * run-time-shaped one included: the input length is an argument.
-	 */
-	template<int D>
-	__global__ __launch_bounds__(256) void value_head_kernel(const half_t *__restrict__ x, const half8 *__restrict__ w2, const float *__restrict__ b2,
-			const float *__restrict__ w3, float b30, float b31, float b32, const int *__restrict__ slot_list, const int *__restrict__ count_ptr, int batch_cap,
-			int kpad, float *__restrict__ value)
-	{
-		constexpr int MTW = D / 64; // 16-unit tiles per wave
-		__shared__ float hid[16][D + 1];
-		const int batch = (count_ptr != nullptr) ? min(*count_ptr, batch_cap) : batch_cap;
-		const int b0 = blockIdx.x * 16;
-		if (b0 >= batch)
-			return;
-		const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q4 = lane >> 4;
-		const int board = min(b0 + r, batch - 1); // the tail tile repeats the last board (never stored)
-		floatx4 acc[MTW];
-#pragma unroll
-		for (int i = 0; i < MTW; i++)
-			acc[i] = floatx4 { 0.0f, 0.0f, 0.0f, 0.0f };
-		const half8 *xb = reinterpret_cast<const half8*>(x + static_cast<size_t>(board) * kpad) + q4;
-		const half8 *wp = w2 + (wave * MTW) * 64 + lane;
-		const int ksteps = kpad / 32;
-		for (int kc = 0; kc < ksteps; kc++)
-		{
-			const half8 bfrag = xb[kc * 4];
-#pragma unroll
-			for (int i = 0; i < MTW; i++)
-				acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wp[(kc * (D / 16) + i) * 64], bfrag, acc[i], 0, 0, 0);
-		}
-		// lane holds hidden units 4 * q4 .. + 3 of tile i for board r
-#pragma unroll
-		for (int i = 0; i < MTW; i++)
-		{
-			const int u = (wave * MTW + i) * 16 + 4 * q4;
-#pragma unroll
-			for (int e = 0; e < 4; e++)
-				hid[r][u + e] = fmaxf(acc[i][e] + b2[u + e], 0.0f);
-		}
-		__syncthreads();
-		// 16 boards x 3 outputs: threads 0 .. 47 each reduce one (board, output) pair in a fixed order
-		__shared__ float logits[16][3];
-		if (tid < 48)
-		{
-			const int bb = tid / 3, o = tid % 3;
-			float sacc = 0.0f;
-			for (int j = 0; j < D; j++)
-				sacc += hid[bb][j] * w3[j * 3 + o];
-			logits[bb][o] = sacc + ((o == 0) ? b30 : ((o == 1) ? b31 : b32));
-		}
-		__syncthreads();
-		if (tid < 16 && b0 + tid < batch)
-		{
-			const int bi = b0 + tid;
-			const int slot = (slot_list != nullptr) ? slot_list[bi] : bi;
-			const float z0 = logits[tid][0], z1 = logits[tid][1], z2 = logits[tid][2];
-			const float m = fmaxf(z0, fmaxf(z1, z2));
-			const float e0 = __expf(z0 - m), e1 = __expf(z1 - m), e2 = __expf(z2 - m);
-			const float inv = 1.0f / (e0 + e1 + e2);
-			value[static_cast<size_t>(slot) * 3 + 0] = e0 * inv;
-			value[static_cast<size_t>(slot) * 3 + 1] = e1 * inv;
-			value[static_cast<size_t>(slot) * 3 + 2] = e2 * inv;
-		}
-	}
+	/* (the value head's dense layers behind the tower: value_head_kernel, nn_device.hpp — the layered towers launch it too) */
 
 	/*
 	 * Host side.  The tap-major fragment order [tap][kc][mtile][lane][8] is pack_conv (nn_pack.hpp).  Here: the same fragments in the order the
@@ -1946,19 +1879,7 @@ namespace agx_res
 		ptr += F * 4;
 		for (int i = 0; i < 4; i++)
 			net->bv1[i] = *ptr++;
-		{ // dense 4 HW -> D in MFMA A-fragment order [k-step][16-unit tile][lane][8] (value_head_kernel), zero beyond the last input
-			const int kpad = net->kpad(), mtiles = D / 16;
-			wv2.assign(static_cast<size_t>(kpad) * D, static_cast<half_t>(0.0f));
-			for (int kc = 0; kc < kpad / 32; kc++)
-				for (int mt = 0; mt < mtiles; mt++)
-					for (int lane = 0; lane < 64; lane++)
-						for (int j = 0; j < 8; j++)
-						{
-							const int unit = mt * 16 + (lane & 15), k = kc * 32 + 8 * (lane >> 4) + j;
-							if (k < HW * 4)
-								wv2[((static_cast<size_t>(kc) * mtiles + mt) * 64 + lane) * 8 + j] = static_cast<half_t>(ptr[static_cast<size_t>(k) * D + unit]);
-						}
-		}
+		pack_value_dense(ptr, HW, D, wv2); // dense 4 HW -> D as value_head_kernel reads it
 		ptr += static_cast<size_t>(HW) * 4 * D;
 		bv2.assign(ptr, ptr + D);
 		ptr += D;

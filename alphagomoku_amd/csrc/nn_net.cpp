@@ -1,12 +1,16 @@
 /*
  * nn_net.cpp — AgxNet and every network entry point of the C ABI (include/agx.h): the small thing above the towers.  An architecture is a
  * namespace with supported / blob_floats / load / destroy / launch over an opaque Net: agx_res (nn_resnet.hpp; the kernels and their host
- * side are in nn_forward.hip; the bottleneck towers are a block kind of the same Net and of the run-time-shaped kernel, nn_any_board.hip) and agx_cnx (nn_convnext.hpp, nn_convnext.hip).  Each function below checks its arguments once and forks on
- * the architecture in one place.
+ * side are in nn_forward.hip; the bottleneck towers are a block kind of the same Net and of the run-time-shaped kernel, nn_any_board.hip), agx_lay
+ * (nn_layered.hpp, nn_layered.hip: the residual networks wider than 128 filters, a launch per layer) and agx_cnx (nn_convnext.hpp, nn_convnext.hip).
+ * Each function below checks its arguments once and forks on the architecture in one place.
  */
 #include "agx_internal.hpp"
 #include "nn_resnet.hpp"
+#include "nn_layered.hpp"
 #include "nn_convnext.hpp"
+
+#include <cstdlib>
 
 struct AgxNet
 {
@@ -15,11 +19,22 @@ struct AgxNet
 		int moves_left = 0;
 		int num_cus = 256;
 		int launch_width = 0; // 0 = every CU
-		// the loaded weights: the pointer of `architecture` is non-null once agx_net_load_weights succeeded, the other one stays null
-		// (`resnet` carries the residual and the bottleneck towers)
+		// the loaded weights: the pointer of `architecture` is non-null once agx_net_load_weights succeeded, the others stay null
+		// (`resnet` carries the residual and the bottleneck towers, `layered` the residual networks the kernels behind `resnet` do not take)
 		agx_res::Net *resnet = nullptr;
+		agx_lay::Net *layered = nullptr;
 		agx_cnx::Net *convnext = nullptr;
 };
+
+/* A residual network goes to the layered tower when its width is beyond the single-plane kernels (agx_res::supported refuses it) — or, for
+ * tests and A/B runs, whenever AGX_NN_LAYERED=1 is set while its weights are loaded. */
+static bool runs_layered(const AgxNetDesc &desc, int architecture)
+{
+	if (architecture != AGX_ARCH_RESNET || !agx_lay::supported(desc, 0))
+		return false;
+	const char *force = getenv("AGX_NN_LAYERED");
+	return !agx_res::supported(desc, 0) || (force != nullptr && force[0] == '1');
+}
 
 extern "C" {
 
@@ -30,7 +45,7 @@ size_t agx_net_blob_floats_ex(const AgxNetDesc *d, int architecture, int moves_l
 	switch (architecture)
 	{
 		case AGX_ARCH_RESNET:
-			return (moves_left == 0) ? agx_res::blob_floats(*d) : 0;
+			return (moves_left == 0) ? agx_res::blob_floats(*d) : 0; // (agx_lay::blob_floats is the same formula: one blob layout for every width)
 		case AGX_ARCH_CONVNEXT:
 			return agx_cnx::blob_floats(*d, moves_left);
 		case AGX_ARCH_BOTTLENECK:
@@ -53,8 +68,8 @@ int agx_net_create_ex(const AgxNetDesc *desc, int architecture, int moves_left, 
 		case AGX_ARCH_RESNET:
 			AGX_REQUIRE(moves_left == 0, AGX_ERR_UNSUPPORTED, "agx_net_create_ex: unsupported architecture %d with moves_left=%d (the residual networks have no moves-left head)",
 					architecture, moves_left);
-			AGX_REQUIRE(agx_res::supported(*desc, moves_left), AGX_ERR_UNSUPPORTED,
-					"agx_net_create: unsupported network %dx%d blocks=%d filters=%d cin=%d hidden=%d (supported: 5..20 rows and cols, F in {64,128}, cin 32, or cin 8 without the action-values head)",
+			AGX_REQUIRE(agx_res::supported(*desc, moves_left) || agx_lay::supported(*desc, moves_left), AGX_ERR_UNSUPPORTED,
+					"agx_net_create: unsupported network %dx%d blocks=%d filters=%d cin=%d hidden=%d (supported: 5..20 rows and cols, F a multiple of 64 from 64 to 512, hidden min(256, 2F), cin 32, or cin 8 without the action-values head)",
 					desc->rows, desc->cols, desc->blocks, desc->filters, desc->in_channels, desc->value_hidden);
 			break;
 		case AGX_ARCH_BOTTLENECK:
@@ -103,13 +118,17 @@ int agx_net_load_weights(AgxNet *net, const float *h_blob, size_t n_floats)
 	const size_t expected = agx_net_blob_floats_ex(&net->desc, net->architecture, net->moves_left);
 	AGX_REQUIRE(n_floats == expected, AGX_ERR_INVALID, "agx_net_load_weights: blob has %zu floats, expected %zu", n_floats, expected);
 	agx_res::Net *resnet = nullptr;
+	agx_lay::Net *layered = nullptr;
 	agx_cnx::Net *convnext = nullptr;
 	int status = AGX_ERR_STATE;
 	switch (net->architecture)
 	{
 		case AGX_ARCH_RESNET:
 		case AGX_ARCH_BOTTLENECK:
-			status = agx_res::load(net->desc, net->num_cus, h_blob, &resnet, net->architecture == AGX_ARCH_BOTTLENECK);
+			if (runs_layered(net->desc, net->architecture))
+				status = agx_lay::load(net->desc, h_blob, &layered);
+			else
+				status = agx_res::load(net->desc, net->num_cus, h_blob, &resnet, net->architecture == AGX_ARCH_BOTTLENECK);
 			break;
 		case AGX_ARCH_CONVNEXT:
 			status = agx_cnx::load(net->desc, net->moves_left, h_blob, &convnext);
@@ -117,13 +136,15 @@ int agx_net_load_weights(AgxNet *net, const float *h_blob, size_t n_floats)
 	}
 	if (status != AGX_OK)
 		return status;
-	if (net->resnet != nullptr || net->convnext != nullptr)
+	if (net->resnet != nullptr || net->layered != nullptr || net->convnext != nullptr)
 	{ // (launches of the old weights may be in flight)
 		AGX_HIP_CHECK(hipDeviceSynchronize());
 		agx_res::destroy(net->resnet);
+		agx_lay::destroy(net->layered);
 		agx_cnx::destroy(net->convnext);
 	}
 	net->resnet = resnet;
+	net->layered = layered;
 	net->convnext = convnext;
 	return AGX_OK;
 }
@@ -132,7 +153,7 @@ static int launch_forward(AgxNet *net, const uint32_t *d_features, const int *d_
 		float *d_action_values, void *stream, float *d_moves_left = nullptr)
 {
 	AGX_REQUIRE(net != nullptr, AGX_ERR_INVALID, "agx_nn_forward: null network");
-	AGX_REQUIRE(net->resnet != nullptr || net->convnext != nullptr, AGX_ERR_STATE, "agx_nn_forward: weights not loaded");
+	AGX_REQUIRE(net->resnet != nullptr || net->layered != nullptr || net->convnext != nullptr, AGX_ERR_STATE, "agx_nn_forward: weights not loaded");
 	AGX_REQUIRE(batch >= 0, AGX_ERR_INVALID, "agx_nn_forward: negative batch");
 	if (batch == 0)
 		return AGX_OK;
@@ -149,6 +170,8 @@ static int launch_forward(AgxNet *net, const uint32_t *d_features, const int *d_
 	{
 		case AGX_ARCH_RESNET:
 		case AGX_ARCH_BOTTLENECK:
+			if (net->layered != nullptr) // (a launch per layer: the width caps every one of them)
+				return agx_lay::launch(net->layered, width, d_features, d_slot_list, d_count, batch, d_policy, d_value, d_action_values, s);
 			return agx_res::launch(net->resnet, grid, d_features, d_slot_list, d_count, batch, d_policy, d_value, d_action_values, s);
 		case AGX_ARCH_CONVNEXT:
 			return agx_cnx::launch(net->convnext, grid, d_features, d_slot_list, d_count, batch, d_policy, d_value, d_action_values, d_moves_left, s);
@@ -208,6 +231,7 @@ int agx_net_destroy(AgxNet *net)
 	if (net == nullptr)
 		return AGX_OK;
 	agx_res::destroy(net->resnet);
+	agx_lay::destroy(net->layered);
 	agx_cnx::destroy(net->convnext);
 	delete net;
 	return AGX_OK;

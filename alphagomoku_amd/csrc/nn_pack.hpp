@@ -1,6 +1,6 @@
 /*
- * nn_pack.hpp — the host-side weight packers that more than one network file uses (nn_forward.hip, nn_convnext.hip): canonical fp32 weights
- * to fp16 MFMA A fragments.  A packer that feeds one kernel only stays with that kernel (pack_conv_rows, the value head's dense packing).
+ * nn_pack.hpp — the host-side weight packers that more than one network file uses (nn_forward.hip, nn_convnext.hip,
+ * nn_layered.hip): canonical fp32 weights to fp16 MFMA A fragments.  A packer that feeds one kernel only stays with that kernel (pack_conv_rows).
  */
 #ifndef AGX_NN_PACK_HPP_
 #define AGX_NN_PACK_HPP_
@@ -51,6 +51,29 @@ namespace
 					for (int j = 0; j < 8; j++)
 						dst[((static_cast<size_t>(t) * mtiles + mt) * 64 + lane) * 8 + j] = static_cast<half_t>(w[(static_cast<size_t>(dy * 5 + dx) * 8 + j) * cout + mt * 16 + (lane & 15)]);
 				}
+	}
+
+	/* value-head dense input length: 4 HW padded to whole MFMA k-steps */
+	inline int value_kpad(int rows, int cols)
+	{
+		return (rows * cols * 4 + 31) / 32 * 32;
+	}
+
+	/* the value head's dense layer 4 HW -> D ([4 HW][D] fp32) in MFMA A-fragment order [k-step][16-unit tile][lane][8] for value_head_kernel
+	 * (nn_device.hpp), zero beyond the last input.  Replaces dst. */
+	inline void pack_value_dense(const float *w, int hw, int d, std::vector<half_t> &dst)
+	{
+		const int kpad = (hw * 4 + 31) / 32 * 32, mtiles = d / 16;
+		dst.assign(static_cast<size_t>(kpad) * d, static_cast<half_t>(0.0f));
+		for (int kc = 0; kc < kpad / 32; kc++)
+			for (int mt = 0; mt < mtiles; mt++)
+				for (int lane = 0; lane < 64; lane++)
+					for (int j = 0; j < 8; j++)
+					{
+						const int unit = mt * 16 + (lane & 15), k = kc * 32 + 8 * (lane >> 4) + j;
+						if (k < hw * 4)
+							dst[((static_cast<size_t>(kc) * mtiles + mt) * 64 + lane) * 8 + j] = static_cast<half_t>(w[static_cast<size_t>(k) * d + unit]);
+					}
 	}
 }
 

@@ -58,7 +58,9 @@ typedef struct AgxNetDesc
 	int cols;           /* board cols, 5 .. 20, independent of rows (15x15 and 20x20 run kernels of their own, every other shape the
 	                       run-time-shaped one, csrc/nn_any_board.hip; AGX_NN_ANY_BOARD=1 in the environment sends those two there as well) */
 	int blocks;         /* residual blocks */
-	int filters;        /* conv filters F (64 or 128) */
+	int filters;        /* conv filters F: 64 or 128 for every architecture (one LDS-resident plane per board); the residual networks
+	                       (AGX_ARCH_RESNET) also take 192, 256, ... 512 (multiples of 64), which run a launch per layer with the activations
+	                       in a global scratch (csrc/nn_layered.hip; AGX_NN_LAYERED=1 in the environment sends 64 and 128 there as well) */
 	int in_channels;    /* 32 (bit-packed features, NNInputFeatures.cpp:59-113) or 8 (ResnetPVraw, networks.cpp:107-129: ml::unpackInput
 	                       expands the 8 low bits of the feature word, AGNetwork.cpp:249-258; without the action-values head) */
 	int value_hidden;   /* D = min(256, 2F) (blocks.cpp:113) */
@@ -67,7 +69,7 @@ typedef struct AgxNetDesc
 
 typedef struct AgxNet AgxNet; /* opaque */
 
-/* Number of fp32 values in the canonical (BN-folded) weight blob, in this order:
+/* Number of fp32 values in the canonical (BN-folded) weight blob — one layout for every filter count F, 64 to 512 —, in this order:
  *   conv_in  W[5][5][Cin][F]  b[F]
  *   blocks x { W1[3][3][F][F] b1[F]  W2[3][3][F][F] b2[F] }
  *   policy   Wp1[3][3][F][F] bp1[F]  Wp2[F] bp2[1]
@@ -91,7 +93,8 @@ int agx_nn_forward_pvq(AgxNet* net, const uint32_t* d_features, int batch, float
 int agx_net_description(const AgxNet* net, AgxNetDesc* out);
 /* Caps the persistent grid of the tower kernel at `workgroups` CUs (0 = all of them).  A tower workgroup fills its CU (LDS, registers), so
  * a narrowed launch leaves whole CUs to kernels running at the same time on other streams: the other slices of a pool stepped as
- * pipelined groups (agx_engine_*_group). */
+ * pipelined groups (agx_engine_*_group).  The layered towers (filters above 128) cap every layer's grid at the workgroups that fill that
+ * many CUs. */
 int agx_net_set_launch_width(AgxNet* net, int workgroups);
 int agx_net_destroy(AgxNet* net);
 

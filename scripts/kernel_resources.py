@@ -33,7 +33,7 @@ def resources(src):
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r06"
     out = ["# hipcc -Rpass-analysis=kernel-resource-usage of the final build (%s): registers, scratch, LDS per kernel (scripts/kernel_resources.py)" % build.source_hash()]
-    for src in ("nn_forward.hip", "nn_any_board.hip", "nn_any_board_bottleneck.hip", "nn_convnext.hip", "engine.hip"):
+    for src in ("nn_forward.hip", "nn_any_board.hip", "nn_any_board_bottleneck.hip", "nn_layered.hip", "nn_convnext.hip", "engine.hip"):
         out.append("# " + src)
         for r in resources(src):
             out.append("%-120s sgpr %3s vgpr %3s scratch %4s B/lane occupancy %s waves/SIMD lds %6s B" % (r["name"], r.get("SGPRs", "?"), r.get("VGPRs", "?"),
