@@ -471,6 +471,8 @@ def _declare(c):  # noqa: F811
     c.agx_engine_player_search.argtypes = [vp, ci, ctypes.POINTER(AgxPlayerSearch)]
     c.agx_engine_set_player_search.argtypes = [vp, ci, ctypes.POINTER(AgxPlayerSearch)]
     c.agx_engine_match_summary.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong), vp]
+    c.agx_engine_match_track_pairs.argtypes = [vp, ci]
+    c.agx_engine_match_pair_results.argtypes = [vp, ci, vp, ci, ctypes.POINTER(ctypes.c_longlong), vp]
     outputs, sink = ctypes.POINTER(AgxPositionSearchOutputs), ctypes.POINTER(AgxPositionSampleSink)
     c.agx_position_searcher_begin_ex.argtypes = [vp, ci, vp, vp, vp, outputs, sink, ci, ci, vp]
     c.agx_position_searcher_search_ex.argtypes = [vp, vp, ci, vp, vp, vp, outputs, sink, ci, ci, vp]

@@ -3036,6 +3036,105 @@ namespace
 			out[tid] = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
 	}
 
+	/* agx_engine_match_track_pairs: what a match pool keeps about its PAIR RESULTS — the points the first player took from one opening
+	 * played twice with the colours swapped (2 per win, 1 per draw: 0..4), which is what a sequential test consumes one at a time
+	 * (the reference's get_points / convert_match_results in front of GSPRT).  head[0..4] histogram of the points, [5] results seen (logged
+	 * or not), [6] flags (1 log full, 2 an opening was skipped, 4 inconsistent scores), [7] log launches, [8] cursor = entries written;
+	 * shadow[pair] = (games_done, won, drawn, lost) as of the pair's last logged opening. */
+	struct PairLogDev
+	{
+			long long *head = nullptr;
+			int4 *shadow = nullptr;
+			AgxPairResult *entries = nullptr;
+			int capacity = 0;
+	};
+	constexpr int PAIR_LOG_HEAD = 16; // long longs in front of the shadows (9 used; keeps the int4 shadows 16-byte aligned)
+	/* Behind every k_advance of a match pool that tracks its pairs, ONE workgroup: the pairs in index order, 256 at a time.  A pair whose
+	 * games_done is even and above its shadow's has finished an opening: points = 2 dW + dD against the shadow, one entry, hist[points]++,
+	 * the shadow follows.  The entries are placed by an ordered compaction (wave ballot, prefix over the four waves in LDS, running base from
+	 * chunk to chunk), so the log's order is launch, then pair index, whatever the scheduling.  This kernel is the only writer of everything
+	 * it touches and its launches follow each other on the step's stream: plain loads and stores, no atomics.  What cannot be a result — more
+	 * than one opening since the shadow, or scores that do not add up to two games — raises a flag and is neither logged nor counted; the
+	 * shadow is resynchronised all the same.  A full log still counts the result (head[0..5]), sets flag 1 and writes nothing. */
+	__global__ __launch_bounds__(256) void k_match_pair_log(EngineDev E, PairLogDev L)
+	{
+		__shared__ int wave_found[4];
+		__shared__ long long part[4][6]; // [wave][hist 0..4, flags]
+		const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, pairs = E.n_games / 2;
+		const int launch = static_cast<int>(L.head[7]);
+		long long seen = L.head[5]; // = the log position of the next result
+		int hist[5] = { 0, 0, 0, 0, 0 }, flags = 0; // (wave-uniform)
+		for (int first = 0; first < pairs; first += 256)
+		{
+			const int i = first + tid;
+			bool result = false;
+			int points = 0, round = 0, bad = 0;
+			if (i < pairs)
+			{
+				const GameState &gs = E.games[i];
+				const int done = gs.games_done;
+				const int4 was = L.shadow[i];
+				if ((done & 1) == 0 && done > was.x)
+				{
+					const int won = gs.match_score[0], drawn = gs.match_score[1], lost = gs.match_score[2];
+					if (done - was.x > 2)
+						bad |= 2;
+					if ((won - was.y) + (drawn - was.z) + (lost - was.w) != 2)
+						bad |= 4;
+					result = (bad == 0);
+					points = 2 * (won - was.y) + (drawn - was.z);
+					round = done / 2 - 1;
+					L.shadow[i] = make_int4(done, won, drawn, lost);
+				}
+			}
+			const u64 found = __ballot(result);
+			if (lane == 0)
+				wave_found[wave] = __popcll(found);
+			for (int k = 0; k < 5; k++)
+				hist[k] += __popcll(__ballot(result && points == k));
+			flags |= (__ballot((bad & 2) != 0) != 0ull ? 2 : 0) | (__ballot((bad & 4) != 0) != 0ull ? 4 : 0);
+			__syncthreads();
+			int before = 0, total = 0;
+			for (int w = 0; w < 4; w++)
+			{
+				before += (w < wave) ? wave_found[w] : 0;
+				total += wave_found[w];
+			}
+			if (result)
+			{
+				const long long pos = seen + before + __popcll(found & ((1ull << lane) - 1ull));
+				if (pos < L.capacity)
+				{
+					AgxPairResult r;
+					r.pair = i;
+					r.round = round;
+					r.points = points;
+					r.launch = launch;
+					L.entries[pos] = r;
+				}
+			}
+			seen += total;
+			__syncthreads(); // (wave_found is rewritten by the next chunk)
+		}
+		if (lane == 0)
+		{
+			for (int k = 0; k < 5; k++)
+				part[wave][k] = hist[k];
+			part[wave][5] = flags;
+		}
+		__syncthreads(); // (every thread has read head[5] and head[7] by now)
+		if (tid < 5)
+			L.head[tid] += part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
+		else if (tid == 5)
+			L.head[5] = seen;
+		else if (tid == 6)
+			L.head[6] |= part[0][5] | part[1][5] | part[2][5] | part[3][5] | (seen > L.capacity ? 1 : 0);
+		else if (tid == 7)
+			L.head[7] = launch + 1;
+		else if (tid == 8)
+			L.head[8] = (seen < L.capacity) ? seen : L.capacity;
+	}
+
 	/* Tree::getInfo(moves) / the principal variation (agx_engine_node_info / agx_engine_principal_variation): read-only walks over one tree's
 	 * node cache, one wave per walk.  The position is the compressed board in LDS plus the node-cache key, updated per ply like the descent
 	 * updates them (k_select); the colours alternate from the base board's side to move (Tree.cpp:403-424). */
@@ -3990,6 +4089,11 @@ struct AgxEngine
 		int sizing_cus = 0;
 		int *summary_dev = nullptr, *summary_host = nullptr; // agx_engine_root_summary: four words on their way back (device, pinned host)
 		long long *match_sum_dev = nullptr, *match_sum_host = nullptr; // agx_engine_match_summary: its four sums, the same way
+		// agx_engine_match_track_pairs: the pair log (head, shadows, entries: one allocation) and the pinned words its head comes back in;
+		// pair_log.head == nullptr: no tracking, no launch
+		PairLogDev pair_log;
+		size_t pair_log_bytes = 0;
+		long long *pair_head_host = nullptr;
 		// match pools: what each player searches with (agx_engine_set_player_search; both start as the pool's configuration).  dev's own
 		// fields stay the pool's: has_q and tss_max_nodes there are what the pool was ALLOCATED for, the upper bounds of a player's
 		PlayerSearchDev player[2];
@@ -4494,6 +4598,8 @@ int agx_engine_destroy(AgxEngine *e)
 		(void) hipHostFree(e->summary_host);
 	if (e->match_sum_host != nullptr)
 		(void) hipHostFree(e->match_sum_host);
+	if (e->pair_head_host != nullptr)
+		(void) hipHostFree(e->pair_head_host);
 	if (e->query_host != nullptr)
 		(void) hipHostFree(e->query_host);
 	delete e;
@@ -4514,6 +4620,8 @@ int agx_engine_begin(AgxEngine *e, const uint16_t *h_openings, int n_openings, v
 	counters[1] = e->dev.match_mode ? 0 : (e->dev.shared_tree ? 1 : e->dev.n_games);
 	AGX_HIP_CHECK(hipMemcpy(e->dev.counters, counters, sizeof(counters), hipMemcpyHostToDevice));
 	hipStream_t s = static_cast<hipStream_t>(stream);
+	if (e->pair_log.head != nullptr) // an empty log, zero totals, shadows at "nothing played"
+		AGX_HIP_CHECK(hipMemsetAsync(e->pair_log.head, 0, e->pair_log_bytes, s));
 	hipLaunchKernelGGL(k_begin, dim3(e->dev.n_games), dim3(256), 0, s, e->dev);
 	if (e->dev.match_mode)
 	{ // the pairs take openings 0 .. n_games/2 - 1 in order, exactly as they will after finished matches
@@ -4791,6 +4899,8 @@ int agx_engine_expand_backup_match(AgxEngine *e, void *stream)
 		KernelTimer t(e, s, 3);
 		// a moving tree's workgroup also rebases its partner's tree; the partner's own workgroup has nothing to do (it is not searching)
 		hipLaunchKernelGGL(k_advance<true>, dim3(d.n_games), dim3(ADV_THREADS), 0, s, d);
+		if (e->pair_log.head != nullptr) // agx_engine_match_track_pairs: the openings this launch finished, in pair order
+			hipLaunchKernelGGL(k_match_pair_log, dim3(1), dim3(256), 0, s, d, e->pair_log);
 		hipLaunchKernelGGL(k_arena_service, dim3(1), dim3(1024), 0, s, d, d.n_games, 0);
 		hipLaunchKernelGGL(k_arena_copy, dim3(d.n_games * CLEAR_PARTS), dim3(256), 0, s, d, CLEAR_PARTS); // (its last part per game commits)
 		hipLaunchKernelGGL(k_assign_openings, dim3(1), dim3(1024), 0, s, d, d.n_games / 2);
@@ -4905,6 +5015,8 @@ int agx_engine_advance_group(AgxEngine *e, int group, int n_groups, void *stream
 			count = d.n_games;
 		}
 		hipLaunchKernelGGL(k_advance<false>, dim3(trees), dim3(ADV_THREADS), 0, s, d);
+		if (e->pair_log.head != nullptr) // (a match pool that tracks its pairs: either player's move may have ended an opening)
+			hipLaunchKernelGGL(k_match_pair_log, dim3(1), dim3(256), 0, s, d, e->pair_log);
 		// four launches behind k_advance instead of seven (round 6): the openings are assigned by the service workgroup, a game's last copy part
 		// commits its larger arenas, a game's last clear part restarts it
 		hipLaunchKernelGGL(k_arena_service, dim3(1), dim3(1024), 0, s, d, trees, d.match_mode ? 0 : trees);
@@ -4986,6 +5098,53 @@ int agx_engine_match_results(AgxEngine *e, int *h_results, int pair_capacity)
 		h_results[4 * i + 1] = games[i].match_score[1];
 		h_results[4 * i + 2] = games[i].match_score[2];
 		h_results[4 * i + 3] = games[i].games_done;
+	}
+	return AGX_OK;
+}
+
+/* ---- match pools: the pair log (k_match_pair_log) ---- */
+int agx_engine_match_track_pairs(AgxEngine *e, int capacity)
+{
+	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_engine_match_track_pairs: null engine");
+	AGX_REQUIRE(e->dev.match_mode, AGX_ERR_STATE, "agx_engine_match_track_pairs: the engine was not created with match_mode");
+	AGX_REQUIRE(!e->begun, AGX_ERR_STATE, "agx_engine_match_track_pairs: call it before agx_engine_begin");
+	AGX_REQUIRE(capacity >= 1, AGX_ERR_INVALID, "agx_engine_match_track_pairs: capacity %d, need at least 1", capacity);
+	AGX_REQUIRE(e->pair_log.head == nullptr, AGX_ERR_STATE, "agx_engine_match_track_pairs: the pool already tracks its pairs (capacity %d)", e->pair_log.capacity);
+	const size_t pairs = static_cast<size_t>(e->dev.n_games / 2);
+	const size_t bytes = PAIR_LOG_HEAD * sizeof(long long) + pairs * sizeof(int4) + static_cast<size_t>(capacity) * sizeof(AgxPairResult);
+	if (e->pair_head_host == nullptr)
+		AGX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e->pair_head_host), PAIR_LOG_HEAD * sizeof(long long), hipHostMallocDefault));
+	uint8_t *p = nullptr;
+	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), bytes));
+	e->allocations.push_back(p);
+	e->device_bytes += bytes;
+	AGX_HIP_CHECK(hipMemset(p, 0, bytes));
+	e->pair_log.head = reinterpret_cast<long long*>(p);
+	e->pair_log.shadow = reinterpret_cast<int4*>(p + PAIR_LOG_HEAD * sizeof(long long));
+	e->pair_log.entries = reinterpret_cast<AgxPairResult*>(p + PAIR_LOG_HEAD * sizeof(long long) + pairs * sizeof(int4));
+	e->pair_log.capacity = capacity;
+	e->pair_log_bytes = bytes;
+	return AGX_OK;
+}
+
+int agx_engine_match_pair_results(AgxEngine *e, int first, AgxPairResult *h_out, int capacity, long long totals[8], void *stream)
+{
+	AGX_REQUIRE(e != nullptr && totals != nullptr, AGX_ERR_INVALID, "agx_engine_match_pair_results: null argument");
+	AGX_REQUIRE(first >= 0 && capacity >= 0 && (h_out != nullptr || capacity == 0), AGX_ERR_INVALID,
+			"agx_engine_match_pair_results: first %d, capacity %d%s", first, capacity, h_out == nullptr ? " with a null buffer" : "");
+	AGX_REQUIRE(e->dev.match_mode, AGX_ERR_STATE, "agx_engine_match_pair_results: the engine was not created with match_mode");
+	AGX_REQUIRE(e->pair_log.head != nullptr, AGX_ERR_STATE, "agx_engine_match_pair_results: the pool does not track its pairs (agx_engine_match_track_pairs)");
+	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_match_pair_results: agx_engine_begin has not been called");
+	hipStream_t s = static_cast<hipStream_t>(stream);
+	AGX_HIP_CHECK(hipMemcpyAsync(e->pair_head_host, e->pair_log.head, 9 * sizeof(long long), hipMemcpyDeviceToHost, s));
+	AGX_HIP_CHECK(hipStreamSynchronize(s));
+	std::memcpy(totals, e->pair_head_host, 8 * sizeof(long long));
+	const long long logged = e->pair_head_host[8]; // (<= the log's capacity: the kernel's cursor)
+	const long long end = std::min(logged, static_cast<long long>(first) + capacity);
+	if (end > first)
+	{ // the entries are final once written: a later launch only appends
+		AGX_HIP_CHECK(hipMemcpyAsync(h_out, e->pair_log.entries + first, static_cast<size_t>(end - first) * sizeof(AgxPairResult), hipMemcpyDeviceToHost, s));
+		AGX_HIP_CHECK(hipStreamSynchronize(s));
 	}
 	return AGX_OK;
 }

@@ -12,6 +12,7 @@ from ._lib import (lib, check, AgxEngineConfig, AgxEngineBuffers, AgxEngineStats
 
 OPENING_CAP = 32
 PLAYER_SEARCH_FIELDS = tuple(name for name, _ in AgxPlayerSearch._fields_)
+PAIR_RESULT_DTYPE = np.dtype([("pair", np.int32), ("round", np.int32), ("points", np.int32), ("launch", np.int32)])   # AgxPairResult
 
 
 def default_config(**overrides):
@@ -392,6 +393,26 @@ class GeneratorPool:
         out = (ctypes.c_longlong * 4)()
         check(lib.agx_engine_match_summary(self._h, out, stream))
         return dict(wins=int(out[0]), draws=int(out[1]), losses=int(out[2]), games=int(out[3]))
+
+    def track_pairs(self, capacity):
+        """switches the pool's pair log on (agx_engine_match_track_pairs; a match_mode pool, before begin()): from then on one small launch
+        behind every advance launch appends an entry for every pair that has finished an opening — both games, colours swapped"""
+        check(lib.agx_engine_match_track_pairs(self._h, int(capacity)))
+        self._pair_capacity = int(capacity)
+
+    def pair_results(self, first=0, stream=None):
+        """(entries, totals) of the pair log behind the work `stream` holds.  entries: structured array (pair, round, points, launch) of the log
+        from entry `first` on, in log order (launch, then pair index); points = 2 per win + 1 per draw of the first player over the opening's
+        two games.  totals: dict(histogram = results per points 0..4, results = results seen, logged or not, flags = 1 log full | 2 opening
+        skipped | 4 inconsistent scores, launches = log launches since begin())."""
+        totals = (ctypes.c_longlong * 8)()
+        capacity = getattr(self, "_pair_capacity", 0)
+        room = max(capacity - int(first), 0)
+        out = np.zeros(room, PAIR_RESULT_DTYPE)
+        check(lib.agx_engine_match_pair_results(self._h, int(first), out.ctypes.data_as(ctypes.c_void_p) if room else None, room, totals, stream))
+        logged = min(int(totals[5]), capacity)
+        return out[:max(logged - int(first), 0)], dict(histogram=[int(x) for x in totals[0:5]], results=int(totals[5]), flags=int(totals[6]),
+                                                       launches=int(totals[7]))
 
     def player_search(self, player):
         """what player 0 (first) / 1 (second) of a match_mode pool searches with now: a dict of the AgxPlayerSearch fields"""

@@ -551,6 +551,35 @@ int agx_engine_match_results(AgxEngine* engine, int* h_results, int pair_capacit
  * lost by the first player, out[3] = games finished.  Waits for THAT stream only and copies 32 bytes — what a loop that polls "are all
  * games played?" wants instead of agx_engine_match_results' device-wide synchronise and its copy of every pair's record. */
 int agx_engine_match_summary(AgxEngine* engine, long long out[4], void* stream);
+/* Match mode: PAIR RESULTS, logged on the device.  A pair result is what the first player took from one opening played twice with the
+ * colours swapped: 2 points per win, 1 per draw, 0..4 (the reference's get_points / convert_match_results) — what a sequential test
+ * (GSPRT) consumes one at a time in a fixed order, and what the running totals above cannot give back once two openings of a pair have
+ * been added up.  agx_engine_match_track_pairs switches the log on: `capacity` entries, allocated once and freed with the engine.  From
+ * then on ONE 256-thread workgroup follows every advance launch of the pool (merged: agx_engine_expand_backup_match / agx_engine_step_match;
+ * group-stepped: the advance stage of either group) on that launch's stream and appends an entry for every pair that has finished an
+ * opening since its previous entry.  The log's order is launch, then pair index: it does not depend on how the device schedules the
+ * games, so two runs of the same pool log the same sequence.  (The advance stages of a pool are issued in stream order, as they already must be:
+ * the log has one writer at a time.)  A pool that never calls agx_engine_match_track_pairs launches exactly what it did before.
+ *   status: AGX_ERR_STATE on a pool without match_mode, after agx_engine_begin, and for a second call; AGX_ERR_INVALID for capacity < 1.
+ * agx_engine_begin empties the log and zeroes the totals.
+ * agx_engine_match_pair_results copies entries first .. min(logged, first + capacity) to h_out and the totals to totals[8], behind the work
+ * `stream` holds (it waits for that stream only); h_out may be NULL with capacity 0: the totals alone.  logged = min(totals[5], the log's
+ * capacity), so the call has written max(0, min(logged, first + capacity) - first) entries.
+ *   totals[0..4] histogram of the points; [5] results seen, logged or not; [6] flags: 1 the log was full (the result is counted in [0..5]
+ *   and not written), 2 a pair finished more than one opening between two log launches, 4 a pair's scores did not add up to two games (2 and
+ *   4 cannot happen with the stepping calls above; such a pair is neither logged nor counted, and its next opening is read afresh);
+ *   [7] log launches since agx_engine_begin.
+ *   status: AGX_ERR_STATE before agx_engine_begin, on a pool without match_mode or without tracking; AGX_ERR_INVALID for null totals, a
+ *   negative first or capacity, a NULL h_out with capacity > 0. */
+typedef struct AgxPairResult
+{
+	int32_t pair;   /* the pair (= the first player's tree) */
+	int32_t round;  /* the pair's games_done / 2 - 1: its opening was number pair + round * (n_games / 2) of the pool's list */
+	int32_t points; /* 0..4, the first player's */
+	int32_t launch; /* the log launch that found it, counted from 0 at agx_engine_begin */
+} AgxPairResult;
+int agx_engine_match_track_pairs(AgxEngine* engine, int capacity);
+int agx_engine_match_pair_results(AgxEngine* engine, int first, AgxPairResult* h_out, int capacity, long long totals[8], void* stream);
 /* Match mode: each player with search settings of its own.  The reference hands every player of an evaluation game a SelfplayConfig
  * (EvaluationGame::setFirstPlayer / setSecondPlayer; evaluation/Player.cpp:64-81 takes search_config, final_selector,
  * constraints.max_simulations and max_batch_size from it), which is how tuning_launcher plays a base configuration against a tested one on

@@ -194,6 +194,7 @@ namespace agx
 			std::vector<void*> m_slice_streams; // useChipSlices: one CU-masked stream per slice of the pool
 			std::vector<HostPacer> m_pacers;    // one per slice (or one for the un-sliced pool)
 			int m_steps_ahead = 2;
+			int m_pair_capacity = 0; // trackPairs: the pair log's entries
 			bool m_phase_started = false, m_skip_first_search_of_slice0 = false;
 			int m_games = 0;
 			bool m_match = false;
@@ -418,6 +419,23 @@ namespace agx
 			{
 				std::array<long long, 4> out { };
 				check(agx_engine_match_summary(m_engine, out.data(), stream));
+				return out;
+			}
+			/* pair results logged on the device (agx_engine_match_track_pairs): before the pool's openings are set; `capacity` log entries */
+			void trackPairs(int capacity)
+			{
+				check(agx_engine_match_track_pairs(m_engine, capacity));
+				m_pair_capacity = capacity;
+			}
+			/* the log's entries from `first` on, in log order (launch, then pair), and the totals (agx_engine_match_pair_results: histogram of
+			 * the points, results seen, flags, log launches); max_entries = 0: the totals alone */
+			std::vector<AgxPairResult> pairResults(int first, int max_entries, std::array<long long, 8> &totals, void *stream = nullptr) const
+			{
+				std::vector<AgxPairResult> out(static_cast<size_t>(max_entries > 0 ? max_entries : 0));
+				check(agx_engine_match_pair_results(m_engine, first, out.empty() ? nullptr : out.data(), static_cast<int>(out.size()), totals.data(), stream));
+				const long long logged = std::min<long long>(totals[5], m_pair_capacity); // (a full log counts on: flag 1 in totals[6])
+				const long long end = std::min<long long>(logged, static_cast<long long>(first) + static_cast<long long>(out.size()));
+				out.resize(static_cast<size_t>(end > first ? end - first : 0));
 				return out;
 			}
 			/* what player 0 (first) / 1 (second) of an evaluation pool searches with (evaluation/Player.cpp:64-81: every Player takes these from
