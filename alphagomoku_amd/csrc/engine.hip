@@ -17,8 +17,9 @@
  *   k_arena_service / _copy   trees that outgrew their arenas move into larger ones (NodeCache::resize, ObjectPool growth)
  *
  * Everything stays in HBM between steps; the host only enqueues launches.  One wavefront per game for the sequential
- * tree work (games are independent, the batch inside a game is order-dependent through virtual loss); k_advance uses a
- * 1024-thread workgroup per game because compaction is data parallel.
+ * tree work (the games of different slots share nothing, the batch inside a game is order-dependent through virtual loss); k_advance
+ * uses a 1024-thread workgroup per game because compaction is data parallel.  A slot's games follow one another on one generator:
+ * its task slots and its solver's generation go on from game to game (begin_game), as a GameGenerator's do.
  */
 #include "agx_internal.hpp"
 #include "engine_types.hpp"
@@ -2498,10 +2499,13 @@ namespace
 		}
 		if (E.shared_tree)
 		{ // every SearchThread's Search sees the move: Search::setBoard -> AlphaBetaSearch::increaseGeneration; a finished game stops them all
+		  // (no prepare_search behind the move that ends a game: the generation stays, as record 0's does — begin_game raises them all alike,
+		  // so that a thread's solver sees one generation in the tree's next game, whichever of its task buffers a leaf sits in)
 			for (int t = 1 + tid; t < E.n_games; t += TPB)
 			{
 				GameState &ls = E.games[t];
-				ls.generation = (ls.generation + 1) % 64;
+				if (sh_int[2] == 0)
+					ls.generation = (ls.generation + 1) % 64;
 				ls.outcome = sh_int[2];
 				ls.n_moves = gs.n_moves;
 				if (sh_int[2] != 0)

@@ -785,6 +785,24 @@ void ago_game_tree_info(void *h, float *out_f, int *out_i)
 	out_i[2] = (r.n_edges == 1) ? 1 : 0;
 	out_i[3] = (non_losing == 1) ? 1 : 0;
 }
+/* What a generator's Search keeps between games (Game::begin): out_i = { the solver's generation, stored tasks of the current buffer, of
+ * the other buffer, task slots per buffer }, then per task slot k < capacity of the current buffer out_flags[k] = 1 proven-edge leaf
+ * (skip edge generation) | 2 processed by the solver | 4 evaluated by the network and out_moves_left[k] = SearchTask::moves_left */
+void ago_game_search_state(void *h, int lane, int *out_i, int *out_flags, float *out_moves_left, int capacity)
+{
+	Game &g = static_cast<GameHandle*>(h)->game;
+	const Search &s = g.lane(lane);
+	out_i[0] = s.solver.generation;
+	out_i[1] = s.stored;
+	out_i[2] = s.other_stored;
+	out_i[3] = static_cast<int>(s.tasks.size());
+	for (int k = 0; k < capacity && k < static_cast<int>(s.tasks.size()); k++)
+	{
+		const Task &t = s.tasks[k];
+		out_flags[k] = (t.skip_edge_generation ? 1 : 0) | (t.by_solver ? 2 : 0) | (t.by_network ? 4 : 0);
+		out_moves_left[k] = t.moves_left;
+	}
+}
 
 /*
  * CPU baseline: plays `games_per_thread` self-play games on each of `threads` host threads with the stand-in evaluator

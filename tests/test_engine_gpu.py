@@ -204,22 +204,50 @@ def test_solver_matches_oracle_per_position(agx_lib, olib, rules, max_nodes):
     pool.close()
 
 
-def _compare_record_sink(olib, pool, handles, rules, n, record_format):
+def _oracle_game_data(olib, h, n, record_format):
+    """what the final comparisons need of the game an oracle generator holds (its next Game::begin clears it): the played moves, the root flags,
+    the outcome and, for the record sink, every sample's format-201 bytes and the finished game framed by GameDataStorage::serialize"""
+    count = olib.ago_game_num_records(h)
+    moves = []
+    for i in range(count):
+        mv, rv, rs = ctypes.c_uint16(), ctypes.c_int(), ctypes.c_uint16()
+        rval = (ctypes.c_float * 2)()
+        em = np.zeros(512, np.uint16)
+        ev = np.zeros(512, np.int32)
+        ep = np.zeros(512, np.float32)
+        evl = np.zeros(1024, np.float32)
+        es = np.zeros(512, np.uint16)
+        olib.ago_game_record(h, i, ctypes.byref(mv), ctypes.byref(rv), rval, ctypes.byref(rs), ol.ptr(em), ol.ptr(ev), ol.ptr(ep), ol.ptr(evl), ol.ptr(es), 512)
+        moves.append(mv.value)
+    data = dict(moves=moves, flags=[olib.ago_game_record_flags(h, i) for i in range(count)], outcome=olib.ago_game_outcome(h), samples=[], storage=None)
+    if record_format & 2:
+        one = np.zeros(16 + 6 * n * n + 16, np.uint8)
+        for k in range(count):
+            size = olib.ago_game_record_v201(h, k, ol.ptr(one), one.size)
+            data["samples"].append(bytes(one[:size]))
+        if data["outcome"] != 0:
+            big = np.zeros(1 << 20, np.uint8)
+            size = olib.ago_game_storage_v201(h, ol.ptr(big), big.size)
+            data["storage"] = bytes(big[:size])
+    return data
+
+
+def _compare_record_sink(olib, pool, oracle_games, games, rules, n, record_format):
     """the samples quantised by k_advance to dataset format 201 and the finished games framed by the library
-    (GameDataStorage::serialize) must equal the oracle's restatement byte for byte"""
+    (GameDataStorage::serialize) must equal the oracle's restatement byte for byte.  oracle_games: opening id -> _oracle_game_data of every
+    game begun; game `id` is game id // games of slot id % games"""
     from alphagomoku_amd import selfplay
     recs, edges, samples, ends = pool.fetch_records()
     one = np.zeros(16 + 6 * n * n + 16, np.uint8)
     checked = entries = 0
-    for g, h in enumerate(handles):
+    for g, data in sorted(oracle_games.items()):
         mine = sorted((r.move_number, i) for i, r in enumerate(recs) if r.game_serial == g)
-        assert len(mine) == olib.ago_game_num_records(h)
+        assert len(mine) == len(data["samples"])
         for k, (_, i) in enumerate(mine):
             r = recs[i]
-            assert r.game_slot == g and r.game_index == 0 and r.sample_offset >= 0 and r.sample_offset % 4 == 0
-            size = olib.ago_game_record_v201(h, k, ol.ptr(one), one.size)
+            assert r.game_slot == g % games and r.game_index == g // games and r.sample_offset >= 0 and r.sample_offset % 4 == 0
             dev = samples[r.sample_offset:r.sample_offset + r.sample_bytes]
-            assert size == r.sample_bytes and np.array_equal(dev, one[:size]), (g, k)
+            assert len(data["samples"][k]) == r.sample_bytes and bytes(dev) == data["samples"][k], (g, k)
             if record_format & 1:   # ... and the same bytes from the device's own raw snapshot through the oracle's quantiser
                 e = edges[r.edge_offset:r.edge_offset + r.n_edges]
                 size2 = olib.ago_sample_v201_pack(n, n, r.move_number, len(e), ol.ptr(np.array([x.move for x in e], np.uint16)),
@@ -227,23 +255,22 @@ def _compare_record_sink(olib, pool, handles, rules, n, record_format):
                                                   ol.ptr(np.array([[x.win, x.draw] for x in e], np.float32).reshape(-1)),
                                                   ol.ptr(np.array([x.score for x in e], np.uint16)), r.root_score, r.root_flags, ol.ptr(one), one.size)
                 assert size2 == r.sample_bytes and np.array_equal(dev, one[:size2]), (g, k)
-            assert (r.outcome != 0) == (k == len(mine) - 1 and olib.ago_game_outcome(h) != 0), (g, k)
+            assert (r.outcome != 0) == (k == len(mine) - 1 and data["outcome"] != 0), (g, k)
             entries += int(dev[12:16].view(np.uint32)[0])
             checked += 1
-    finished = [g for g, h in enumerate(handles) if olib.ago_game_outcome(h) != 0]
-    assert sorted(e.game_slot for e in ends) == finished
+    finished = [g for g, data in sorted(oracle_games.items()) if data["outcome"] != 0]
+    assert sorted(e.game_serial for e in ends) == finished
+    assert all(e.game_slot == e.game_serial % games and e.game_index == e.game_serial // games for e in ends)
     buffer = selfplay.GameBuffer(rules, n, n)
     assert buffer.collect(pool) == len(finished)
-    big = np.zeros(1 << 20, np.uint8)
     by_first = {}
     for i in range(len(finished)):
         data = buffer.game(i)
         by_first[bytes(data)] = i
     for g in finished:
-        size = olib.ago_game_storage_v201(handles[g], ol.ptr(big), big.size)
-        assert bytes(big[:size]) in by_first, g      # GameDataStorage::serialize, byte for byte
+        assert oracle_games[g]["storage"] in by_first, g      # GameDataStorage::serialize, byte for byte
     st = buffer.stats()
-    assert st["games"] == len(finished) and st["samples"] == sum(olib.ago_game_num_records(handles[g]) for g in finished)
+    assert st["games"] == len(finished) and st["samples"] == sum(len(oracle_games[g]["samples"]) for g in finished)
     assert st["cross_win"] + st["draws"] + st["circle_win"] == len(finished)
     buffer.close()
     assert checked > 0 and entries > checked
@@ -265,17 +292,28 @@ def _oracle_root(olib, h):
 
 def _play_and_compare(olib, rules, games, batch, sims, max_steps, evaluator, table_entries=1 << 16, n=N, final_selector=0, use_symmetries=0,
                       action_values=0, noise_weight=0.0, noise_type=1, exploration_scaling=0.0, draw_after=0, max_children=0, policy_temperature=1.0,
-                      record_format=1, node_capacity=4096, edge_capacity=0, arena_reserve=1.0, groups=1, restore_from=None, **engine_options):
-    """evaluator(features uint32 [n][HW]) -> (policy [n][HW] f32, value [n][2] f32 (win, draw)[, q [n][HW][2]]); used for BOTH sides"""
+                      record_format=1, node_capacity=4096, edge_capacity=0, arena_reserve=1.0, groups=1, restore_from=None, rounds=1, n_openings=None,
+                      **engine_options):
+    """evaluator(features uint32 [n][HW]) -> (policy [n][HW] f32, value [n][2] f32 (win, draw)[, q [n][HW][2]]); used for BOTH sides.
+
+    rounds > 1: the pool is given games * rounds openings and every slot plays `rounds` games, slot g the openings g, g + games, g + 2 games, ...
+    (assign_openings).  The oracle keeps ONE generator per slot for the whole run, as the reference does (GameGenerator.cpp:46-77): when a slot's
+    game ends in a step, its next game begins on the same handle right behind that step's expand + backup — the device restarts the slot inside the
+    same advance stage — and everything compared in a first game is compared in the later ones under their opening ids, with the slot's
+    opening_id and games_done at every compared step.  n_openings: only that many openings at begin(); a slot whose next opening is missing
+    must sit idle (nothing scheduled, not active), the rest is handed over by add_openings once a slot has waited three steps, and the waiting
+    slots start — device and oracle — in the step that follows.  The returned stats also hold compared_by_round (roots compared per round)
+    and idle_steps (how often a slot was seen waiting)."""
     from alphagomoku_amd import selfplay
     N, HW = n, n * n   # noqa: N806 (shadow the 15x15 module defaults)
+    total = games * rounds
     cfg = selfplay.default_config(rules=rules, board_size=n, draw_after=draw_after if draw_after > 0 else n * n, n_games=games, max_batch_size=batch, max_simulations=sims,
                                   tss_table_entries=table_entries, node_capacity=node_capacity,
                                   edge_capacity=edge_capacity if edge_capacity > 0 else (65536 if n <= 15 else 131072), arena_reserve=arena_reserve,
                                   final_selector=final_selector, use_symmetries=use_symmetries, action_values=action_values,
                                   noise_type=noise_type if noise_weight > 0 else 0, noise_weight=noise_weight,
                                   exploration_scaling=exploration_scaling, max_children=max_children, policy_temperature=policy_temperature,
-                                  record_format=record_format, record_edge_capacity=games * HW * HW,   # a root edge per empty cell at worst
+                                  record_format=record_format, record_edge_capacity=total * HW * HW,   # a root edge per empty cell at worst
                                   **engine_options)
     pool = selfplay.GeneratorPool(cfg)
     ocfg = ol.default_search_config(max_batch_size=batch, max_simulations=sims, table_entries=table_entries, final_selector=final_selector,
@@ -286,31 +324,44 @@ def _play_and_compare(olib, rules, games, batch, sims, max_steps, evaluator, tab
     if max_children > 0:
         ocfg.max_children = max_children
     openings, handles = [], []
-    for g in range(games):
+    for g in range(total):
         op = np.zeros(256, np.uint16)
-        if restore_from is not None:
+        if restore_from is not None and g < games:
             # games in flight saved by another engine (agx_engine_save_games) continue here: for the oracle the saved moves are the "opening"
             k = len(restore_from[g]["moves"])
             op[:k] = restore_from[g]["moves"]
         else:
             k = olib.ago_prepare_opening(rules, N, N, 100 + g, ol.ptr(op))
         openings.append([int(x) for x in op[:k]])
+        if g >= games:
+            continue    # a later game of slot g % games: begun on that slot's handle when its turn comes
         h = olib.ago_game_create_ex(rules, N, N, draw_after, ctypes.byref(ocfg))
         olib.ago_game_set_serial(h, g)   # the device keys the symmetry hash by the opening id
         olib.ago_game_set_policy_temperature(h, policy_temperature)
         olib.ago_game_begin(h, ol.ptr(op), k)
         handles.append(h)
+    available = total if n_openings is None else n_openings
+    assert games <= available <= total
     if restore_from is not None:
-        pool.begin(selfplay.pack_openings([[] for _ in range(games)]))
+        pool.begin(selfplay.pack_openings([[] for _ in range(games)] + openings[games:available]))
         for g in range(games):
             pool.restore_game(dict(restore_from[g], opening_id=g, nn_queued=0), slot=g)
     else:
-        pool.begin(selfplay.pack_openings(openings))
+        pool.begin(selfplay.pack_openings(openings[:available]))
     compared = 0
+    compared_by_round = [0] * rounds
+    idle_steps = 0                  # steps in which a slot was seen waiting for an opening
     deferred = [False] * games
+    played = [0] * games            # games the slot's oracle generator has finished
+    waiting = [0] * games           # steps the slot has waited for an opening that is not in the pool's list yet
+    just_begun = [False] * games    # the oracle's next game was begun behind the last step: no root yet
+    oracle_games = {}               # opening id -> _oracle_game_data of every game a generator has left behind
     # groups > 1: the pool stepped as slices on CU-masked streams, the way bench.py and ag::GeneratorThread run it
     streams = selfplay.chip_slices(groups)[0] if groups > 1 else [None]
     for step in range(max_steps):
+        if available < total and max(waiting) >= 3:
+            pool.add_openings(selfplay.pack_openings(openings[available:]))
+            available = total
         if groups > 1:
             for k in range(groups):
                 pool.select_solve_group(k, groups, streams[k])
@@ -327,6 +378,8 @@ def _play_and_compare(olib, rules, games, batch, sims, max_steps, evaluator, tab
         by_slot = {int(s): i for i, s in enumerate(slots)}
         for g in range(games):
             if olib.ago_game_outcome(handles[g]) != 0:
+                # (rounds > 1: the slot has played its last game, or waits for an opening — either way the device has nothing to search there)
+                assert rounds == 1 or not any(s // batch == g for s in by_slot), (step, g)
                 continue
             if deferred[g]:
                 # the game's previous batch waited for larger arenas: this step the device only expands it (no select, nothing scheduled);
@@ -335,6 +388,7 @@ def _play_and_compare(olib, rules, games, batch, sims, max_steps, evaluator, tab
                 continue
             f = np.zeros((batch, HW), np.uint32)
             c = olib.ago_game_step_select(handles[g], ol.ptr(f), batch)
+            just_begun[g] = False
             mine = sorted(s for s in by_slot if s // batch == g)
             assert c == len(mine), (step, g)
             idx = [by_slot[s] for s in mine]
@@ -351,16 +405,49 @@ def _play_and_compare(olib, rules, games, batch, sims, max_steps, evaluator, tab
         else:
             pool.expand_backup()
         for g in range(games):
+            if rounds > 1 and played[g] < rounds and olib.ago_game_outcome(handles[g]) != 0:
+                # GAME_NOT_STARTED: the slot's generator goes on with its next opening (if the pool has been given it), the finished game is kept
+                cur = g + games * played[g]
+                if cur not in oracle_games:
+                    oracle_games[cur] = _oracle_game_data(olib, handles[g], N, record_format)
+                nxt = cur + games
+                if played[g] + 1 == rounds:
+                    played[g] += 1
+                elif nxt < available:
+                    played[g] += 1
+                    waiting[g] = 0
+                    op = np.array(openings[nxt] + [0], np.uint16)
+                    olib.ago_game_set_serial(handles[g], nxt)
+                    olib.ago_game_begin(handles[g], ol.ptr(op), len(openings[nxt]))
+                    just_begun[g] = True
+                else:
+                    waiting[g] += 1
             info = pool.game_info(g)
             assert info["error"] == 0
             deferred[g] = info["grow_pending"] != 0
             if deferred[g]:
                 continue   # compared again once the batch has been expanded
-            if info["opening_id"] != g or not info["active"] or olib.ago_game_outcome(handles[g]) != 0:
+            if rounds > 1:
+                if played[g] == rounds:
+                    assert not info["active"] and info["games_done"] == rounds, (step, g)
+                    continue
+                if waiting[g] > 0:
+                    assert not info["active"] and info["games_done"] == played[g] + 1, (step, g)   # idle until its opening arrives
+                    idle_steps += 1
+                    continue
+                cur = g + games * played[g]
+                assert info["active"] and info["opening_id"] == cur and info["games_done"] == played[g], (step, g, info["opening_id"], info["games_done"], cur)
+                assert info["n_moves"] == len(openings[cur]) + olib.ago_game_num_records(handles[g]), (step, g)
+                if just_begun[g]:
+                    assert info["root_edges"] == 0 and info["root_visits"] == 0, (step, g)   # a new game: no root on either side yet
+                    continue
+            elif info["opening_id"] != g or not info["active"] or olib.ago_game_outcome(handles[g]) != 0:
                 continue
+            else:
+                cur = g
             r = _oracle_root(olib, handles[g])
             e = info["edges"]
-            assert info["n_moves"] == len(openings[g]) + olib.ago_game_num_records(handles[g]), (step, g)
+            assert info["n_moves"] == len(openings[cur]) + olib.ago_game_num_records(handles[g]), (step, g)
             assert r["n"] == info["root_edges"] and r["visits"] == info["root_visits"], (step, g)
             assert np.array_equal(np.array([x["move"] for x in e], np.uint16), r["moves"]), (step, g)
             assert np.array_equal(np.array([x["visits"] for x in e], np.int32), r["ev"]), (step, g)   # visit counts
@@ -374,29 +461,26 @@ def _play_and_compare(olib, rules, games, batch, sims, max_steps, evaluator, tab
             olib.ago_game_tree_info(handles[g], ol.ptr(tree_f), ol.ptr(tree_i))
             assert np.float32(info["root_moves_left"]) == tree_f[0] and info["max_depth"] == tree_i[0], (step, g, info["root_moves_left"], tree_f[0], info["max_depth"], tree_i[0])
             compared += 1
-        if all(olib.ago_game_outcome(h) != 0 for h in handles) and not any(deferred):
+            compared_by_round[played[g]] += 1
+        if all(olib.ago_game_outcome(h) != 0 for h in handles) and not any(deferred) and (rounds == 1 or all(x == rounds for x in played)):
             break
-    # the played moves (the path's output records) must be identical
-    recs, _ = pool.records()
+    # the played moves (the path's output records) must be identical: every game a generator has begun, by its opening id
     for g in range(games):
+        cur = g + games * min(played[g], rounds - 1)
+        if cur not in oracle_games:
+            oracle_games[cur] = _oracle_game_data(olib, handles[g], N, record_format)   # its last game, finished or not
+    assert rounds > 1 or sorted(oracle_games) == list(range(games))
+    recs, _ = pool.records()
+    for g, data in sorted(oracle_games.items()):
         dev_moves = [r.move for r in recs if r.game_serial == g]
-        n = olib.ago_game_num_records(handles[g])
-        assert [r.root_flags for r in recs if r.game_serial == g] == [olib.ago_game_record_flags(handles[g], i) for i in range(n)], g
-        om = []
-        for i in range(n):
-            mv, rv, rs = ctypes.c_uint16(), ctypes.c_int(), ctypes.c_uint16()
-            rval = (ctypes.c_float * 2)()
-            em = np.zeros(512, np.uint16)
-            ev = np.zeros(512, np.int32)
-            ep = np.zeros(512, np.float32)
-            evl = np.zeros(1024, np.float32)
-            es = np.zeros(512, np.uint16)
-            olib.ago_game_record(handles[g], i, ctypes.byref(mv), ctypes.byref(rv), rval, ctypes.byref(rs), ol.ptr(em), ol.ptr(ev), ol.ptr(ep), ol.ptr(evl), ol.ptr(es), 512)
-            om.append(mv.value)
-        assert dev_moves == om, g
+        assert [r.root_flags for r in recs if r.game_serial == g] == data["flags"], g
+        assert dev_moves == data["moves"], g
+    assert all(r.game_serial in oracle_games for r in recs)
     if record_format & 2:
-        _compare_record_sink(olib, pool, handles, rules, N, record_format)
+        _compare_record_sink(olib, pool, oracle_games, games, rules, N, record_format)
     stats = pool.stats()
+    stats["compared_by_round"] = compared_by_round
+    stats["idle_steps"] = idle_steps
     pool.close()
     for h in handles:
         olib.ago_game_destroy(h)
@@ -1208,9 +1292,12 @@ FULL_SIZE = {
 @pytest.mark.parametrize("name", list(FULL_SIZE))
 def test_full_size_pool_matches_a_small_pool_game_by_game(agx_lib, name):
     """BASELINE configs[1..4] at FULL size — 1024 games, the config's network in the loop, its playout budget, batch 8, yielding on, the
-    reference's 4 Mi-entry solver table per game and bench.py's arena sizes: games are independent, so every game of the big pool must play
-    exactly what the same opening plays in a 128-game pool stepped in one piece, serial solver, no yielding (whose behaviour the other tests pin
-    to the oracle step by step) — a size-independent property checked at full size, on the path bench.py times; the arenas must hold."""
+    reference's 4 Mi-entry solver table per game and bench.py's arena sizes: a slot's FIRST game does not depend on the other slots, on how the
+    pool is sliced or on the order of the launches, so every game of the big pool must play exactly what the same opening plays in a 128-game
+    pool stepped in one piece, serial solver, no yielding (whose behaviour the other tests pin to the oracle step by step) — a size-independent
+    property checked at full size, on the path bench.py times; the arenas must hold.  A slot's LATER games do depend on what the slot played
+    before (the generator keeps its task slots and its solver's generation: tests/generator_restart_ref.py), and pools of different sizes give
+    a slot different histories — hence "no spare openings" below; later games are held to the oracle by tests/test_engine_restart_gpu.py."""
     from alphagomoku_amd import selfplay, lib, check
     from alphagomoku_amd.networks import AGNetwork
     c = FULL_SIZE[name]
