@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libagx.so")
 
 INCLUDE = os.path.join(HERE, "..", "include")
-SOURCES = ["agx_api.hip", "nn_forward.hip", "nn_any_board.hip", "nn_any_board_bottleneck.hip", "nn_layered.hip", "nn_convnext.hip", "engine.hip", "training_batch.hip", "net_score.hip", "head_loss.hip", "position_eval.hip", "nn_net.cpp", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
+SOURCES = ["agx_api.hip", "nn_forward.hip", "nn_any_board.hip", "nn_any_board_bottleneck.hip", "nn_layered.hip", "nn_convnext.hip", "engine.hip", "training_batch.hip", "net_score.hip", "head_loss.hip", "position_eval.hip", "nn_net.cpp", "engine_host.cpp", "position_solver.cpp", "position_searcher.cpp", "stream_host.cpp", "tables_host.cpp", "host_util.cpp", "game_buffer.cpp"]
 DRIVER = os.path.join(HERE, "agx_selfplay")
 AG_LIB = os.path.join(HERE, "libagx_ag.so")               # the reference-named C++ classes (include/alphagomoku_agx/) over the C ABI
 BOUNDARY_TEST = os.path.join(HERE, "agx_boundary_test")  # tests/cpp/boundary_main.cpp: the reference's call chain on those classes

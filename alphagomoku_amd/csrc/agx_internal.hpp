@@ -24,12 +24,12 @@ namespace agx
 	 * reduction behind agx_net_score_outputs); checks hipGetLastError, so a caller's launch just before it is covered too */
 	int add_sample_scores(int n, AgxSampleScore *d_scores, AgxNetScore *d_total, hipStream_t stream);
 
-	/* engine.hip, for agx_position_evaluator_evaluate_solved (position_eval.hip): what a position solver was created for and its device
+	/* position_solver.cpp, for agx_position_evaluator_evaluate_solved (position_eval.hip): what a position solver was created for and its device
 	 * workspace [capacity] (score, n_actions, moves, move_scores, status; the other members null) ... */
 	int position_solver_describe(AgxPositionSolver *solver, int *rules, int *board_size, int *capacity, AgxSolvedPositions *workspace);
 	/* ... and "the work enqueued on `stream` so far still reads the solver's workspace": the solver's next call on another stream waits for it */
 	int position_solver_mark(AgxPositionSolver *solver, hipStream_t stream);
-	/* engine.hip, for agx_dataset_reanalyse (training_batch.hip): what a position searcher was created for */
+	/* position_searcher.cpp, for agx_dataset_reanalyse (training_batch.hip): what a position searcher was created for */
 	int position_searcher_describe(AgxPositionSearcher *ps, int *rules, int *board_size, int *slots);
 }
 

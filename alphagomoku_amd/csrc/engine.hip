@@ -1,5 +1,6 @@
 /*
- * engine.hip — the device-resident self-play engine: kernels, host object and its C ABI (include/agx.h).
+ * engine.hip — the device-resident self-play engine: its kernels and, at the end, the launch layer over them (engine_launch.hpp).  The host
+ * objects and the C ABI (include/agx.h) are in engine_host.cpp, position_solver.cpp and position_searcher.cpp.
  *
  * One step of the pool = what GameGenerator::generate does for every game of a GeneratorThread
  * (src/selfplay/GameGenerator.cpp:79-118, src/selfplay/GeneratorManager.cpp:124-141), as four launches:
@@ -23,16 +24,12 @@
  */
 #include "agx_internal.hpp"
 #include "engine_types.hpp"
+#include "engine_launch.hpp"
 #include "dev_mcts.hpp"
-#include "tables_host.hpp"
 #include "renju_static.hpp"
 #include "root_noise.hpp"
 #include "sample_v201.hpp"
 
-#include <vector>
-#include <thread>
-#include <chrono>
-#include <mutex>
 #include <cstring>
 #include <algorithm>
 
@@ -254,7 +251,6 @@ namespace
 	 * written while its batch is in flight).  A solve is parked at most once (it then has a whole launch in front of it), and only when a
 	 * buffer is free.  Pacing only, like the yield rule.
 	 */
-	constexpr float SPEC_PARK_FRACTION = 0.90f; // (C5 on one box: 0.80 484 k, 0.86 511 k, 0.90 520 k, 0.94 469 k, 0.97 406 k simulations/s; without parking 408 k)
 	struct ParkCtl
 	{
 			int count;     // games of the launch
@@ -2097,7 +2093,6 @@ namespace
 	/* ADV_THREADS threads per game that must move: the compaction of a large tree (2000 nodes, 250 k edges: 6 MB) is a chain of dependent
 	 * load -> store rounds per wave, so its duration falls with the number of waves that copy (256 -> 1024 threads: k_advance 0.36 -> see
 	 * DESIGN 6.1); the other games' workgroups leave at once. */
-	constexpr int ADV_THREADS = 1024;
 	template<bool MERGED> // (MERGED: as k_search_spec's)
 	__global__ __launch_bounds__(ADV_THREADS) void k_advance(EngineDev E)
 	{
@@ -3040,19 +3035,6 @@ namespace
 			out[tid] = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
 	}
 
-	/* agx_engine_match_track_pairs: what a match pool keeps about its PAIR RESULTS — the points the first player took from one opening
-	 * played twice with the colours swapped (2 per win, 1 per draw: 0..4), which is what a sequential test consumes one at a time
-	 * (the reference's get_points / convert_match_results in front of GSPRT).  head[0..4] histogram of the points, [5] results seen (logged
-	 * or not), [6] flags (1 log full, 2 an opening was skipped, 4 inconsistent scores), [7] log launches, [8] cursor = entries written;
-	 * shadow[pair] = (games_done, won, drawn, lost) as of the pair's last logged opening. */
-	struct PairLogDev
-	{
-			long long *head = nullptr;
-			int4 *shadow = nullptr;
-			AgxPairResult *entries = nullptr;
-			int capacity = 0;
-	};
-	constexpr int PAIR_LOG_HEAD = 16; // long longs in front of the shadows (9 used; keeps the int4 shadows 16-byte aligned)
 	/* Behind every k_advance of a match pool that tracks its pairs, ONE workgroup: the pairs in index order, 256 at a time.  A pair whose
 	 * games_done is even and above its shadow's has finished an opening: points = 2 dW + dD against the shadow, one entry, hist[points]++,
 	 * the shadow follows.  The entries are placed by an ordered compaction (wave ballot, prefix over the four waves in LDS, running base from
@@ -3313,19 +3295,6 @@ namespace
 	 * board), k_harvest_positions the back end (k_advance's place in the step: final selector, dense per-cell rows, principal variation),
 	 * and a harvested slot is left as a finished game is, so that k_arena_service takes grown arenas back before the next load.
 	 */
-	struct PositionJob
-	{
-			const uint8_t *boards;  // [n][hw] 0 empty, 1 cross, 2 circle
-			const uint8_t *signs;   // [n] 1 cross, 2 circle to move
-			const int32_t *serials; // [n] noise / symmetry serial (GameState::opening_id), null = 0
-			int n, max_pv, max_steps;
-			AgxPositionSearchOutputs out; // each may be null
-			AgxPositionSampleSink sink;   // format-201 samples (position_write_sample); d_bytes or d_sizes null = none
-			int *cursor;        // next position of the list
-			int *finished;      // positions whose outputs are written
-			int *slot_position; // [n_games] the position a slot searches, -1 = free
-			int *slot_steps;    // [n_games] steps the slot has spent on it
-	};
 	/* every output of position p that has no root behind it: zeros, no edge anywhere (whole workgroup of `threads`) */
 	__device__ void position_write_empty(const PositionJob &J, int p, int hw, int status, int nodes, int edges, int steps, int error, int tid, int threads)
 	{
@@ -3897,13 +3866,6 @@ namespace
 	 * around solver_run / solver_place is that function's.  Nothing is shared between waves: no atomics, no waiting; a solve ends by its node
 	 * budget and solve_task's depth loop.
 	 */
-	struct SolvePositionsArgs
-	{
-			const uint8_t *boards; // [n][hw] 0 empty, 1 cross, 2 circle
-			const uint8_t *signs;  // [n] 1 cross, 2 circle
-			int n;
-			AgxSolvedPositions out; // each may be null
-	};
 	template<bool RENJU, int NFIX>
 	__global__ __launch_bounds__(64, AGX_SOLVE_WAVES) void k_solve_positions(EngineDev E, SolvePositionsArgs A)
 	{
@@ -4072,640 +4034,76 @@ namespace
 }
 
 /* ================================================================================================================ */
-struct AgxEngine
-{
-		AgxEngineConfig cfg;
-		EngineDev dev;
-		std::vector<void*> allocations;
-		unsigned long long device_bytes = 0; // sum of the allocations' sizes (agx_engine_device_bytes)
-		std::vector<GameState> idle_games; // the pool before agx_engine_begin: every game idle, in its class-0 arena bundle
-		std::vector<unsigned long long> debug_solve_nodes; // solver nodes per position of the last agx_debug_solve
-		ArenaHeap idle_heap;
-		std::vector<uint64_t> zobrist; // [2*hw][2]
-		bool begun = false;
-		// Search::select and the threat solver of a game in one launch (k_solve<.., FUSED>); AGX_FUSE_SELECT=0 keeps them as two launches
-		// (separate k_select / k_solve times in agx_engine_kernel_timing and in profiles)
-		bool fuse_select = true;
-		// AgxEngineConfig.speculative_solver: select + solver as one persistent launch with the leaves of a batch solved in parallel (k_search_spec)
-		uint8_t *board_staging = nullptr; // agx_engine_set_board: the caller's board on its way to the device
-		uint16_t *moves_staging = nullptr; // agx_engine_restore_game: the saved move list on its way to the device
-		bool sizing_only = false; // agx_engine_estimate_device_bytes: dev_alloc only adds up, nothing touches a device
-		int sizing_cus = 0;
-		int *summary_dev = nullptr, *summary_host = nullptr; // agx_engine_root_summary: four words on their way back (device, pinned host)
-		long long *match_sum_dev = nullptr, *match_sum_host = nullptr; // agx_engine_match_summary: its four sums, the same way
-		// agx_engine_match_track_pairs: the pair log (head, shadows, entries: one allocation) and the pinned words its head comes back in;
-		// pair_log.head == nullptr: no tracking, no launch
-		PairLogDev pair_log;
-		size_t pair_log_bytes = 0;
-		long long *pair_head_host = nullptr;
-		// match pools: what each player searches with (agx_engine_set_player_search; both start as the pool's configuration).  dev's own
-		// fields stay the pool's: has_q and tss_max_nodes there are what the pool was ALLOCATED for, the upper bounds of a player's
-		PlayerSearchDev player[2];
-		// agx_engine_node_info / agx_engine_principal_variation: the paths on their way to the device and the answers on their way back, one
-		// staging buffer each side (grown on demand)
-		uint8_t *query_dev = nullptr, *query_host = nullptr;
-		size_t query_bytes = 0;
-		bool speculative = false;
-		bool external_moves = false; // agx_engine_set_board has been called: the caller makes the moves, no advance stage services the arenas
-		int spec_waves = 0; // waves of that launch over the whole pool
-		// optional per-kernel timing (agx_engine_kernel_timing): HIP events on the launch stream around every kernel of a step
-		bool timing = false;
-		std::vector<hipEvent_t> events;   // groups of (before, after) per kernel launch
-		std::vector<int> event_kernel;    // kernel id of each pair: 0 select, 1 solve, 2 expand, 3 advance
-		std::vector<hipEvent_t> free_events;
-};
-
-namespace
-{
-	hipEvent_t timing_event(AgxEngine *e)
-	{
-		hipEvent_t ev = nullptr;
-		if (!e->free_events.empty())
-		{
-			ev = e->free_events.back();
-			e->free_events.pop_back();
-		}
-		else
-			(void) hipEventCreate(&ev);
-		return ev;
-	}
-	struct KernelTimer
-	{ // records an event pair around one kernel launch when timing is enabled
-			AgxEngine *e;
-			hipStream_t s;
-			hipEvent_t a = nullptr;
-			KernelTimer(AgxEngine *engine, hipStream_t stream, int kernel) :
-					e(engine), s(stream)
-			{
-				if (e->timing)
-				{
-					a = timing_event(e);
-					(void) hipEventRecord(a, s);
-					e->event_kernel.push_back(kernel);
-				}
-			}
-			~KernelTimer()
-			{
-				if (e->timing)
-				{
-					hipEvent_t b = timing_event(e);
-					(void) hipEventRecord(b, s);
-					e->events.push_back(a);
-					e->events.push_back(b);
-				}
-			}
-	};
-	template<typename T>
-	int dev_alloc(AgxEngine *e, T **ptr, size_t count)
-	{
-		if (e->sizing_only)
-		{
-			e->device_bytes += std::max<size_t>(count * sizeof(T), 16);
-			*ptr = nullptr;
-			return AGX_OK;
-		}
-		void *p = nullptr;
-		const hipError_t err = hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16));
-		if (err != hipSuccess)
-		{
-			(void) hipGetLastError(); // the failure must not stay behind as the "last error" of this thread's later, successful calls
-			agx::set_error("hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(err));
-			return AGX_ERR_HIP;
-		}
-		e->allocations.push_back(p);
-		e->device_bytes += std::max<size_t>(count * sizeof(T), 16);
-		*ptr = static_cast<T*>(p);
-		return AGX_OK;
-	}
-	template<typename T>
-	int dev_upload(AgxEngine *e, const T **ptr, const std::vector<T> &src)
-	{
-		T *p = nullptr;
-		const int st = dev_alloc(e, &p, src.size());
-		if (st != AGX_OK)
-			return st;
-		if (!e->sizing_only)
-			AGX_HIP_CHECK(hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-		*ptr = p;
-		return AGX_OK;
-	}
-	uint64_t splitmix64(uint64_t &state)
-	{
-		uint64_t z = (state += 0x9E3779B97F4A7C15ull);
-		z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-		z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-		return z ^ (z >> 31);
-	}
-	size_t round_pow2(size_t x)
-	{
-		size_t r = 1;
-		while (r < x)
-			r <<= 1;
-		return r;
-	}
-}
-
-extern "C" {
-
-int agx_engine_default_config(AgxEngineConfig *cfg)
-{
-	AGX_REQUIRE(cfg != nullptr, AGX_ERR_INVALID, "agx_engine_default_config: null argument");
-	std::memset(cfg, 0, sizeof(*cfg));
-	cfg->rules = AGX_FREESTYLE;
-	cfg->board_size = 15;
-	cfg->draw_after = 225;
-	cfg->n_games = 1024;
-	cfg->max_batch_size = 8;
-	cfg->max_simulations = 400;
-	cfg->exploration_constant = 1.25f;
-	cfg->exploration_scaling = 0.0f;
-	cfg->init_to = 0;
-	cfg->information_leak_threshold = 0.01f;
-	cfg->policy_expansion_threshold = 1.0e-4f;
-	cfg->max_children = 0;
-	cfg->tss_max_positions = 100;
-	cfg->tss_table_entries = 4ull * 1024ull * 1024ull;
-	cfg->zobrist_seed = 0x9E3779B97F4A7C15ull;
-	cfg->node_capacity = 8192;
-	cfg->edge_capacity = 524288; // whole freestyle games at 400 playouts peak at ~250 k edges per game with an untrained (flat) policy
-	cfg->record_capacity = 0;
-	cfg->record_edge_capacity = 0;
-	cfg->solver_yield_fraction = 0.0f;
-	cfg->final_selector = 0;
-	cfg->use_symmetries = 0;
-	cfg->symmetry_seed = 0x5DEECE66Dull;
-	cfg->action_values = 0;
-	cfg->match_mode = 0;
-	cfg->policy_temperature = 1.0f;
-	cfg->arena_reserve = 1.0f;
-	cfg->search_threads = 0;
-	cfg->record_format = 1;
-	cfg->record_sample_capacity = 0;
-	cfg->game_end_capacity = 0;
-	cfg->speculative_solver = 0;
-	cfg->speculative_waves = 0;
-	cfg->force_expand_root = 1;
-	cfg->search_buffers = 0;
-	cfg->noise_type = 0;
-	cfg->noise_weight = 0.0f;
-	cfg->noise_seed = 0x2545F4914F6CDD1Dull;
-	return AGX_OK;
-}
+/* The launch layer (engine_launch.hpp): what the host files call.  Nothing below knows AgxEngine or the C ABI. */
 
 #if defined(AGX_QUICK) && !defined(AGX_QUICK_RENJU)
 #define AGX_QUICK_RENJU false /* developer builds (AGX_QUICK: only the 15x15 solver is instantiated); -DAGX_QUICK_RENJU=true: the renju solver instead of the other rules' */
 #endif
-/* the instantiation of k_search_spec a pool of these rules and board size launches */
-typedef void (*SpecKernel)(EngineDev, int);
-static SpecKernel spec_kernel(int rules, int n, bool merged = false)
-{ // merged: the variant for a match pool's launch over both players' trees (k_search_spec's MERGED)
-#ifdef AGX_QUICK
-	(void) rules;
-	(void) n;
-	return merged ? k_search_spec<AGX_QUICK_RENJU, 15, true> : k_search_spec<AGX_QUICK_RENJU, 15, false>;
+/* (rules, board size) -> the compile-time pair {renju, NFIX} of k_search_spec, k_solve and k_solve_positions: USE(RENJU, NFIX) is expanded
+ * for the one shape that plays these rules on this board (NFIX 15 and 20 are the boards with kernels of their own, 0 is any size) */
+#ifdef AGX_QUICK /* developer builds: one shape only, the 15x15 board (a fifth of the compile time) */
+#define AGX_FOR_SHAPE(rules, n, USE) do { (void) (rules); (void) (n); USE(AGX_QUICK_RENJU, 15); } while (0)
 #else
-	if (rules == AGX_RENJU)
-	{
-		if (n == 15)
-			return merged ? k_search_spec<true, 15, true> : k_search_spec<true, 15, false>;
-		return merged ? k_search_spec<true, 0, true> : k_search_spec<true, 0, false>;
-	}
-	if (n == 15)
-		return merged ? k_search_spec<false, 15, true> : k_search_spec<false, 15, false>;
-	if (n == 20)
-		return merged ? k_search_spec<false, 20, true> : k_search_spec<false, 20, false>;
-	return merged ? k_search_spec<false, 0, true> : k_search_spec<false, 0, false>;
-#endif
-}
-/* a player's search settings <-> the plain fields of a launch's EngineDev (what the kernels read) */
-static PlayerSearchDev player_of(const EngineDev &d)
-{
-	PlayerSearchDev p;
-	p.max_sims = d.max_sims;
-	p.batch_limit = d.batch_limit;
-	p.c_puct = d.c_puct;
-	p.c_scale = d.c_scale;
-	p.init_to = d.init_to;
-	p.leak_threshold = d.leak_threshold;
-	p.expansion_threshold = d.expansion_threshold;
-	p.max_children = d.max_children;
-	p.policy_temperature = d.policy_temperature;
-	p.tss_max_nodes = d.tss_max_nodes;
-	p.final_selector = d.final_selector;
-	p.has_q = d.has_q;
-	return p;
-}
-static void use_player(EngineDev &d, const PlayerSearchDev &p)
-{
-	d.max_sims = p.max_sims;
-	d.batch_limit = p.batch_limit;
-	d.c_puct = p.c_puct;
-	d.c_scale = p.c_scale;
-	d.init_to = p.init_to;
-	d.leak_threshold = p.leak_threshold;
-	d.expansion_threshold = p.expansion_threshold;
-	d.max_children = p.max_children;
-	d.policy_temperature = p.policy_temperature;
-	d.tss_max_nodes = p.tss_max_nodes;
-	d.final_selector = p.final_selector;
-	d.has_q = p.has_q;
-}
-/* how many of its one-wave workgroups a compute unit keeps resident (LDS state and registers of that instantiation; asked of the runtime, 12 if it will not say) */
-static int spec_resident_waves_per_cu(int rules, int n)
-{
-	int blocks = 0;
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(spec_kernel(rules, n)), 64, 0) != hipSuccess || blocks <= 0)
-	{
-		(void) hipGetLastError();
-		return 12;
-	}
-	return blocks;
-}
-/* sizing_cus > 0: nothing is allocated and no device is touched — the engine only adds up what it WOULD allocate on a device with that many
- * compute units (agx_engine_estimate_device_bytes); *out then is a host-only object for the caller to read device_bytes from and delete */
-static int engine_create(const AgxEngineConfig *cfg, AgxEngine **out, int sizing_cus)
-{
-	AGX_REQUIRE(cfg != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_engine_create: null argument");
-	AGX_REQUIRE(cfg->rules >= 0 && cfg->rules <= AGX_CARO6, AGX_ERR_INVALID, "agx_engine_create: unknown rules %d", cfg->rules);
-	AGX_REQUIRE(cfg->board_size >= 5 && cfg->board_size <= MAXN, AGX_ERR_UNSUPPORTED, "agx_engine_create: board size %d not in [5, %d]", cfg->board_size, MAXN);
-	AGX_REQUIRE(cfg->n_games > 0 && cfg->max_batch_size > 0 && cfg->max_simulations > 0, AGX_ERR_INVALID, "agx_engine_create: non-positive sizes");
-	AGX_REQUIRE(cfg->tss_max_positions >= 1 && cfg->tss_max_positions <= 1000, AGX_ERR_UNSUPPORTED, "agx_engine_create: tss_max_positions must be in [1, 1000]");
-	AGX_REQUIRE(cfg->init_to >= 0 && cfg->init_to <= 3, AGX_ERR_INVALID, "agx_engine_create: init_to must be 0..3");
-	AGX_REQUIRE(cfg->solver_yield_fraction >= 0.0f && cfg->solver_yield_fraction <= 1.0f, AGX_ERR_INVALID, "agx_engine_create: solver_yield_fraction must be in [0, 1]");
-	AGX_REQUIRE(cfg->final_selector >= 0 && cfg->final_selector <= 5, AGX_ERR_INVALID, "agx_engine_create: final_selector must be 0..5");
-	AGX_REQUIRE(cfg->noise_type >= 0 && cfg->noise_type <= 3, AGX_ERR_INVALID, "agx_engine_create: noise_type must be 0 (none), 1 (custom), 2 (dirichlet) or 3 (gumbel)");
-	AGX_REQUIRE(cfg->policy_temperature >= 0.0f, AGX_ERR_INVALID, "agx_engine_create: policy_temperature must not be negative");
-	AGX_REQUIRE(!cfg->match_mode || cfg->n_games % 2 == 0, AGX_ERR_INVALID, "agx_engine_create: match_mode pairs the trees, n_games must be even");
-	AGX_REQUIRE(cfg->noise_weight >= 0.0f && cfg->noise_weight <= 1.0f, AGX_ERR_INVALID, "agx_engine_create: noise_weight must be in [0, 1]");
-	AGX_REQUIRE(cfg->search_buffers >= 0 && cfg->search_buffers <= 2, AGX_ERR_INVALID, "agx_engine_create: search_buffers must be 0, 1 or 2");
-	{
-		const int threads = std::max(1, cfg->search_threads), buffers = (cfg->search_buffers == 2) ? 2 : 1;
-		AGX_REQUIRE((threads == 1 && buffers == 1) || (threads * buffers == cfg->n_games && !cfg->match_mode && cfg->solver_yield_fraction == 0.0f), AGX_ERR_INVALID,
-				"agx_engine_create: search_threads > 1 / search_buffers = 2 make the pool ONE tree searched by n_games task buffers: n_games must equal "
-				"search_threads x buffers (%d x %d), no match_mode, no yielding", threads, buffers);
-	}
-	AGX_REQUIRE(cfg->record_format >= 0 && cfg->record_format <= 3, AGX_ERR_INVALID, "agx_engine_create: record_format must be 0..3 (bit 0 edge snapshots, bit 1 format-201 samples)");
-
-	AgxEngine *e = new AgxEngine();
-	e->cfg = *cfg;
-	e->sizing_only = sizing_cus > 0;
-	e->sizing_cus = sizing_cus;
-	if (const char *fuse = std::getenv("AGX_FUSE_SELECT"))
-		e->fuse_select = std::atoi(fuse) != 0;
-	EngineDev &d = e->dev;
-	std::memset(&d, 0, sizeof(d));
-	d.rules = cfg->rules;
-	d.n = cfg->board_size;
-	d.hw = d.n * d.n;
-	d.draw_after = (cfg->draw_after > 0) ? cfg->draw_after : d.hw;
-	d.n_games = cfg->n_games;
-	d.batch = cfg->max_batch_size;
-	d.max_sims = cfg->max_simulations;
-	d.c_puct = cfg->exploration_constant;
-	d.c_scale = cfg->exploration_scaling;
-	d.init_to = cfg->init_to;
-	d.leak_threshold = cfg->information_leak_threshold;
-	d.expansion_threshold = cfg->policy_expansion_threshold;
-	d.max_children = (cfg->max_children > 0) ? cfg->max_children : 0x7FFFFFFF;
-	d.tss_max_nodes = cfg->tss_max_positions;
-	d.tss_max_depth = 100;
-	d.solve_time_ticks = 0ull;
-	d.batch_limit = d.batch;
-	d.yield_fraction = cfg->solver_yield_fraction;
-	d.final_selector = cfg->final_selector;
-	d.use_symmetries = cfg->use_symmetries;
-	d.symmetry_seed = cfg->symmetry_seed;
-	d.noise_type = (cfg->noise_weight > 0.0f) ? cfg->noise_type : 0;
-	d.noise_weight = cfg->noise_weight;
-	d.noise_seed = cfg->noise_seed;
-	const size_t buckets = round_pow2(std::max<size_t>(cfg->tss_table_entries, 4)) / 4;
-	d.tt_bucket_mask = buckets - 1;
-	d.zobrist_seed = cfg->zobrist_seed;
-	d.node_cap = cfg->node_capacity > 0 ? cfg->node_capacity : 8192;
-	d.edge_cap = cfg->edge_capacity > 0 ? cfg->edge_capacity : 524288;
-	d.edge_cap += d.edge_cap & 1; // even: every arena region then starts on a 16-byte boundary (k_arena_copy moves edges as 16-byte words)
-	d.ht_cap = static_cast<int>(round_pow2(4 * static_cast<size_t>(d.node_cap)));
-	d.act_cap = d.hw * (d.hw + 1) / 2 + 64;
-	d.record_cap = cfg->record_capacity > 0 ? cfg->record_capacity : d.n_games * d.hw;
-	d.record_edge_cap = cfg->record_edge_capacity > 0 ? cfg->record_edge_capacity : d.record_cap * 64;
-	d.record_format = cfg->record_format;
-	d.sample_cap = cfg->record_sample_capacity > 0 ? cfg->record_sample_capacity
-			: static_cast<int>(std::min<size_t>(static_cast<size_t>(d.record_cap) * (16 + 6 * static_cast<size_t>(d.hw) + 2), 0x7FFFFFF0u)); // every cell an entry
-	d.game_end_cap = cfg->game_end_capacity > 0 ? cfg->game_end_capacity : std::max(2 * d.n_games, d.record_cap / 16); // the record pool fills first
-
-	HostTables tables;
-	build_host_tables(cfg->rules, tables);
-	std::vector<uint64_t> nc_keys(3 + 3 * d.hw);
-	uint64_t st = cfg->zobrist_seed ^ 0x5851F42D4C957F2Dull;
-	for (auto &k : nc_keys)
-		k = splitmix64(st);
-	e->zobrist.resize(4 * d.hw);
-	st = cfg->zobrist_seed;
-	for (auto &k : e->zobrist)
-		k = splitmix64(st);
-
-	int status = AGX_OK;
-	const size_t G = d.n_games;
-#define AGX_TRY(expr) if (status == AGX_OK) status = (expr)
-	AGX_TRY(dev_alloc(e, &d.games, G));
-	// tree arenas: pool-wide heaps; every game starts with a class-0 bundle (2 x node_cap nodes, 2 x edge_cap edges, ht_cap table slots),
-	// the reserve behind them feeds the games that outgrow theirs (k_arena_service)
-	const double reserve = (cfg->arena_reserve >= 0.0f) ? cfg->arena_reserve : 1.0;
-	const size_t node_total = static_cast<size_t>(static_cast<double>(G * 2 * d.node_cap) * (1.0 + reserve));
-	const size_t edge_total = static_cast<size_t>(static_cast<double>(G * 2 * d.edge_cap) * (1.0 + reserve));
-	const size_t ht_total = static_cast<size_t>(static_cast<double>(G * d.ht_cap) * (1.0 + reserve));
-	AGX_TRY(dev_alloc(e, &d.nodes, node_total));
-	AGX_TRY(dev_alloc(e, &d.edges, edge_total));
-	AGX_TRY(dev_alloc(e, &d.ht, ht_total));
-	AGX_TRY(dev_alloc(e, &d.heap, 1));
-	AGX_TRY(dev_alloc(e, &d.free_bundles, static_cast<size_t>(ARENA_CLASSES) * G));
-	AGX_TRY(dev_alloc(e, &d.tasks, G * d.batch));
-	// speculative solver: its waves solve several leaves of one game at once, so each wave brings its own spill areas (behind the games')
-	e->speculative = cfg->speculative_solver != 0 && cfg->tss_max_positions <= 250 && cfg->max_batch_size <= 16;
-	if (e->speculative)
-	{
-		int cus = e->sizing_cus, device_of_engine = 0;
-		if (!e->sizing_only)
-		{
-			(void) hipGetDevice(&device_of_engine);
-			(void) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_of_engine);
-		}
-		// default: as many waves as the launch's kernel keeps resident (16 per compute unit on 15x15 boards, 10 on 20x20: its LDS state and registers), but
-		// no more than one per leaf of a full batch (a one-tree engine has a few dozen leaves per launch)
-		const int per_cu = spec_resident_waves_per_cu(cfg->rules, cfg->board_size);
-		e->spec_waves = (cfg->speculative_waves > 0) ? cfg->speculative_waves : std::min<long long>(static_cast<long long>(per_cu) * std::max(1, cus), std::max<long long>(64, static_cast<long long>(G) * cfg->max_batch_size));
-		e->spec_waves = std::min(e->spec_waves, SPEC_QUEUE_SLACK);
-	}
-	// (a group's waves take the areas n_games + group * waves + wave with waves = max(1, spec_waves / n_groups): at least one area per possible group)
-	// ... and behind the waves' areas one per park buffer (a parked solve keeps its tails there until the next launch takes it up)
-	const bool parking = e->speculative && cfg->rules == AGX_RENJU && cfg->solver_yield_fraction > 0.0f && !cfg->match_mode && std::max(1, cfg->search_threads) == 1;
-	const size_t areas = G + static_cast<size_t>(std::max(e->spec_waves, 16)) + (parking ? SPEC_PARK_POOL : 0);
-	d.park_area0 = static_cast<int>(G) + std::max(e->spec_waves, 16);
-	d.spec_on = e->speculative ? 1 : 0;
-	d.park_fraction = parking ? SPEC_PARK_FRACTION : 0.0f;
-	if (const char *pf = std::getenv("AGX_PARK_FRACTION")) // (developer knob: the sweep behind SPEC_PARK_FRACTION, profiles/r05_search_variants_ab.txt)
-		if (parking && std::atof(pf) > 0.0)
-			d.park_fraction = std::min(1.0f, static_cast<float>(std::atof(pf))); // (a fraction of the launch's games: (0, 1])
-	AGX_TRY(dev_alloc(e, &d.park_slot, G * d.batch));
-	AGX_TRY(dev_alloc(e, &d.park_owner, SPEC_PARK_POOL));
-	AGX_TRY(dev_alloc(e, &d.parts_done, 2 * G));
-	if (!e->sizing_only)
-		(void) hipMemset(d.parts_done, 0, 2 * G * sizeof(int));
-	AGX_TRY(dev_alloc(e, &d.park_lds, parking ? static_cast<size_t>(SPEC_PARK_POOL) * SPEC_PARK_WORDS : 1));
-	if (!e->sizing_only)
-		(void) hipMemset(d.park_slot, 0, G * d.batch * sizeof(int));
-	if (!e->sizing_only)
-		(void) hipMemset(d.park_owner, 0, SPEC_PARK_POOL * sizeof(int));
-	AGX_TRY(dev_alloc(e, &d.act, areas * d.act_cap));
-	// per area 20 lists x MAXHW entries: list_get / list_set stride by the kernel's compile-time board (SolverSharedT::HW, = MAXHW in the any-size kernels)
-	AGX_TRY(dev_alloc(e, &d.list_spill, areas * 20 * static_cast<size_t>(MAXHW)));
-	AGX_TRY(dev_alloc(e, &d.frame_spill, areas * MAX_FRAMES));
-	AGX_TRY(dev_alloc(e, &d.snap_spill, areas * static_cast<size_t>(d.hw + 2) * 64)); // undo snapshots: 512 bytes per stone on the board and area
-	d.spec_group = 0;
-	d.spec_waves = e->spec_waves;
-	AGX_TRY(dev_alloc(e, &d.spec_watchdog, 16));
-	if (!e->sizing_only)
-		(void) hipMemset(d.spec_watchdog, 0, 16 * sizeof(int));
-	AGX_TRY(dev_alloc(e, &d.spec_prof, 16));
-	AGX_TRY(dev_alloc(e, &d.spec_trace, 4 * (G + static_cast<size_t>(std::max(e->spec_waves, 16))))); // per game, then per wave (profile builds)
-	if (!e->sizing_only)
-		(void) hipMemset(d.spec_trace, 0, 4 * (G + static_cast<size_t>(std::max(e->spec_waves, 16))) * sizeof(unsigned long long));
-	if (!e->sizing_only)
-		(void) hipMemset(d.spec_prof, 0, 16 * sizeof(unsigned long long));
-	AGX_TRY(dev_alloc(e, &d.spec_items, e->speculative ? G * d.batch + 16 * static_cast<size_t>(SPEC_QUEUE_SLACK) : 1));
-	AGX_TRY(dev_alloc(e, &d.spec_left, e->speculative ? G : 1));
-	AGX_TRY(dev_alloc(e, &d.spec_tasks, e->speculative ? G * d.batch : 1));
-	AGX_TRY(dev_alloc(e, &d.spec_overlay, e->speculative ? G * d.batch * (SPEC_OV_CAP * 16) : 1));
-	AGX_TRY(dev_alloc(e, &d.tt, G * buckets * 8));
-	AGX_TRY(dev_upload(e, &d.t_pattern, tables.pattern));
-	AGX_TRY(dev_upload(e, &d.t_ho3, tables.half_open_three));
-	AGX_TRY(dev_upload(e, &d.t_threat, tables.threat));
-	{ // the solver's form of the same table: cross type | circle type << 4 in one byte (dev_solver.hpp:threat_lookup)
-		std::vector<uint8_t> packed(4096);
-		for (int i = 0; i < 4096; i++)
-			packed[i] = static_cast<uint8_t>((tables.threat[2 * i] & 15u) | ((tables.threat[2 * i + 1] & 15u) << 4));
-		AGX_TRY(dev_upload(e, &d.t_threat_packed, packed));
-	}
-	AGX_TRY(dev_upload(e, &d.t_defense, tables.defense));
-	AGX_TRY(dev_upload(e, &d.nc_keys, nc_keys));
-	AGX_TRY(dev_upload(e, &d.zob, e->zobrist));
-	AGX_TRY(dev_alloc(e, &d.nn_features, G * d.batch * d.hw));
-	AGX_TRY(dev_alloc(e, &d.nn_policy, G * d.batch * d.hw));
-	AGX_TRY(dev_alloc(e, &d.nn_value, G * d.batch * 3));
-	d.has_q = cfg->action_values ? 1 : 0;
-	d.match_mode = cfg->match_mode ? 1 : 0;
-	d.prune_root = (cfg->match_mode || !cfg->force_expand_root) ? 1 : 0; // UnifiedGenerator(.., forceExpandRoot): true in self-play (GameGenerator.cpp:183-184), false for a Player (Player.cpp:109)
-	d.search_buffers = (cfg->search_buffers == 2) ? 2 : 1;
-	d.shared_tree = (cfg->search_threads > 1 || d.search_buffers == 2) ? 1 : 0;
-	d.tt_mod = (d.search_buffers == 2) ? std::max(1, cfg->search_threads) : static_cast<int>(G);
-	d.grp_first = 0;
-	d.grp_count = static_cast<int>(G);
-	d.policy_temperature = cfg->policy_temperature;
-	e->player[0] = e->player[1] = player_of(d);
-	AGX_TRY(dev_alloc(e, &d.nn_q, d.has_q ? G * d.batch * d.hw * 2 : 1));
-	AGX_TRY(dev_alloc(e, &d.noise, d.noise_type ? G * d.hw : 1));
-	AGX_TRY(dev_alloc(e, &d.nn_list, G * d.batch));
-	AGX_TRY(dev_alloc(e, &d.counters, N_COUNTERS));
-	AGX_TRY(dev_alloc(e, &d.records, static_cast<size_t>(d.record_cap)));
-	AGX_TRY(dev_alloc(e, &d.record_edges, (d.record_format & 1) ? static_cast<size_t>(d.record_edge_cap) : 1));
-	AGX_TRY(dev_alloc(e, &d.samples, (d.record_format & 2) ? static_cast<size_t>(d.sample_cap) : 4));
-	AGX_TRY(dev_alloc(e, &d.game_ends, static_cast<size_t>(d.game_end_cap)));
-#undef AGX_TRY
-	if (status == AGX_OK)
-	{
-		std::vector<GameState> games(G);
-		std::memset(static_cast<void*>(games.data()), 0, G * sizeof(GameState));
-		for (size_t g = 0; g < G; g++)
-		{
-			games[g].node_off[0] = (2 * g) * d.node_cap;
-			games[g].node_off[1] = (2 * g + 1) * d.node_cap;
-			games[g].edge_off[0] = (2 * g) * static_cast<uint64_t>(d.edge_cap);
-			games[g].edge_off[1] = (2 * g + 1) * static_cast<uint64_t>(d.edge_cap);
-			games[g].ht_off = g * static_cast<uint64_t>(d.ht_cap);
-			games[g].node_cap = d.node_cap;
-			games[g].edge_cap = d.edge_cap;
-			games[g].ht_cap = d.ht_cap;
-		}
-		ArenaHeap heap;
-		std::memset(&heap, 0, sizeof(heap));
-		heap.node_cursor = G * 2 * d.node_cap;
-		heap.edge_cursor = G * 2 * static_cast<uint64_t>(d.edge_cap);
-		heap.ht_cursor = G * static_cast<uint64_t>(d.ht_cap);
-		heap.node_total = node_total;
-		heap.edge_total = edge_total;
-		heap.ht_total = ht_total;
-		heap.free_capacity = static_cast<int32_t>(G);
-		e->idle_games = games;
-		e->idle_heap = heap;
-		hipError_t err = e->sizing_only ? hipSuccess : hipMemcpy(d.games, games.data(), G * sizeof(GameState), hipMemcpyHostToDevice);
-		if (e->sizing_only)
-			err = hipErrorUnknown; // (skips the chain below; reset behind it)
-		if (err == hipSuccess)
-			err = hipMemcpy(d.heap, &heap, sizeof(heap), hipMemcpyHostToDevice);
-		if (err == hipSuccess)
-			err = hipMemset(d.counters, 0, N_COUNTERS * sizeof(int));
-		if (err == hipSuccess)
-			err = hipMemset(d.tasks, 0, G * d.batch * sizeof(DTask));
-		if (err == hipSuccess && e->speculative)
-			err = hipMemset(d.spec_items, 0, (G * d.batch + 16 * static_cast<size_t>(SPEC_QUEUE_SLACK)) * sizeof(int));
-		if (err == hipSuccess && e->speculative)
-			err = hipMemset(d.spec_tasks, 0, G * d.batch * sizeof(SpecTask));
-		if (err == hipSuccess && e->speculative)
-			err = hipMemset(d.spec_left, 0, G * sizeof(int));
-		if (err != hipSuccess && !e->sizing_only)
-		{
-			agx::set_error("hipMemset failed: %s", hipGetErrorString(err));
-			status = AGX_ERR_HIP;
-		}
-	}
-	if (status != AGX_OK)
-	{
-		for (void *p : e->allocations)
-			(void) hipFree(p);
-		delete e;
-		return status;
-	}
-	*out = e;
-	return AGX_OK;
-}
-
-int agx_engine_create(const AgxEngineConfig *cfg, AgxEngine **out)
-{
-	return engine_create(cfg, out, 0);
-}
-
-/* What agx_engine_create(cfg) allocates on a device with `compute_units` compute units, without touching one (a launcher sizing its ranks:
- * GeneratorManager.cpp:146-152 starts one generator thread per device; tests of the multi-GPU plan on a box without a GPU) */
-int agx_engine_estimate_device_bytes(const AgxEngineConfig *cfg, int compute_units, unsigned long long *bytes)
-{
-	AGX_REQUIRE(bytes != nullptr && compute_units > 0, AGX_ERR_INVALID, "agx_engine_estimate_device_bytes: invalid argument");
-	AgxEngine *e = nullptr;
-	const int st = engine_create(cfg, &e, compute_units);
-	if (st != AGX_OK)
-		return st;
-	*bytes = e->device_bytes;
-	delete e;
-	return AGX_OK;
-}
-
-int agx_engine_destroy(AgxEngine *e)
-{
-	if (e == nullptr)
-		return AGX_OK;
-	for (void *p : e->allocations)
-		(void) hipFree(p);
-	for (hipEvent_t ev : e->events)
-		(void) hipEventDestroy(ev);
-	for (hipEvent_t ev : e->free_events)
-		(void) hipEventDestroy(ev);
-	if (e->summary_host != nullptr)
-		(void) hipHostFree(e->summary_host);
-	if (e->match_sum_host != nullptr)
-		(void) hipHostFree(e->match_sum_host);
-	if (e->pair_head_host != nullptr)
-		(void) hipHostFree(e->pair_head_host);
-	if (e->query_host != nullptr)
-		(void) hipHostFree(e->query_host);
-	delete e;
-	return AGX_OK;
-}
-
-int agx_engine_begin(AgxEngine *e, const uint16_t *h_openings, int n_openings, void *stream)
-{
-	AGX_REQUIRE(e != nullptr && h_openings != nullptr, AGX_ERR_INVALID, "agx_engine_begin: null argument");
-	AGX_REQUIRE(n_openings > 0, AGX_ERR_INVALID, "agx_engine_begin: need at least one opening");
-	uint16_t *d_op = nullptr;
-	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_op), static_cast<size_t>(n_openings) * OPENING_CAP * sizeof(uint16_t)));
-	e->allocations.push_back(d_op);
-	AGX_HIP_CHECK(hipMemcpy(d_op, h_openings, static_cast<size_t>(n_openings) * OPENING_CAP * sizeof(uint16_t), hipMemcpyHostToDevice));
-	e->dev.openings = d_op;
-	e->dev.n_openings = n_openings;
-	int counters[N_COUNTERS] = { 0 };
-	counters[1] = e->dev.match_mode ? 0 : (e->dev.shared_tree ? 1 : e->dev.n_games);
-	AGX_HIP_CHECK(hipMemcpy(e->dev.counters, counters, sizeof(counters), hipMemcpyHostToDevice));
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	if (e->pair_log.head != nullptr) // an empty log, zero totals, shadows at "nothing played"
-		AGX_HIP_CHECK(hipMemsetAsync(e->pair_log.head, 0, e->pair_log_bytes, s));
-	hipLaunchKernelGGL(k_begin, dim3(e->dev.n_games), dim3(256), 0, s, e->dev);
-	if (e->dev.match_mode)
-	{ // the pairs take openings 0 .. n_games/2 - 1 in order, exactly as they will after finished matches
-		EngineDev d = e->dev;
-		d.g0 = 0;
-		hipLaunchKernelGGL(k_assign_openings, dim3(1), dim3(1024), 0, s, d, d.n_games / 2);
-		hipLaunchKernelGGL(k_match_restart, dim3(d.n_games / 2), dim3(256), 0, s, d);
-	}
-	AGX_HIP_CHECK(hipGetLastError());
-	e->begun = true;
-	return AGX_OK;
-}
-
-int agx_engine_add_openings(AgxEngine *e, const uint16_t *h_openings, int n_openings)
-{
-	AGX_REQUIRE(e != nullptr && h_openings != nullptr, AGX_ERR_INVALID, "agx_engine_add_openings: null argument");
-	AGX_REQUIRE(n_openings > 0, AGX_ERR_INVALID, "agx_engine_add_openings: need at least one opening");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_add_openings: agx_engine_begin has not been called");
-	AGX_HIP_CHECK(hipDeviceSynchronize());
-	const size_t words_old = static_cast<size_t>(e->dev.n_openings) * OPENING_CAP, words_new = static_cast<size_t>(n_openings) * OPENING_CAP;
-	uint16_t *d_op = nullptr;
-	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_op), (words_old + words_new) * sizeof(uint16_t)));
-	AGX_HIP_CHECK(hipMemcpy(d_op, e->dev.openings, words_old * sizeof(uint16_t), hipMemcpyDeviceToDevice));
-	AGX_HIP_CHECK(hipMemcpy(d_op + words_old, h_openings, words_new * sizeof(uint16_t), hipMemcpyHostToDevice));
-	// the previous table is no longer referenced by any launch (device synchronised above): replace it in the allocation list
-	for (void *&p : e->allocations)
-		if (p == static_cast<const void*>(e->dev.openings))
-		{
-			(void) hipFree(p);
-			p = d_op;
-		}
-	e->dev.openings = d_op;
-	e->dev.n_openings += n_openings;
-	return AGX_OK;
-}
-
-/* games [first, first + count) of group `group` out of `n_groups` equal parts of the pool */
-static int group_range(const AgxEngine *e, int group, int n_groups, EngineDev &d, int &count)
-{
-	// counters[16 + g] / counters[32 + g] are group g's network count and yield count: at most 16 groups
-	AGX_REQUIRE(n_groups >= 1 && n_groups <= 16 && group >= 0 && group < n_groups, AGX_ERR_INVALID, "group %d of %d is not valid (1..16 groups)", group, n_groups);
-	const int per = (e->dev.n_games + n_groups - 1) / n_groups;
-	d = e->dev;
-	d.g0 = group * per;
-	count = std::min(per, e->dev.n_games - d.g0);
-	d.nn_counter = 16 + group;
-	d.yield_counter = 32 + group;
-	AGX_REQUIRE(count > 0, AGX_ERR_INVALID, "group %d of %d is empty for %d games", group, n_groups, e->dev.n_games);
-	AGX_REQUIRE(!e->dev.shared_tree || n_groups == e->dev.search_buffers, AGX_ERR_INVALID,
-			"a tournament-search pool (search_threads) is one tree: it is stepped as a whole, or buffer by buffer (2 groups) when search_buffers = 2 — not in %d groups", n_groups);
-	d.grp_first = d.g0;
-	d.grp_count = count;
-	if (d.match_mode) // a group of a match pool is one player's trees: the launch searches with that player's settings (agx_engine_set_player_search)
-		use_player(d, e->player[(d.g0 >= d.n_games / 2) ? 1 : 0]);
-	return AGX_OK;
-}
-
-static constexpr int CLEAR_PARTS = 16; // workgroups per restarting game in k_clear_tables
-
-#ifdef AGX_QUICK /* developer builds: only the 15x15 non-renju solver is instantiated (a fifth of the compile time) */
-#define AGX_LAUNCH_SOLVE(FUSED) hipLaunchKernelGGL((k_solve<AGX_QUICK_RENJU, 15, FUSED>), grid, block, 0, s, d)
-#else
-#define AGX_LAUNCH_SOLVE(FUSED) \
+#define AGX_FOR_SHAPE(rules, n, USE) \
 	do { \
-		if (d.rules == AGX_RENJU) \
+		if ((rules) == AGX_RENJU) \
 		{ \
-			if (d.n == 15) \
-				hipLaunchKernelGGL((k_solve<true, 15, FUSED>), grid, block, 0, s, d); \
+			if ((n) == 15) \
+				USE(true, 15); \
 			else \
-				hipLaunchKernelGGL((k_solve<true, 0, FUSED>), grid, block, 0, s, d); \
+				USE(true, 0); \
 		} \
-		else if (d.n == 15) \
-			hipLaunchKernelGGL((k_solve<false, 15, FUSED>), grid, block, 0, s, d); \
-		else if (d.n == 20) \
-			hipLaunchKernelGGL((k_solve<false, 20, FUSED>), grid, block, 0, s, d); \
+		else if ((n) == 15) \
+			USE(false, 15); \
+		else if ((n) == 20) \
+			USE(false, 20); \
 		else \
-			hipLaunchKernelGGL((k_solve<false, 0, FUSED>), grid, block, 0, s, d); \
+			USE(false, 0); \
 	} while (0)
 #endif
-__global__ void k_reset_spec(int *nn_counter, int *nn_second, int *spec_counters, int *done_counter)
+
+namespace agx_eng
+{
+	/* the instantiation of k_search_spec a pool of these rules and board size launches; merged: the variant for a match pool's launch over
+	 * both players' trees (k_search_spec's MERGED) */
+	typedef void (*SpecKernel)(EngineDev, int);
+	static SpecKernel spec_kernel(int rules, int n, bool merged)
+	{
+		SpecKernel kernel = nullptr;
+#define AGX_USE(RENJU, NFIX) kernel = merged ? k_search_spec<RENJU, NFIX, true> : k_search_spec<RENJU, NFIX, false>
+		AGX_FOR_SHAPE(rules, n, AGX_USE);
+#undef AGX_USE
+		return kernel;
+	}
+	int spec_resident_waves_per_cu(int rules, int n)
+	{
+		int blocks = 0;
+		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(spec_kernel(rules, n, false)), 64, 0) != hipSuccess || blocks <= 0)
+		{
+			(void) hipGetLastError();
+			return 12;
+		}
+		return blocks;
+	}
+	void search_spec(const EngineDev &d, int count, hipStream_t s)
+	{
+		hipLaunchKernelGGL(spec_kernel(d.rules, d.n, d.match_merged != 0), dim3(d.spec_waves), dim3(64), 0, s, d, count);
+	}
+	void begin(const EngineDev &d, hipStream_t s)
+	{
+		hipLaunchKernelGGL(k_begin, dim3(d.n_games), dim3(256), 0, s, d);
+	}
+	void assign_openings(const EngineDev &d, int count, hipStream_t s)
+	{
+		hipLaunchKernelGGL(k_assign_openings, dim3(1), dim3(1024), 0, s, d, count);
+	}
+	void match_restart(const EngineDev &d, int pairs, hipStream_t s)
+	{
+		hipLaunchKernelGGL(k_match_restart, dim3(pairs), dim3(256), 0, s, d);
+	}
+}
+
+extern "C" __global__ void k_reset_spec(int *nn_counter, int *nn_second, int *spec_counters, int *done_counter) // (its unmangled name is in the committed traces)
 {
 	*nn_counter = 0;
 	*done_counter = 0;
@@ -4714,2148 +4112,130 @@ __global__ void k_reset_spec(int *nn_counter, int *nn_second, int *spec_counters
 	for (int i = 0; i < 4; i++)
 		spec_counters[i] = 0;
 }
-/* select + speculative solve + scheduleToNN of `count` games from d.g0 as one persistent launch of `waves` waves (k_search_spec) */
-static void launch_search_spec(EngineDev d, int count, int group, int waves, hipStream_t s)
-{
-	d.spec_group = group;
-	d.spec_waves = waves;
-	const dim3 grid(waves), block(64);
-	hipLaunchKernelGGL(spec_kernel(d.rules, d.n, d.match_merged != 0), grid, block, 0, s, d, count);
-}
-static void launch_solve(const EngineDev &d, int count, hipStream_t s, bool with_select = false)
-{
-	const dim3 grid(count), block(64);
-	if (with_select)
-		AGX_LAUNCH_SOLVE(true);
-	else
-		AGX_LAUNCH_SOLVE(false);
-}
-#undef AGX_LAUNCH_SOLVE
 
-/* Search::select for every game of the group (Search.cpp:117-158) */
-int agx_engine_select_group(AgxEngine *e, int group, int n_groups, void *stream)
+namespace agx_eng
 {
-	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_engine_select: null engine");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_select: agx_engine_begin has not been called");
-	EngineDev d;
-	int count = 0;
-	const int st = group_range(e, group, n_groups, d, count);
-	if (st != AGX_OK)
-		return st;
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	hipLaunchKernelGGL(k_reset_counter, dim3(1), dim3(1), 0, s, d.counters + d.nn_counter, d.counters + d.yield_counter);
+	void reset_spec(int *nn_counter, int *nn_second, int *spec_counters, int *done_counter, hipStream_t s)
 	{
-		KernelTimer t(e, s, 0);
-		hipLaunchKernelGGL(k_select, dim3(d.shared_tree ? 1 : count), dim3(64), 0, s, d); // tournament search: one wave walks the threads in turn
+		hipLaunchKernelGGL(k_reset_spec, dim3(1), dim3(1), 0, s, nn_counter, nn_second, spec_counters, done_counter);
 	}
-	AGX_HIP_CHECK(hipGetLastError());
-	return AGX_OK;
-}
-/* Search::solve + Search::scheduleToNN (Search.cpp:159-199): the threat solver on the selected leaves, then the device-side queue */
-int agx_engine_solve_group(AgxEngine *e, int group, int n_groups, void *stream)
-{
-	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_engine_solve: null engine");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_solve: agx_engine_begin has not been called");
-	EngineDev d;
-	int count = 0;
-	const int st = group_range(e, group, n_groups, d, count);
-	if (st != AGX_OK)
-		return st;
-	hipStream_t s = static_cast<hipStream_t>(stream);
+	void solve(const EngineDev &d, int count, bool with_select, hipStream_t s)
 	{
-		KernelTimer t(e, s, 1);
-		launch_solve(d, count, s);
+		const dim3 grid(count), block(64);
+#define AGX_USE_FUSED(RENJU, NFIX) hipLaunchKernelGGL((k_solve<RENJU, NFIX, true>), grid, block, 0, s, d)
+#define AGX_USE_SPLIT(RENJU, NFIX) hipLaunchKernelGGL((k_solve<RENJU, NFIX, false>), grid, block, 0, s, d)
+		if (with_select)
+			AGX_FOR_SHAPE(d.rules, d.n, AGX_USE_FUSED);
+		else
+			AGX_FOR_SHAPE(d.rules, d.n, AGX_USE_SPLIT);
+#undef AGX_USE_FUSED
+#undef AGX_USE_SPLIT
 	}
-	AGX_HIP_CHECK(hipGetLastError());
-	return AGX_OK;
-}
-/* Search::solve(endTime >= 0) (Search.cpp:159-183, the call of SearchThread::asynchronous_run): node limit `max_nodes` (the reference sets
- * 10 000) and a time budget of `seconds` from the moment the launch starts, shared out task by task like the reference does.  Always the
- * serial solver (one wave per game, straight on the table): overlays of speculative solves hold 256 buckets. */
-int agx_engine_solve_timed_group(AgxEngine *e, int group, int n_groups, int max_nodes, double seconds, void *stream)
-{
-	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_engine_solve_timed: null engine");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_solve_timed: agx_engine_begin has not been called");
-	AGX_REQUIRE(max_nodes >= 1 && max_nodes <= 100000, AGX_ERR_INVALID, "agx_engine_solve_timed: node limit %d outside [1, 100000]", max_nodes);
-	EngineDev d;
-	int count = 0;
-	const int st = group_range(e, group, n_groups, d, count);
-	if (st != AGX_OK)
-		return st;
-	d.tss_max_nodes = max_nodes;
-	d.yield_fraction = 0.0f; // every task is solved in this launch: the time limit is what bounds it
-	d.solve_time_ticks = (seconds <= 0.0) ? 1ull : static_cast<unsigned long long>(std::min(seconds, 3600.0) * 1.0e8) + 1ull;
-	hipStream_t s = static_cast<hipStream_t>(stream);
+	void reset_counter(int *counter, int *second, hipStream_t s)
 	{
-		KernelTimer t(e, s, 1);
-		launch_solve(d, count, s);
+		hipLaunchKernelGGL(k_reset_counter, dim3(1), dim3(1), 0, s, counter, second);
 	}
-	AGX_HIP_CHECK(hipGetLastError());
-	return AGX_OK;
-}
-int agx_engine_select_solve_group(AgxEngine *e, int group, int n_groups, void *stream)
-{
-	if (e != nullptr && e->begun && e->speculative)
-	{ // one persistent launch: games select off a cursor, their leaves are solved in parallel against overlays, committed in batch order
-		EngineDev d;
-		int count = 0;
-		const int st = group_range(e, group, n_groups, d, count);
-		if (st != AGX_OK)
-			return st;
-		hipStream_t s = static_cast<hipStream_t>(stream);
-		hipLaunchKernelGGL(k_reset_spec, dim3(1), dim3(1), 0, s, d.counters + d.nn_counter, static_cast<int*>(nullptr), d.counters + SPEC_COUNTER0 + 4 * group,
-				d.counters + d.yield_counter);
-		if (d.shared_tree)
-		{ // tournament search: the threads descend the one tree in turn (one wave), then their leaves are solved in parallel
-			KernelTimer t(e, s, 0);
-			hipLaunchKernelGGL(k_select, dim3(1), dim3(64), 0, s, d);
-		}
-		{
-			KernelTimer t(e, s, 1);
-			launch_search_spec(d, count, group, std::max(1, e->spec_waves / n_groups), s);
-		}
-		AGX_HIP_CHECK(hipGetLastError());
-		return AGX_OK;
-	}
-	if (e != nullptr && e->begun && e->fuse_select && !e->dev.shared_tree)
-	{ // one launch: every game selects and solves in its own wave (k_solve<.., FUSED>); timed as the solve stage
-		EngineDev d;
-		int count = 0;
-		const int st = group_range(e, group, n_groups, d, count);
-		if (st != AGX_OK)
-			return st;
-		hipStream_t s = static_cast<hipStream_t>(stream);
-		hipLaunchKernelGGL(k_reset_counter, dim3(1), dim3(1), 0, s, d.counters + d.nn_counter, d.counters + d.yield_counter);
-		{
-			KernelTimer t(e, s, 1);
-			launch_solve(d, count, s, true);
-		}
-		AGX_HIP_CHECK(hipGetLastError());
-		return AGX_OK;
-	}
-	const int st = agx_engine_select_group(e, group, n_groups, stream);
-	return (st != AGX_OK) ? st : agx_engine_solve_group(e, group, n_groups, stream);
-}
-
-/* match mode, both players' trees in one launch per stage: about half of the trees search at any time, so one launch over all of
- * them keeps the GPU as busy as a self-play pool of n_games / 2; only the network stage is split (one slot list per player) */
-static int match_launch(AgxEngine *e, EngineDev &d)
-{
-	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_engine_*_match: null engine");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_*_match: agx_engine_begin has not been called");
-	AGX_REQUIRE(e->dev.match_mode, AGX_ERR_STATE, "agx_engine_*_match: the engine was not created with match_mode");
-	d = e->dev;
-	d.g0 = 0;
-	d.nn_counter = 16;
-	d.yield_counter = 32;
-	d.match_merged = 1;
-	d.player[0] = e->player[0]; // the kernels pick a tree's settings by its half of the pool (dev::use_player_search)
-	d.player[1] = e->player[1];
-	use_player(d, e->player[0]);
-	return AGX_OK;
-}
-int agx_engine_select_solve_match(AgxEngine *e, void *stream)
-{
-	EngineDev d;
-	const int st = match_launch(e, d);
-	if (st != AGX_OK)
-		return st;
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	hipLaunchKernelGGL(k_reset_counter, dim3(1), dim3(1), 0, s, d.counters + 16, d.counters + 32);
-	hipLaunchKernelGGL(k_reset_counter, dim3(1), dim3(1), 0, s, d.counters + 17, static_cast<int*>(nullptr));
-	if (e->speculative)
+	void select(const EngineDev &d, int waves, hipStream_t s)
 	{
-		hipLaunchKernelGGL(k_reset_spec, dim3(1), dim3(1), 0, s, d.counters + 16, d.counters + 17, d.counters + SPEC_COUNTER0, d.counters + 32);
-		KernelTimer t(e, s, 1);
-		launch_search_spec(d, d.n_games, 0, e->spec_waves, s);
+		hipLaunchKernelGGL(k_select, dim3(waves), dim3(64), 0, s, d);
 	}
-	else if (e->fuse_select)
+	void expand_merged(const EngineDev &d, hipStream_t s)
 	{
-		KernelTimer t(e, s, 1);
-		launch_solve(d, d.n_games, s, true);
-	}
-	else
-	{
-		{
-			KernelTimer t(e, s, 0);
-			hipLaunchKernelGGL(k_select, dim3(d.n_games), dim3(64), 0, s, d);
-		}
-		{
-			KernelTimer t(e, s, 1);
-			launch_solve(d, d.n_games, s);
-		}
-	}
-	AGX_HIP_CHECK(hipGetLastError());
-	return AGX_OK;
-}
-int agx_engine_expand_backup_match(AgxEngine *e, void *stream)
-{
-	EngineDev d;
-	const int st = match_launch(e, d);
-	if (st != AGX_OK)
-		return st;
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	{
-		KernelTimer t(e, s, 2);
 		hipLaunchKernelGGL(k_expand<true>, dim3(d.n_games), dim3(64), 0, s, d);
 	}
+	void advance_merged(const EngineDev &d, hipStream_t s)
 	{
-		KernelTimer t(e, s, 3);
-		// a moving tree's workgroup also rebases its partner's tree; the partner's own workgroup has nothing to do (it is not searching)
 		hipLaunchKernelGGL(k_advance<true>, dim3(d.n_games), dim3(ADV_THREADS), 0, s, d);
-		if (e->pair_log.head != nullptr) // agx_engine_match_track_pairs: the openings this launch finished, in pair order
-			hipLaunchKernelGGL(k_match_pair_log, dim3(1), dim3(256), 0, s, d, e->pair_log);
-		hipLaunchKernelGGL(k_arena_service, dim3(1), dim3(1024), 0, s, d, d.n_games, 0);
-		hipLaunchKernelGGL(k_arena_copy, dim3(d.n_games * CLEAR_PARTS), dim3(256), 0, s, d, CLEAR_PARTS); // (its last part per game commits)
-		hipLaunchKernelGGL(k_assign_openings, dim3(1), dim3(1024), 0, s, d, d.n_games / 2);
-		hipLaunchKernelGGL(k_clear_tables, dim3(d.n_games * CLEAR_PARTS), dim3(256), 0, s, d, CLEAR_PARTS, 0);
-		hipLaunchKernelGGL(k_match_restart, dim3(d.n_games / 2), dim3(256), 0, s, d);
 	}
-	AGX_HIP_CHECK(hipGetLastError());
-	return AGX_OK;
-}
-int agx_engine_step_match(AgxEngine *e, AgxNet *first_net, AgxNet *second_net, void *stream)
-{
-	if (e != nullptr && e->dev.match_mode && first_net != nullptr && second_net != nullptr)
-	{ // a network without the head a player asks for is refused before anything is launched, not between the two players' forwards
-		AgxNet *nets[2] = { first_net, second_net };
-		for (int p = 0; p < 2; p++)
-		{
-			AgxNetDesc desc;
-			const int ds = agx_net_description(nets[p], &desc);
-			if (ds != AGX_OK)
-				return ds;
-			AGX_REQUIRE(!e->player[p].has_q || desc.action_values, AGX_ERR_INVALID,
-					"agx_engine_step_match: the %s player is configured for a 'pvq' network but its network has no action-values head", p == 0 ? "first" : "second");
-		}
-	}
-	int st = agx_engine_select_solve_match(e, stream);
-	if (st == AGX_OK)
-		st = agx_engine_evaluate_group(e, first_net, 0, 2, stream);
-	if (st == AGX_OK)
-		st = agx_engine_evaluate_group(e, second_net, 1, 2, stream);
-	if (st == AGX_OK)
-		st = agx_engine_expand_backup_match(e, stream);
-	return st;
-}
-
-int agx_engine_evaluate_group(AgxEngine *e, AgxNet *net, int group, int n_groups, void *stream)
-{
-	AGX_REQUIRE(e != nullptr && net != nullptr, AGX_ERR_INVALID, "agx_engine_evaluate: null argument");
-	EngineDev d;
-	int count = 0;
-	const int st = group_range(e, group, n_groups, d, count);
-	if (st != AGX_OK)
-		return st;
-	AgxNetDesc desc;
-	const int ds = agx_net_description(net, &desc);
-	if (ds != AGX_OK)
-		return ds;
-	// the exchange buffers are laid out with the ENGINE's board (hw cells per slot): a network of another geometry would index them with
-	// the wrong stride
-	AGX_REQUIRE(desc.rows == d.n && desc.cols == d.n, AGX_ERR_INVALID, "agx_engine_evaluate: the network is built for %dx%d boards, the engine plays on %dx%d",
-			desc.rows, desc.cols, d.n, d.n);
-	if (d.has_q)
+	void match_pair_log(const EngineDev &d, const PairLogDev &log, hipStream_t s)
 	{
-		AGX_REQUIRE(desc.action_values, AGX_ERR_INVALID, "agx_engine_evaluate: the engine was configured for a 'pvq' network but this one has no action-values head");
-		return agx_nn_forward_indirect_pvq(net, d.nn_features, d.nn_list + static_cast<size_t>(d.g0) * d.batch, d.counters + d.nn_counter, count * d.batch,
-				d.nn_policy, d.nn_value, d.nn_q, stream);
+		hipLaunchKernelGGL(k_match_pair_log, dim3(1), dim3(256), 0, s, d, log);
 	}
-	return agx_nn_forward_indirect(net, d.nn_features, d.nn_list + static_cast<size_t>(d.g0) * d.batch, d.counters + d.nn_counter, count * d.batch, d.nn_policy,
-			d.nn_value, stream);
-}
-
-/* Search::generateEdges + expand + backup for every game of the group (Search.cpp:206-232), incl. the move rule's decision */
-static int expand_stage(AgxEngine *e, int group, int n_groups, void *stream, bool service_arenas)
-{
-	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_engine_expand: null engine");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_expand: agx_engine_begin has not been called");
-	EngineDev d;
-	int count = 0;
-	const int st = group_range(e, group, n_groups, d, count);
-	if (st != AGX_OK)
-		return st;
-	AGX_REQUIRE(!d.match_mode || n_groups == 2, AGX_ERR_INVALID, "agx_engine_expand: a match-mode engine is stepped as two groups (first players, second players)");
-	hipStream_t s = static_cast<hipStream_t>(stream);
+	void arena_service(const EngineDev &d, int count, int assign_count, hipStream_t s)
 	{
-		KernelTimer t(e, s, 2);
-		hipLaunchKernelGGL(k_expand<false>, dim3(d.shared_tree ? 1 : count), dim3(64), 0, s, d);
+		hipLaunchKernelGGL(k_arena_service, dim3(1), dim3(1024), 0, s, d, count, assign_count);
 	}
-	if (service_arenas && e->external_moves && !d.match_mode)
-	{ // a caller that makes the moves itself (set_board) never runs the advance stage: the trees that asked for larger arenas get them here
-	  // (a pool stepped through expand_group + advance_group — ag::Search::expand, then GameGenerator — has them serviced ONCE, by the advance stage)
-		const int trees = d.shared_tree ? 1 : count;
-		if (d.shared_tree)
-			d.g0 = 0;
-		hipLaunchKernelGGL(k_arena_service, dim3(1), dim3(1024), 0, s, d, trees, 0);
-		hipLaunchKernelGGL(k_arena_copy, dim3(trees * CLEAR_PARTS), dim3(256), 0, s, d, CLEAR_PARTS); // (its last part per game commits)
-	}
-	AGX_HIP_CHECK(hipGetLastError());
-	return AGX_OK;
-}
-int agx_engine_expand_group(AgxEngine *e, int group, int n_groups, void *stream)
-{
-	return expand_stage(e, group, n_groups, stream, true);
-}
-/* GameGenerator::make_move + prepare_search for the games whose search is complete (GameGenerator.cpp:145-185), then the next openings
- * for the games that ended */
-int agx_engine_advance_group(AgxEngine *e, int group, int n_groups, void *stream)
-{
-	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_engine_advance: null engine");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_advance: agx_engine_begin has not been called");
-	EngineDev d;
-	int count = 0;
-	const int st = group_range(e, group, n_groups, d, count);
-	if (st != AGX_OK)
-		return st;
-	AGX_REQUIRE(!d.match_mode || n_groups == 2, AGX_ERR_INVALID, "agx_engine_advance: a match-mode engine is stepped as two groups (first players, second players)");
-	hipStream_t s = static_cast<hipStream_t>(stream);
+	void arena_copy(const EngineDev &d, int trees, hipStream_t s)
 	{
-		KernelTimer t(e, s, 3);
-		const int trees = d.shared_tree ? 1 : count; // tournament search: one tree (game 0), the other records are its search threads
-		if (d.shared_tree)
-		{ // (whichever buffer this group is: the tree, its arenas and the restart are record 0's; grp_first / grp_count keep the buffer)
-			d.g0 = 0;
-			count = d.n_games;
-		}
-		hipLaunchKernelGGL(k_advance<false>, dim3(trees), dim3(ADV_THREADS), 0, s, d);
-		if (e->pair_log.head != nullptr) // (a match pool that tracks its pairs: either player's move may have ended an opening)
-			hipLaunchKernelGGL(k_match_pair_log, dim3(1), dim3(256), 0, s, d, e->pair_log);
-		// four launches behind k_advance instead of seven (round 6): the openings are assigned by the service workgroup, a game's last copy part
-		// commits its larger arenas, a game's last clear part restarts it
-		hipLaunchKernelGGL(k_arena_service, dim3(1), dim3(1024), 0, s, d, trees, d.match_mode ? 0 : trees);
 		hipLaunchKernelGGL(k_arena_copy, dim3(trees * CLEAR_PARTS), dim3(256), 0, s, d, CLEAR_PARTS);
-		if (!d.match_mode)
-		{
-			hipLaunchKernelGGL(k_clear_tables, dim3(count * CLEAR_PARTS), dim3(256), 0, s, d, CLEAR_PARTS, d.shared_tree ? 0 : 1);
-			if (d.shared_tree)
-			{ // the search threads restart on thread 0's opening: they first (they read its request), thread 0 last (it clears the request)
-				EngineDev others = d;
-				others.g0 = 1;
-				if (count > 1)
-					hipLaunchKernelGGL(k_restart, dim3(count - 1), dim3(256), 0, s, others);
-				hipLaunchKernelGGL(k_restart, dim3(1), dim3(256), 0, s, d);
-			}
-
-		}
-		else if (group == 0)
-		{ // restarts go by pair, requested through the first players' trees (= group 0)
-			hipLaunchKernelGGL(k_assign_openings, dim3(1), dim3(1024), 0, s, d, count);
-			{
-				EngineDev all = d; // both players' trees
-				all.g0 = 0;
-				hipLaunchKernelGGL(k_clear_tables, dim3(all.n_games * CLEAR_PARTS), dim3(256), 0, s, all, CLEAR_PARTS, 0);
-			}
-			hipLaunchKernelGGL(k_match_restart, dim3(count), dim3(256), 0, s, d);
-		}
 	}
-	AGX_HIP_CHECK(hipGetLastError());
-	return AGX_OK;
-}
-int agx_engine_expand_backup_group(AgxEngine *e, int group, int n_groups, void *stream)
-{
-	const int st = expand_stage(e, group, n_groups, stream, false); // (the advance stage services the arenas)
-	return (st != AGX_OK) ? st : agx_engine_advance_group(e, group, n_groups, stream);
-}
-
-int agx_engine_step_group(AgxEngine *e, AgxNet *net, int group, int n_groups, void *stream)
-{
-	int st = agx_engine_select_solve_group(e, group, n_groups, stream);
-	if (st == AGX_OK)
-		st = agx_engine_evaluate_group(e, net, group, n_groups, stream);
-	if (st == AGX_OK)
-		st = agx_engine_expand_backup_group(e, group, n_groups, stream);
-	return st;
-}
-
-int agx_engine_select_solve(AgxEngine *e, void *stream) { return agx_engine_select_solve_group(e, 0, 1, stream); }
-int agx_engine_evaluate(AgxEngine *e, AgxNet *net, void *stream) { return agx_engine_evaluate_group(e, net, 0, 1, stream); }
-int agx_engine_expand_backup(AgxEngine *e, void *stream) { return agx_engine_expand_backup_group(e, 0, 1, stream); }
-int agx_engine_step(AgxEngine *e, AgxNet *net, void *stream) { return agx_engine_step_group(e, net, 0, 1, stream); }
-
-int agx_engine_buffers(AgxEngine *e, AgxEngineBuffers *out)
-{
-	AGX_REQUIRE(e != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_engine_buffers: null argument");
-	out->d_nn_features = e->dev.nn_features;
-	out->d_nn_policy = e->dev.nn_policy;
-	out->d_nn_value = e->dev.nn_value;
-	out->d_nn_action_values = e->dev.has_q ? e->dev.nn_q : nullptr;
-	out->d_nn_list = e->dev.nn_list;
-	out->d_nn_count = e->dev.counters + 16; /* group 0 of 1 */
-	out->slots = e->dev.n_games * e->dev.batch;
-	out->cells = e->dev.hw;
-	return AGX_OK;
-}
-
-int agx_engine_match_results(AgxEngine *e, int *h_results, int pair_capacity)
-{
-	AGX_REQUIRE(e != nullptr && h_results != nullptr, AGX_ERR_INVALID, "agx_engine_match_results: null argument");
-	AGX_REQUIRE(e->dev.match_mode, AGX_ERR_STATE, "agx_engine_match_results: the engine was not created with match_mode");
-	const int pairs = e->dev.n_games / 2;
-	AGX_REQUIRE(pair_capacity >= pairs, AGX_ERR_INVALID, "agx_engine_match_results: %d pairs do not fit into %d", pairs, pair_capacity);
-	AGX_HIP_CHECK(hipDeviceSynchronize());
-	std::vector<GameState> games(pairs);
-	AGX_HIP_CHECK(hipMemcpy(games.data(), e->dev.games, games.size() * sizeof(GameState), hipMemcpyDeviceToHost));
-	for (int i = 0; i < pairs; i++)
+	void clear_tables(const EngineDev &d, int games, int restart, hipStream_t s)
 	{
-		h_results[4 * i + 0] = games[i].match_score[0];
-		h_results[4 * i + 1] = games[i].match_score[1];
-		h_results[4 * i + 2] = games[i].match_score[2];
-		h_results[4 * i + 3] = games[i].games_done;
+		hipLaunchKernelGGL(k_clear_tables, dim3(games * CLEAR_PARTS), dim3(256), 0, s, d, CLEAR_PARTS, restart);
 	}
-	return AGX_OK;
-}
-
-/* ---- match pools: the pair log (k_match_pair_log) ---- */
-int agx_engine_match_track_pairs(AgxEngine *e, int capacity)
-{
-	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_engine_match_track_pairs: null engine");
-	AGX_REQUIRE(e->dev.match_mode, AGX_ERR_STATE, "agx_engine_match_track_pairs: the engine was not created with match_mode");
-	AGX_REQUIRE(!e->begun, AGX_ERR_STATE, "agx_engine_match_track_pairs: call it before agx_engine_begin");
-	AGX_REQUIRE(capacity >= 1, AGX_ERR_INVALID, "agx_engine_match_track_pairs: capacity %d, need at least 1", capacity);
-	AGX_REQUIRE(e->pair_log.head == nullptr, AGX_ERR_STATE, "agx_engine_match_track_pairs: the pool already tracks its pairs (capacity %d)", e->pair_log.capacity);
-	const size_t pairs = static_cast<size_t>(e->dev.n_games / 2);
-	const size_t bytes = PAIR_LOG_HEAD * sizeof(long long) + pairs * sizeof(int4) + static_cast<size_t>(capacity) * sizeof(AgxPairResult);
-	if (e->pair_head_host == nullptr)
-		AGX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e->pair_head_host), PAIR_LOG_HEAD * sizeof(long long), hipHostMallocDefault));
-	uint8_t *p = nullptr;
-	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), bytes));
-	e->allocations.push_back(p);
-	e->device_bytes += bytes;
-	AGX_HIP_CHECK(hipMemset(p, 0, bytes));
-	e->pair_log.head = reinterpret_cast<long long*>(p);
-	e->pair_log.shadow = reinterpret_cast<int4*>(p + PAIR_LOG_HEAD * sizeof(long long));
-	e->pair_log.entries = reinterpret_cast<AgxPairResult*>(p + PAIR_LOG_HEAD * sizeof(long long) + pairs * sizeof(int4));
-	e->pair_log.capacity = capacity;
-	e->pair_log_bytes = bytes;
-	return AGX_OK;
-}
-
-int agx_engine_match_pair_results(AgxEngine *e, int first, AgxPairResult *h_out, int capacity, long long totals[8], void *stream)
-{
-	AGX_REQUIRE(e != nullptr && totals != nullptr, AGX_ERR_INVALID, "agx_engine_match_pair_results: null argument");
-	AGX_REQUIRE(first >= 0 && capacity >= 0 && (h_out != nullptr || capacity == 0), AGX_ERR_INVALID,
-			"agx_engine_match_pair_results: first %d, capacity %d%s", first, capacity, h_out == nullptr ? " with a null buffer" : "");
-	AGX_REQUIRE(e->dev.match_mode, AGX_ERR_STATE, "agx_engine_match_pair_results: the engine was not created with match_mode");
-	AGX_REQUIRE(e->pair_log.head != nullptr, AGX_ERR_STATE, "agx_engine_match_pair_results: the pool does not track its pairs (agx_engine_match_track_pairs)");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_match_pair_results: agx_engine_begin has not been called");
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	AGX_HIP_CHECK(hipMemcpyAsync(e->pair_head_host, e->pair_log.head, 9 * sizeof(long long), hipMemcpyDeviceToHost, s));
-	AGX_HIP_CHECK(hipStreamSynchronize(s));
-	std::memcpy(totals, e->pair_head_host, 8 * sizeof(long long));
-	const long long logged = e->pair_head_host[8]; // (<= the log's capacity: the kernel's cursor)
-	const long long end = std::min(logged, static_cast<long long>(first) + capacity);
-	if (end > first)
-	{ // the entries are final once written: a later launch only appends
-		AGX_HIP_CHECK(hipMemcpyAsync(h_out, e->pair_log.entries + first, static_cast<size_t>(end - first) * sizeof(AgxPairResult), hipMemcpyDeviceToHost, s));
-		AGX_HIP_CHECK(hipStreamSynchronize(s));
-	}
-	return AGX_OK;
-}
-
-int agx_engine_set_board(AgxEngine *e, int game, const uint8_t *h_board, int sign_to_move, void *stream)
-{
-	return agx_engine_set_board_ex(e, game, h_board, sign_to_move, 0, stream);
-}
-int agx_engine_set_board_ex(AgxEngine *e, int game, const uint8_t *h_board, int sign_to_move, int force_remove_root, void *stream)
-{
-	AGX_REQUIRE(e != nullptr && h_board != nullptr, AGX_ERR_INVALID, "agx_engine_set_board: null argument");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_set_board: agx_engine_begin has not been called");
-	AGX_REQUIRE(game >= 0 && game < e->dev.n_games, AGX_ERR_INVALID, "agx_engine_set_board: game %d of %d", game, e->dev.n_games);
-	AGX_REQUIRE(sign_to_move == 1 || sign_to_move == 2, AGX_ERR_INVALID, "agx_engine_set_board: sign_to_move must be 1 (cross) or 2 (circle)");
-	AGX_REQUIRE(!e->dev.match_mode, AGX_ERR_STATE, "agx_engine_set_board: a match-mode engine plays its own games");
-	AGX_REQUIRE(!e->dev.shared_tree || game == 0, AGX_ERR_INVALID, "agx_engine_set_board: a tournament-search engine has one tree, game 0 (records 1.. are its task buffers)");
-	for (int i = 0; i < e->dev.hw; i++)
-		AGX_REQUIRE(h_board[i] <= 2, AGX_ERR_INVALID, "agx_engine_set_board: cell %d holds %d (0 empty, 1 cross, 2 circle)", i, h_board[i]);
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	if (e->board_staging == nullptr)
+	void expand(const EngineDev &d, int waves, hipStream_t s)
 	{
-		AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->board_staging), MAXHW));
-		e->allocations.push_back(e->board_staging);
+		hipLaunchKernelGGL(k_expand<false>, dim3(waves), dim3(64), 0, s, d);
 	}
-	AGX_HIP_CHECK(hipStreamSynchronize(s)); // (the staging buffer of the previous call may still be read)
-	AGX_HIP_CHECK(hipMemcpy(e->board_staging, h_board, e->dev.hw, hipMemcpyHostToDevice));
-	{ // Player::setBoard begins with search.cleanup(tree) (Player.cpp:98-100): leaves still in flight give their virtual losses back first
-		EngineDev one = e->dev;
-		one.g0 = game;
-		hipLaunchKernelGGL(k_cancel_pending, dim3(1), dim3(64), 0, s, one);
-	}
-	hipLaunchKernelGGL(k_set_board, dim3(1), dim3(256), 0, s, e->dev, game, e->board_staging, sign_to_move, force_remove_root ? 1 : 0);
-	e->external_moves = true;
-	AGX_HIP_CHECK(hipGetLastError());
-	return AGX_OK;
-}
-/* GeneratorThread::saveGames / loadGames (GeneratorManager.cpp:98-122) on the device pool: the games in flight as their move lists */
-int agx_engine_save_games(AgxEngine *e, AgxSavedGame *h_out, int capacity, int *count)
-{
-	AGX_REQUIRE(e != nullptr && count != nullptr, AGX_ERR_INVALID, "agx_engine_save_games: null argument");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_save_games: agx_engine_begin has not been called");
-	AGX_REQUIRE(!e->dev.match_mode && !e->dev.shared_tree, AGX_ERR_UNSUPPORTED, "agx_engine_save_games: self-play pools only");
-	AGX_HIP_CHECK(hipDeviceSynchronize());
-	std::vector<GameState> games(e->dev.n_games);
-	AGX_HIP_CHECK(hipMemcpy(games.data(), e->dev.games, games.size() * sizeof(GameState), hipMemcpyDeviceToHost));
-	int n = 0;
-	for (size_t g = 0; g < games.size(); g++)
+	void advance(const EngineDev &d, int trees, hipStream_t s)
 	{
-		const GameState &gs = games[g];
-		if (!gs.active || gs.outcome != 0 || gs.error != 0)
-			continue; // waiting for an opening, finished (its record is already in the pools) or stopped
-		if (h_out != nullptr)
-		{
-			AGX_REQUIRE(n < capacity, AGX_ERR_INVALID, "agx_engine_save_games: more than %d games in flight", capacity);
-			AgxSavedGame &o = h_out[n];
-			std::memset(&o, 0, sizeof(o));
-			o.game_slot = static_cast<int>(g);
-			o.game_index = gs.games_done;
-			o.opening_id = gs.opening_id;
-			o.sign_to_move = gs.sign_to_move;
-			o.nn_queued = gs.nn_queued;
-			o.n_moves = gs.n_moves;
-			for (int i = 0; i < gs.n_moves; i++)
-				o.moves[i] = gs.moves[i];
-		}
-		n++;
+		hipLaunchKernelGGL(k_advance<false>, dim3(trees), dim3(ADV_THREADS), 0, s, d);
 	}
-	*count = n;
-	return AGX_OK;
-}
-int agx_engine_restore_game(AgxEngine *e, const AgxSavedGame *game, void *stream)
-{
-	AGX_REQUIRE(e != nullptr && game != nullptr, AGX_ERR_INVALID, "agx_engine_restore_game: null argument");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_restore_game: agx_engine_begin has not been called");
-	AGX_REQUIRE(!e->dev.match_mode && !e->dev.shared_tree, AGX_ERR_UNSUPPORTED, "agx_engine_restore_game: self-play pools only");
-	AGX_REQUIRE(game->game_slot >= 0 && game->game_slot < e->dev.n_games, AGX_ERR_INVALID, "agx_engine_restore_game: slot %d of %d", game->game_slot, e->dev.n_games);
-	AGX_REQUIRE(game->n_moves >= 0 && game->n_moves < e->dev.hw, AGX_ERR_INVALID, "agx_engine_restore_game: %d moves on a board of %d cells", game->n_moves, e->dev.hw);
-	std::vector<uint8_t> seen(e->dev.hw, 0);
-	for (int i = 0; i < game->n_moves; i++)
+	void restart(const EngineDev &d, int games, hipStream_t s)
 	{
-		const uint32_t mv = game->moves[i];
-		const int sg = mv & 3, r = (mv >> 2) & 127, c = (mv >> 9) & 127;
-		AGX_REQUIRE((sg == 1 || sg == 2) && r < e->dev.n && c < e->dev.n && !seen[r * e->dev.n + c], AGX_ERR_INVALID,
-				"agx_engine_restore_game: move %d (0x%x) is not a stone on an empty cell", i, mv);
-		seen[r * e->dev.n + c] = 1;
+		hipLaunchKernelGGL(k_restart, dim3(games), dim3(256), 0, s, d);
 	}
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	if (e->moves_staging == nullptr)
+	void cancel_pending(const EngineDev &d, int waves, hipStream_t s)
 	{
-		AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->moves_staging), MAXHW * sizeof(uint16_t)));
-		e->allocations.push_back(e->moves_staging);
+		hipLaunchKernelGGL(k_cancel_pending, dim3(waves), dim3(64), 0, s, d);
 	}
-	AGX_HIP_CHECK(hipStreamSynchronize(s)); // (the staging buffer of the previous call may still be read)
-	AGX_HIP_CHECK(hipMemcpy(e->moves_staging, game->moves, sizeof(uint16_t) * std::max(1, game->n_moves), hipMemcpyHostToDevice));
-	hipLaunchKernelGGL(k_restore_game, dim3(1), dim3(256), 0, s, e->dev, game->game_slot, e->moves_staging, game->n_moves, game->opening_id, game->nn_queued);
-	AGX_HIP_CHECK(hipGetLastError());
-	return AGX_OK;
-}
-int agx_engine_set_batch_size(AgxEngine *e, int batch_size)
-{ // Search::setBatchSize (Search.cpp:252-255): the task buffers keep their capacity (max_batch_size), the select stage fills `batch_size` of it
-	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_engine_set_batch_size: null engine");
-	AGX_REQUIRE(batch_size >= 1 && batch_size <= e->dev.batch, AGX_ERR_INVALID, "agx_engine_set_batch_size: %d outside [1, max_batch_size = %d]", batch_size, e->dev.batch);
-	e->dev.batch_limit = batch_size;
-	e->player[0].batch_limit = e->player[1].batch_limit = batch_size; // (a match pool: both players, as before; agx_engine_set_player_search sets one)
-	return AGX_OK;
-}
-int agx_engine_root_summary(AgxEngine *e, int game, void *stream, int *out4)
-{
-	AGX_REQUIRE(e != nullptr && out4 != nullptr, AGX_ERR_INVALID, "agx_engine_root_summary: null argument");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_root_summary: agx_engine_begin has not been called");
-	AGX_REQUIRE(game >= 0 && game < e->dev.n_games, AGX_ERR_INVALID, "agx_engine_root_summary: game %d of %d", game, e->dev.n_games);
-	if (e->summary_dev == nullptr)
+	void set_board(const EngineDev &d, int g, const uint8_t *board, int sign_to_move, int force_remove_root, hipStream_t s)
 	{
-		AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->summary_dev), 4 * sizeof(int)));
-		e->allocations.push_back(e->summary_dev);
-		AGX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e->summary_host), 4 * sizeof(int), hipHostMallocDefault));
+		hipLaunchKernelGGL(k_set_board, dim3(1), dim3(256), 0, s, d, g, board, sign_to_move, force_remove_root);
 	}
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	EngineDev d = e->dev;
-	{ // (k_root_summary reads the game's arenas through its own record)
-		hipLaunchKernelGGL(k_root_summary, dim3(1), dim3(1), 0, s, d, game, e->summary_dev);
-	}
-	AGX_HIP_CHECK(hipMemcpyAsync(e->summary_host, e->summary_dev, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-	AGX_HIP_CHECK(hipStreamSynchronize(s)); // THIS stream only: a network launch on another stream keeps running
-	std::memcpy(out4, e->summary_host, 4 * sizeof(int));
-	return AGX_OK;
-}
-namespace
-{
-	size_t align16(size_t bytes)
+	void restore_game(const EngineDev &d, int g, const uint16_t *moves, int count, int opening_id, int nn_queued, hipStream_t s)
 	{
-		return (bytes + 15) & ~static_cast<size_t>(15);
+		hipLaunchKernelGGL(k_restore_game, dim3(1), dim3(256), 0, s, d, g, moves, count, opening_id, nn_queued);
 	}
-	/* the query staging buffers hold at least `bytes` (device and pinned host, same size); their previous contents are not kept */
-	int query_reserve(AgxEngine *e, size_t bytes)
+	void root_summary(const EngineDev &d, int g, int *out, hipStream_t s)
 	{
-		if (bytes <= e->query_bytes)
-			return AGX_OK;
-		const size_t want = std::max(bytes, 2 * e->query_bytes);
-		if (e->query_dev != nullptr)
-		{
-			e->allocations.erase(std::find(e->allocations.begin(), e->allocations.end(), static_cast<void*>(e->query_dev)));
-			AGX_HIP_CHECK(hipFree(e->query_dev));
-			AGX_HIP_CHECK(hipHostFree(e->query_host));
-			e->query_dev = e->query_host = nullptr;
-			e->query_bytes = 0;
-		}
-		AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->query_dev), want));
-		e->allocations.push_back(e->query_dev);
-		AGX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e->query_host), want, hipHostMallocDefault));
-		e->query_bytes = want;
-		return AGX_OK;
+		hipLaunchKernelGGL(k_root_summary, dim3(1), dim3(1), 0, s, d, g, out);
 	}
-	/* the tree a query reads: the pool slot (match mode: that player's tree), game 0 of a tournament-search engine */
-	int query_tree(AgxEngine *e, int game, const char *who)
+	void node_info(const EngineDev &d, int n_paths, int tree, const uint16_t *moves, const int *offsets, AgxNodeView *out_nodes, AgxEdgeView *out_edges,
+			int edges_per_path, hipStream_t s)
 	{
-		AGX_REQUIRE(e->begun, AGX_ERR_STATE, "%s: agx_engine_begin has not been called", who);
-		AGX_REQUIRE(game >= 0 && game < e->dev.n_games, AGX_ERR_INVALID, "%s: game %d of %d", who, game, e->dev.n_games);
-		AGX_REQUIRE(!e->dev.shared_tree || game == 0, AGX_ERR_INVALID, "%s: a tournament-search engine has one tree, game 0 (records 1.. are its task buffers)", who);
-		return AGX_OK;
+		hipLaunchKernelGGL(k_node_info, dim3(n_paths), dim3(64), 0, s, d, tree, moves, offsets, out_nodes, out_edges, edges_per_path);
 	}
-	int query_moves_on_board(const AgxEngine *e, const uint16_t *moves, int count, const char *who)
+	void principal_variation(const EngineDev &d, int tree, const uint16_t *moves, int n_moves, int max_length, int *out_length, uint16_t *out_pv,
+			AgxEdgeView *out_edges, AgxNodeView *out_nodes, hipStream_t s)
 	{
-		for (int i = 0; i < count; i++)
-		{
-			const int r = (moves[i] >> 2) & 127, c = (moves[i] >> 9) & 127;
-			AGX_REQUIRE(r < e->dev.n && c < e->dev.n, AGX_ERR_INVALID, "%s: move %d (0x%x) is at row %d, column %d of a %dx%d board", who, i, moves[i], r, c, e->dev.n,
-					e->dev.n);
-		}
-		return AGX_OK;
+		hipLaunchKernelGGL(k_principal_variation, dim3(1), dim3(64), 0, s, d, tree, moves, n_moves, max_length, out_length, out_pv, out_edges, out_nodes);
 	}
-}
-int agx_engine_node_info(AgxEngine *e, int game, const uint16_t *h_moves, const int *h_path_offsets, int n_paths, AgxNodeView *h_nodes, AgxEdgeView *h_edges,
-		int edges_per_path, void *stream)
-{
-	AGX_REQUIRE(e != nullptr && h_path_offsets != nullptr && h_nodes != nullptr, AGX_ERR_INVALID, "agx_engine_node_info: null argument");
-	AGX_REQUIRE(n_paths >= 0 && edges_per_path >= 0, AGX_ERR_INVALID, "agx_engine_node_info: %d paths, %d edges per path", n_paths, edges_per_path);
-	AGX_REQUIRE(edges_per_path == 0 || h_edges != nullptr, AGX_ERR_INVALID, "agx_engine_node_info: h_edges is null but edges_per_path is %d", edges_per_path);
-	int status = query_tree(e, game, "agx_engine_node_info");
-	if (status != AGX_OK)
-		return status;
-	AGX_REQUIRE(h_path_offsets[0] == 0, AGX_ERR_INVALID, "agx_engine_node_info: the first path offset is %d, not 0", h_path_offsets[0]);
-	for (int i = 0; i < n_paths; i++)
-		AGX_REQUIRE(h_path_offsets[i + 1] >= h_path_offsets[i], AGX_ERR_INVALID, "agx_engine_node_info: path %d ends (%d) before it starts (%d)", i,
-				h_path_offsets[i + 1], h_path_offsets[i]);
-	const int n_moves = h_path_offsets[n_paths];
-	AGX_REQUIRE(n_moves == 0 || h_moves != nullptr, AGX_ERR_INVALID, "agx_engine_node_info: h_moves is null");
-	if ((status = query_moves_on_board(e, h_moves, n_moves, "agx_engine_node_info")) != AGX_OK)
-		return status;
-	if (n_paths == 0)
-		return AGX_OK;
-	// staging: [offsets | moves] in, [nodes | edges] out
-	const size_t off_bytes = align16(sizeof(int) * (n_paths + 1)), move_bytes = align16(sizeof(uint16_t) * std::max(1, n_moves));
-	const size_t node_bytes = align16(sizeof(AgxNodeView) * n_paths), edge_bytes = sizeof(AgxEdgeView) * static_cast<size_t>(n_paths) * edges_per_path;
-	const size_t in_bytes = off_bytes + move_bytes;
-	hipStream_t s = static_cast<hipStream_t>(stream); // (the staging buffers are free: every query waits for its own copy back before it returns)
-	if ((status = query_reserve(e, in_bytes + node_bytes + edge_bytes)) != AGX_OK)
-		return status;
-	std::memcpy(e->query_host, h_path_offsets, sizeof(int) * (n_paths + 1));
-	if (n_moves > 0)
-		std::memcpy(e->query_host + off_bytes, h_moves, sizeof(uint16_t) * n_moves);
-	AGX_HIP_CHECK(hipMemcpyAsync(e->query_dev, e->query_host, in_bytes, hipMemcpyHostToDevice, s));
-	const int *d_offsets = reinterpret_cast<const int*>(e->query_dev);
-	const uint16_t *d_moves = reinterpret_cast<const uint16_t*>(e->query_dev + off_bytes);
-	AgxNodeView *d_nodes = reinterpret_cast<AgxNodeView*>(e->query_dev + in_bytes);
-	AgxEdgeView *d_edges = reinterpret_cast<AgxEdgeView*>(e->query_dev + in_bytes + node_bytes);
-	const int tree = e->dev.shared_tree ? 0 : game;
-	hipLaunchKernelGGL(k_node_info, dim3(n_paths), dim3(64), 0, s, e->dev, tree, d_moves, d_offsets, d_nodes, d_edges, edges_per_path);
-	AGX_HIP_CHECK(hipGetLastError());
-	AGX_HIP_CHECK(hipMemcpyAsync(e->query_host + in_bytes, e->query_dev + in_bytes, node_bytes + edge_bytes, hipMemcpyDeviceToHost, s));
-	AGX_HIP_CHECK(hipStreamSynchronize(s)); // THIS stream only
-	std::memcpy(h_nodes, e->query_host + in_bytes, sizeof(AgxNodeView) * n_paths);
-	if (edge_bytes > 0)
-		std::memcpy(h_edges, e->query_host + in_bytes + node_bytes, edge_bytes);
-	return AGX_OK;
-}
-int agx_engine_principal_variation(AgxEngine *e, int game, const uint16_t *h_moves, int n_moves, int max_length, uint16_t *h_pv, AgxEdgeView *h_pv_edges,
-		AgxNodeView *h_pv_nodes, int *length, void *stream)
-{
-	AGX_REQUIRE(e != nullptr && length != nullptr && (h_pv != nullptr || max_length == 0), AGX_ERR_INVALID, "agx_engine_principal_variation: null argument");
-	AGX_REQUIRE(n_moves >= 0 && (n_moves == 0 || h_moves != nullptr), AGX_ERR_INVALID, "agx_engine_principal_variation: %d moves", n_moves);
-	AGX_REQUIRE(max_length >= 0, AGX_ERR_INVALID, "agx_engine_principal_variation: max_length %d", max_length);
-	int status = query_tree(e, game, "agx_engine_principal_variation");
-	if (status != AGX_OK)
-		return status;
-	if ((status = query_moves_on_board(e, h_moves, n_moves, "agx_engine_principal_variation")) != AGX_OK)
-		return status;
-	const int cap = std::min(max_length, e->dev.hw); // (a variation cannot be longer than the board has cells)
-	// staging: [moves] in, [length | nodes | edges | pv] out
-	const size_t in_bytes = align16(sizeof(uint16_t) * std::max(1, n_moves)), len_bytes = 16;
-	const size_t node_bytes = align16(sizeof(AgxNodeView) * (cap + 1)), edge_bytes = align16(sizeof(AgxEdgeView) * std::max(1, cap));
-	const size_t pv_bytes = sizeof(uint16_t) * std::max(1, cap), out_bytes = len_bytes + node_bytes + edge_bytes + pv_bytes;
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	if ((status = query_reserve(e, in_bytes + out_bytes)) != AGX_OK)
-		return status;
-	if (n_moves > 0)
-		std::memcpy(e->query_host, h_moves, sizeof(uint16_t) * n_moves);
-	AGX_HIP_CHECK(hipMemcpyAsync(e->query_dev, e->query_host, in_bytes, hipMemcpyHostToDevice, s));
-	uint8_t *out_dev = e->query_dev + in_bytes, *out_host = e->query_host + in_bytes;
-	const int tree = e->dev.shared_tree ? 0 : game;
-	hipLaunchKernelGGL(k_principal_variation, dim3(1), dim3(64), 0, s, e->dev, tree, reinterpret_cast<const uint16_t*>(e->query_dev), n_moves, cap,
-			reinterpret_cast<int*>(out_dev), reinterpret_cast<uint16_t*>(out_dev + len_bytes + node_bytes + edge_bytes),
-			reinterpret_cast<AgxEdgeView*>(out_dev + len_bytes + node_bytes), reinterpret_cast<AgxNodeView*>(out_dev + len_bytes));
-	AGX_HIP_CHECK(hipGetLastError());
-	AGX_HIP_CHECK(hipMemcpyAsync(out_host, out_dev, out_bytes, hipMemcpyDeviceToHost, s));
-	AGX_HIP_CHECK(hipStreamSynchronize(s)); // THIS stream only
-	int n = 0;
-	std::memcpy(&n, out_host, sizeof(int));
-	*length = n;
-	if (n > 0)
-		std::memcpy(h_pv, out_host + len_bytes + node_bytes + edge_bytes, sizeof(uint16_t) * n);
-	if (h_pv_edges != nullptr && n > 0)
-		std::memcpy(h_pv_edges, out_host + len_bytes + node_bytes, sizeof(AgxEdgeView) * n);
-	if (h_pv_nodes != nullptr)
-		std::memcpy(h_pv_nodes, out_host + len_bytes, sizeof(AgxNodeView) * (n + 1));
-	return AGX_OK;
-}
-int agx_engine_cancel_pending(AgxEngine *e, void *stream)
-{
-	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_engine_cancel_pending: null engine");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_cancel_pending: agx_engine_begin has not been called");
-	AGX_REQUIRE(!e->dev.match_mode, AGX_ERR_STATE, "agx_engine_cancel_pending: a match-mode engine plays its own games");
-	EngineDev d = e->dev;
-	d.g0 = 0;
-	hipLaunchKernelGGL(k_cancel_pending, dim3(d.shared_tree ? 1 : d.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), d);
-	AGX_HIP_CHECK(hipGetLastError());
-	return AGX_OK;
-}
-int agx_engine_set_force_expand_root(AgxEngine *e, int force_expand_root)
-{
-	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_engine_set_force_expand_root: null engine");
-	AGX_REQUIRE(!e->dev.match_mode, AGX_ERR_STATE, "agx_engine_set_force_expand_root: a match-mode engine always prunes the root");
-	e->dev.prune_root = force_expand_root ? 0 : 1;
-	e->cfg.force_expand_root = force_expand_root ? 1 : 0;
-	return AGX_OK;
-}
-int agx_engine_set_max_simulations(AgxEngine *e, int max_simulations)
-{
-	AGX_REQUIRE(e != nullptr && max_simulations > 0, AGX_ERR_INVALID, "agx_engine_set_max_simulations: invalid argument");
-	e->dev.max_sims = max_simulations;
-	e->cfg.max_simulations = max_simulations;
-	e->player[0].max_sims = e->player[1].max_sims = max_simulations; // (a match pool: both players, as before; agx_engine_set_player_search sets one)
-	return AGX_OK;
-}
-
-/* ---- match pools: search settings per player (evaluation/Player.cpp:64-81 takes them from the player's own SelfplayConfig) ---- */
-int agx_engine_player_search(AgxEngine *e, int player, AgxPlayerSearch *out)
-{
-	AGX_REQUIRE(e != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_engine_player_search: null argument");
-	AGX_REQUIRE(e->dev.match_mode, AGX_ERR_STATE, "agx_engine_player_search: the engine was not created with match_mode");
-	AGX_REQUIRE(player == 0 || player == 1, AGX_ERR_INVALID, "agx_engine_player_search: player must be 0 (first) or 1 (second), not %d", player);
-	const PlayerSearchDev &p = e->player[player];
-	out->max_simulations = p.max_sims;
-	out->max_batch_size = p.batch_limit;
-	out->exploration_constant = p.c_puct;
-	out->exploration_scaling = p.c_scale;
-	out->init_to = p.init_to;
-	out->information_leak_threshold = p.leak_threshold;
-	out->max_children = (p.max_children == 0x7FFFFFFF) ? 0 : p.max_children;
-	out->policy_expansion_threshold = p.expansion_threshold;
-	out->policy_temperature = p.policy_temperature;
-	out->tss_max_positions = p.tss_max_nodes;
-	out->final_selector = p.final_selector;
-	out->action_values = p.has_q;
-	return AGX_OK;
-}
-int agx_engine_set_player_search(AgxEngine *e, int player, const AgxPlayerSearch *in)
-{
-	AGX_REQUIRE(e != nullptr && in != nullptr, AGX_ERR_INVALID, "agx_engine_set_player_search: null argument");
-	AGX_REQUIRE(e->dev.match_mode, AGX_ERR_STATE, "agx_engine_set_player_search: the engine was not created with match_mode");
-	AGX_REQUIRE(player == 0 || player == 1, AGX_ERR_INVALID, "agx_engine_set_player_search: player must be 0 (first) or 1 (second), not %d", player);
-	// (max_simulations below 50: the move rule's threshold can exceed what select ever reaches, AgxEngineConfig.max_simulations.  The pool-wide
-	// agx_engine_set_max_simulations keeps accepting any positive value, as before; a player left below 50 by it has to be given a
-	// max_simulations >= 50 along with whatever else this call changes)
-	AGX_REQUIRE(in->max_simulations >= 50, AGX_ERR_INVALID, "agx_engine_set_player_search: max_simulations must be at least 50, not %d", in->max_simulations);
-	AGX_REQUIRE(in->max_batch_size >= 1 && in->max_batch_size <= e->dev.batch, AGX_ERR_INVALID, "agx_engine_set_player_search: max_batch_size %d outside [1, max_batch_size = %d]",
-			in->max_batch_size, e->dev.batch);
-	AGX_REQUIRE(in->init_to >= 0 && in->init_to <= 3, AGX_ERR_INVALID, "agx_engine_set_player_search: init_to must be 0..3");
-	AGX_REQUIRE(in->tss_max_positions >= 1 && in->tss_max_positions <= e->dev.tss_max_nodes, AGX_ERR_INVALID,
-			"agx_engine_set_player_search: tss_max_positions must be in [1, %d] (the pool's)", e->dev.tss_max_nodes);
-	AGX_REQUIRE(in->final_selector >= 0 && in->final_selector <= 5, AGX_ERR_INVALID, "agx_engine_set_player_search: final_selector must be 0..5");
-	AGX_REQUIRE(in->policy_temperature >= 0.0f, AGX_ERR_INVALID, "agx_engine_set_player_search: policy_temperature must not be negative");
-	AGX_REQUIRE(in->action_values == 0 || in->action_values == 1, AGX_ERR_INVALID, "agx_engine_set_player_search: action_values must be 0 or 1");
-	AGX_REQUIRE(in->action_values == 0 || e->dev.has_q, AGX_ERR_INVALID,
-			"agx_engine_set_player_search: action_values = 1 needs a pool created with action_values = 1 (it has no action-values exchange buffer)");
-	PlayerSearchDev &p = e->player[player];
-	p.max_sims = in->max_simulations;
-	p.batch_limit = in->max_batch_size;
-	p.c_puct = in->exploration_constant;
-	p.c_scale = in->exploration_scaling;
-	p.init_to = in->init_to;
-	p.leak_threshold = in->information_leak_threshold;
-	p.max_children = (in->max_children > 0) ? in->max_children : 0x7FFFFFFF;
-	p.expansion_threshold = in->policy_expansion_threshold;
-	p.policy_temperature = in->policy_temperature;
-	p.tss_max_nodes = in->tss_max_positions;
-	p.final_selector = in->final_selector;
-	p.has_q = in->action_values;
-	return AGX_OK;
-}
-int agx_engine_match_summary(AgxEngine *e, long long out[4], void *stream)
-{
-	AGX_REQUIRE(e != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_engine_match_summary: null argument");
-	AGX_REQUIRE(e->dev.match_mode, AGX_ERR_STATE, "agx_engine_match_summary: the engine was not created with match_mode");
-	AGX_REQUIRE(e->begun, AGX_ERR_STATE, "agx_engine_match_summary: agx_engine_begin has not been called");
-	if (e->match_sum_dev == nullptr)
+	void match_summary(const EngineDev &d, long long *out, hipStream_t s)
 	{
-		AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->match_sum_dev), 4 * sizeof(long long)));
-		e->allocations.push_back(e->match_sum_dev);
+		hipLaunchKernelGGL(k_match_summary, dim3(1), dim3(256), 0, s, d, out);
 	}
-	if (e->match_sum_host == nullptr) // (on its own: a call whose second allocation failed must not leave the next one a null pointer)
-		AGX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e->match_sum_host), 4 * sizeof(long long), hipHostMallocDefault));
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	hipLaunchKernelGGL(k_match_summary, dim3(1), dim3(256), 0, s, e->dev, e->match_sum_dev);
-	AGX_HIP_CHECK(hipGetLastError());
-	AGX_HIP_CHECK(hipMemcpyAsync(e->match_sum_host, e->match_sum_dev, 4 * sizeof(long long), hipMemcpyDeviceToHost, s));
-	AGX_HIP_CHECK(hipStreamSynchronize(s));
-	std::memcpy(out, e->match_sum_host, 4 * sizeof(long long));
-	return AGX_OK;
-}
-int agx_engine_speculative_waves(AgxEngine *e, int *waves)
-{
-	AGX_REQUIRE(e != nullptr && waves != nullptr, AGX_ERR_INVALID, "agx_engine_speculative_waves: null argument");
-	*waves = e->speculative ? e->spec_waves : 0;
-	return AGX_OK;
-}
-int agx_engine_device_bytes(AgxEngine *e, unsigned long long *bytes)
-{
-	AGX_REQUIRE(e != nullptr && bytes != nullptr, AGX_ERR_INVALID, "agx_engine_device_bytes: null argument");
-	*bytes = e->device_bytes;
-	return AGX_OK;
-}
-int agx_engine_stats(AgxEngine *e, AgxEngineStats *out)
-{
-	AGX_REQUIRE(e != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_engine_stats: null argument");
-	std::vector<GameState> games(e->dev.n_games);
-	AGX_HIP_CHECK(hipMemcpy(games.data(), e->dev.games, games.size() * sizeof(GameState), hipMemcpyDeviceToHost));
-	int counters[16];
-	AGX_HIP_CHECK(hipMemcpy(counters, e->dev.counters, sizeof(counters), hipMemcpyDeviceToHost));
-	std::memset(out, 0, sizeof(*out));
-	for (const GameState &g : games)
+	void debug_load_tasks(const EngineDev &d, const uint8_t *boards, const int *signs, int count, hipStream_t s)
 	{
-		out->evaluated_nodes += g.stats[0];
-		out->network_evaluations += g.stats[1];
-		out->information_leaks += g.stats[2];
-		out->proven_edge_visits += g.stats[3];
-		out->wasted_expansions += g.stats[4];
-		out->solver_nodes += g.stats[5];
-		out->select_levels += g.stats[6];
-		out->select_edge_reads += g.stats[7];
-		out->moves_played += g.stats[8];
-		out->duplicate_selections += g.stats[9];
-		out->speculative_solves += g.spec_stats[0];
-		out->speculative_reruns += g.spec_stats[1];
-		out->speculative_deferrals += g.spec_stats[2];
-		out->speculative_parks += static_cast<int>(g.spec_stats[3]);
-		out->peak_nodes = std::max<unsigned long long>(out->peak_nodes, g.stats[10]);
-		out->peak_edges = std::max<unsigned long long>(out->peak_edges, g.stats[11]);
-		out->active_games += g.active ? 1 : 0;
-		if (g.error != 0 && out->first_error == 0)
-			out->first_error = g.error;
+		hipLaunchKernelGGL(k_debug_load_tasks, dim3(count), dim3(64), 0, s, d, boards, signs, count);
 	}
-	if (e->speculative)
+	void debug_pattern_state(const EngineDev &d, int count, const uint8_t *boards, const int *signs, const uint16_t *moves, int n_moves, uint8_t *ptypes,
+			uint8_t *threats, int16_t *lists, int lists_stride, hipStream_t s)
 	{
-		int w[16];
-		AGX_HIP_CHECK(hipMemcpy(w, e->dev.spec_watchdog, sizeof(w), hipMemcpyDeviceToHost));
-		if (w[0] != 0)
-			fprintf(stderr, "[k_search_spec watchdog] a wave waited in vain for queue slot %d: head %d, tail %d, games selected %d of %d, select cursor %d\n", w[1], w[2], w[3], w[4],
-					w[5], w[6]);
+		hipLaunchKernelGGL(k_debug_pattern_state, dim3(count), dim3(64), 0, s, d, boards, signs, moves, n_moves, ptypes, threats, lists, lists_stride);
 	}
-#ifdef AGX_SPEC_PROFILE
-	if (getenv("AGX_SPEC_TRACE"))
-	{ // per game of the LAST launch: select done, commit begin, commit end (100 MHz ticks), re-runs * 16 + leaves
-		std::vector<unsigned long long> tr(4 * games.size());
-		AGX_HIP_CHECK(hipMemcpy(tr.data(), e->dev.spec_trace, tr.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-		FILE *f = fopen(getenv("AGX_SPEC_TRACE"), "w");
-		if (f != nullptr)
-		{
-			for (size_t g = 0; g < games.size(); g++)
-				fprintf(f, "%llu %llu %llu %llu\n", tr[4 * g], tr[4 * g + 1], tr[4 * g + 2], tr[4 * g + 3]);
-			fclose(f);
-		}
-		// per wave of the last launches (one per group): select phase over, exit, leaves solved, ticks waited for items
-		std::vector<unsigned long long> wv(4 * static_cast<size_t>(std::max(e->spec_waves, 16)));
-		AGX_HIP_CHECK(hipMemcpy(wv.data(), e->dev.spec_trace + 4 * games.size(), wv.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-		f = fopen((std::string(getenv("AGX_SPEC_TRACE")) + ".waves").c_str(), "w");
-		if (f != nullptr)
-		{
-			for (size_t w = 0; 4 * w < wv.size(); w++)
-				fprintf(f, "%llu %llu %llu %llu\n", wv[4 * w], wv[4 * w + 1], wv[4 * w + 2], wv[4 * w + 3]);
-			fclose(f);
-		}
-	}
+	void solve_positions(const EngineDev &d, int waves, const SolvePositionsArgs &args, hipStream_t s)
 	{
-		unsigned long long p[16];
-		AGX_HIP_CHECK(hipMemcpy(p, e->dev.spec_prof, sizeof(p), hipMemcpyDeviceToHost));
-		fprintf(stderr, "[k_search_spec profile, wave-ms summed] select phase %.1f (slowest wave, max over launches %.3f ms), waiting for items %.1f, speculative solves %.1f (%llu, %.1f us each), "
-				"commits + re-runs %.1f (longest %.3f ms), longest launch %.3f ms\n", p[0] / 1e5, p[1] / 1e5, p[2] / 1e5, p[3] / 1e5, p[6], p[3] / 1e2 / (p[6] ? p[6] : 1), p[4] / 1e5, p[5] / 1e5,
-				p[7] / 1e5);
+		const dim3 grid(waves), block(64);
+#define AGX_USE(RENJU, NFIX) hipLaunchKernelGGL((k_solve_positions<RENJU, NFIX>), grid, block, 0, s, d, args)
+		AGX_FOR_SHAPE(d.rules, d.n, AGX_USE);
+#undef AGX_USE
 	}
-#endif
-#ifdef AGX_SOLVER_PROFILE
+	void positions_reset(const PositionJob &job, hipStream_t s)
 	{
-		unsigned long long p[10] = { 0 };
-		for (const GameState &g : games)
-		{
-			for (int i = 0; i < 6; i++)
-				p[i] += g.prof[i];
-			p[6] += g.prof[6] & 0xFFFFFFFFull;
-			p[7] += g.prof[6] >> 32;
-			p[8] += g.prof[7] & 0xFFFFFFFFull;
-			p[9] += g.prof[7] >> 32;
-		}
-		fprintf(stderr, "[solver profile, 100 MHz ticks] solves %llu: set_board+encode %.1f us, frame machine %.1f us, place/remove %.1f us (%.1f per solve, %.2f us each), total %.1f us per solve\n",
-				p[5], p[0] / 100.0 / p[5], p[1] / 100.0 / p[5], p[2] / 100.0 / p[5], (double) p[3] / p[5], p[2] / 100.0 / (p[3] ? p[3] : 1), p[4] / 100.0 / p[5]);
-		fprintf(stderr, "[frame machine split, us per solve] table seek %.1f, move generation %.1f, ordering %.1f, evaluate+insert %.1f\n",
-				p[6] / 100.0 / p[5], p[7] / 100.0 / p[5], p[8] / 100.0 / p[5], p[9] / 100.0 / p[5]);
-		unsigned long long dp[24] = { 0 };
-		for (const GameState &g : games)
-			for (int i = 0; i < 24; i++)
-				dp[i] += g.dprof[i];
-		const double solves = static_cast<double>(p[5]);
-		fprintf(stderr, "[generate(), shader cycles per solve; %.1f calls] win1 %.0f, loss2 %.0f, win3 %.0f, loss4 %.0f, win5 %.0f, loss6 %.0f, half4 %.0f, rest %.0f\n",
-				dp[8] / solves, dp[0] / solves, dp[1] / solves, dp[2] / solves, dp[3] / solves, dp[4] / solves, dp[5] / solves, dp[6] / solves, dp[7] / solves);
-		fprintf(stderr, "[frame machine, shader cycles per solve; %.1f loop turns, %.1f picks] resume %.0f, pick %.0f, descend %.0f, child-returned %.0f\n",
-				dp[21] / solves, dp[22] / solves, dp[15] / solves, dp[16] / solves, dp[17] / solves, dp[20] / solves);
-		fprintf(stderr, "[update_around, shader cycles per solve; %.1f calls, %.2f list changes per call] centre %.0f, gather %.0f, lists %.0f\n",
-				dp[14] / solves, dp[13] / (dp[14] ? static_cast<double>(dp[14]) : 1.0), dp[10] / solves, dp[11] / solves, dp[12] / solves);
-		fprintf(stderr, "[renju, per solve] forbidden bits of the network input %.1f us, mark_forbidden_moves %.0f shader cycles, generator foul tests %.0f shader cycles (%.2f tests)\n",
-				dp[23] / 100.0 / solves, dp[9] / solves, dp[18] / solves, dp[19] / solves);
+		hipLaunchKernelGGL(k_positions_reset, dim3(1), dim3(1), 0, s, job);
 	}
-#endif
+	void load_positions(const EngineDev &d, int slots, const PositionJob &job, hipStream_t s)
 	{
-		ArenaHeap heap;
-		AGX_HIP_CHECK(hipMemcpy(&heap, e->dev.heap, sizeof(heap), hipMemcpyDeviceToHost));
-		out->arena_grows = heap.grows;
-		out->arena_releases = heap.releases;
-		out->arena_failures = heap.failures;
-		for (const GameState &g : games)
-			out->arena_max_class = std::max(out->arena_max_class, g.arena_class);
-		out->arena_heap_used = static_cast<float>(static_cast<double>(heap.edge_cursor) / static_cast<double>(heap.edge_total));
+		hipLaunchKernelGGL(k_load_positions, dim3(slots), dim3(256), 0, s, d, job);
 	}
-	out->games_finished = counters[2];
-	out->openings_taken = counters[1];
-	out->records_used = counters[3];
-	out->record_edges_used = counters[4];
-	return AGX_OK;
-}
-
-int agx_engine_game_info(AgxEngine *e, int game, AgxGameInfo *info, uint8_t *h_board, AgxEdgeView *h_root_edges, int edge_capacity)
-{
-	AGX_REQUIRE(e != nullptr && info != nullptr, AGX_ERR_INVALID, "agx_engine_game_info: null argument");
-	AGX_REQUIRE(game >= 0 && game < e->dev.n_games, AGX_ERR_INVALID, "agx_engine_game_info: game %d out of range", game);
-	AGX_HIP_CHECK(hipDeviceSynchronize());
-	GameState gs;
-	AGX_HIP_CHECK(hipMemcpy(&gs, e->dev.games + game, sizeof(GameState), hipMemcpyDeviceToHost));
-	info->active = gs.active;
-	info->sign_to_move = gs.sign_to_move;
-	info->n_moves = gs.n_moves;
-	info->outcome = gs.outcome;
-	info->error = gs.error;
-	info->opening_id = gs.opening_id;
-	info->games_done = gs.games_done;
-	info->n_nodes = gs.n_nodes;
-	info->n_edges = gs.n_edges;
-	info->grow_pending = gs.grow_pending;
-	info->arena_class = gs.arena_class;
-	info->root_visits = 0;
-	info->root_win = info->root_draw = 0.0f;
-	info->root_score = 0;
-	info->root_edges = 0;
-	info->root_moves_left = 0.0f;
-	info->max_depth = gs.max_depth;
-	if (h_board != nullptr)
-		std::memcpy(h_board, gs.board, e->dev.hw);
-	if (gs.root >= 0)
+	void harvest_positions(const EngineDev &d, int slots, const PositionJob &job, hipStream_t s)
 	{
-		DNode root;
-		const DNode *nodes = e->dev.nodes + gs.node_off[gs.arena];
-		AGX_HIP_CHECK(hipMemcpy(&root, nodes + gs.root, sizeof(DNode), hipMemcpyDeviceToHost));
-		info->root_visits = root.visits;
-		info->root_win = root.win;
-		info->root_draw = root.draw;
-		info->root_score = root.score;
-		info->root_edges = root.n_edges;
-		info->root_moves_left = root.moves_left;
-		if (h_root_edges != nullptr)
-		{
-			AGX_REQUIRE(root.n_edges <= edge_capacity, AGX_ERR_INVALID, "agx_engine_game_info: %d root edges do not fit into %d", root.n_edges, edge_capacity);
-			std::vector<DEdge> edges(root.n_edges);
-			const DEdge *pool = e->dev.edges + gs.edge_off[gs.arena];
-			AGX_HIP_CHECK(hipMemcpy(edges.data(), pool + root.edge_begin, edges.size() * sizeof(DEdge), hipMemcpyDeviceToHost));
-			for (int i = 0; i < root.n_edges; i++)
-			{
-				h_root_edges[i].prior = edges[i].prior;
-				h_root_edges[i].win = edges[i].win;
-				h_root_edges[i].draw = edges[i].draw;
-				h_root_edges[i].visits = edges[i].visits;
-				h_root_edges[i].move = edges[i].move;
-				h_root_edges[i].score = edges[i].score;
-				h_root_edges[i].flag_and_virtual_loss = edges[i].flag_vl;
-			}
-		}
+		hipLaunchKernelGGL(k_harvest_positions, dim3(slots), dim3(64), 0, s, d, job);
 	}
-	return AGX_OK;
-}
-
-int agx_engine_fetch_records(AgxEngine *e, AgxMoveRecord *h_records, int record_capacity, AgxEdgeView *h_edges, int edge_capacity, uint8_t *h_samples,
-		int sample_capacity, AgxGameEnd *h_game_ends, int game_end_capacity, AgxRecordCounts *counts, int drain)
-{
-	AGX_REQUIRE(e != nullptr && counts != nullptr, AGX_ERR_INVALID, "agx_engine_fetch_records: null argument");
-	AGX_HIP_CHECK(hipDeviceSynchronize());
-	int counters[16];
-	AGX_HIP_CHECK(hipMemcpy(counters, e->dev.counters, sizeof(counters), hipMemcpyDeviceToHost));
-	const int nr = std::min(counters[3], e->dev.record_cap), ne = (e->dev.record_format & 1) ? std::min(counters[4], e->dev.record_edge_cap) : 0;
-	const int ns = (e->dev.record_format & 2) ? std::min(counters[6], e->dev.sample_cap) : 0, ng = std::min(counters[7], e->dev.game_end_cap);
-	counts->records = nr;
-	counts->edges = ne;
-	counts->sample_bytes = ns;
-	counts->game_ends = ng;
-	if (h_records != nullptr)
+	void positions_init(const EngineDev &d, int slots, const PositionJob &job, hipStream_t s)
 	{
-		AGX_REQUIRE(nr <= record_capacity, AGX_ERR_INVALID, "agx_engine_fetch_records: %d records do not fit into %d", nr, record_capacity);
-		std::vector<MoveRecordHeader> headers(nr);
-		AGX_HIP_CHECK(hipMemcpy(headers.data(), e->dev.records, headers.size() * sizeof(MoveRecordHeader), hipMemcpyDeviceToHost));
-		for (int i = 0; i < nr; i++)
-		{
-			h_records[i].game_serial = headers[i].game_serial;
-			h_records[i].move_number = headers[i].move_number;
-			h_records[i].move = headers[i].move;
-			h_records[i].root_score = headers[i].root_score;
-			h_records[i].root_visits = headers[i].root_visits;
-			h_records[i].root_win = headers[i].root_win;
-			h_records[i].root_draw = headers[i].root_draw;
-			h_records[i].root_flags = headers[i].root_flags;
-			h_records[i].n_edges = headers[i].n_edges;
-			h_records[i].edge_offset = headers[i].edge_offset;
-			h_records[i].game_slot = headers[i].game_slot;
-			h_records[i].game_index = headers[i].game_index;
-			h_records[i].sample_offset = headers[i].sample_offset;
-			h_records[i].sample_bytes = headers[i].sample_bytes;
-			h_records[i].outcome = headers[i].outcome;
-		}
-	}
-	if (h_edges != nullptr && ne > 0)
-	{
-		AGX_REQUIRE(ne <= edge_capacity, AGX_ERR_INVALID, "agx_engine_fetch_records: %d edges do not fit into %d", ne, edge_capacity);
-		std::vector<DEdge> edges(ne);
-		AGX_HIP_CHECK(hipMemcpy(edges.data(), e->dev.record_edges, edges.size() * sizeof(DEdge), hipMemcpyDeviceToHost));
-		for (int i = 0; i < ne; i++)
-		{
-			h_edges[i].prior = edges[i].prior;
-			h_edges[i].win = edges[i].win;
-			h_edges[i].draw = edges[i].draw;
-			h_edges[i].visits = edges[i].visits;
-			h_edges[i].move = edges[i].move;
-			h_edges[i].score = edges[i].score;
-			h_edges[i].flag_and_virtual_loss = edges[i].flag_vl;
-			h_edges[i].reserved = 0;
-		}
-	}
-	if (h_samples != nullptr && ns > 0)
-	{
-		AGX_REQUIRE(ns <= sample_capacity, AGX_ERR_INVALID, "agx_engine_fetch_records: %d sample bytes do not fit into %d", ns, sample_capacity);
-		AGX_HIP_CHECK(hipMemcpy(h_samples, e->dev.samples, static_cast<size_t>(ns), hipMemcpyDeviceToHost));
-	}
-	if (h_game_ends != nullptr && ng > 0)
-	{
-		AGX_REQUIRE(ng <= game_end_capacity, AGX_ERR_INVALID, "agx_engine_fetch_records: %d finished games do not fit into %d", ng, game_end_capacity);
-		std::vector<GameEndRecord> ends(ng);
-		AGX_HIP_CHECK(hipMemcpy(ends.data(), e->dev.game_ends, ends.size() * sizeof(GameEndRecord), hipMemcpyDeviceToHost));
-		for (int i = 0; i < ng; i++)
-		{
-			h_game_ends[i].game_serial = ends[i].game_serial;
-			h_game_ends[i].game_slot = ends[i].game_slot;
-			h_game_ends[i].game_index = ends[i].game_index;
-			h_game_ends[i].outcome = ends[i].outcome;
-			h_game_ends[i].n_moves = ends[i].n_moves;
-			std::memcpy(h_game_ends[i].moves, ends[i].moves, sizeof(ends[i].moves));
-		}
-	}
-	if (drain)
-	{ // the device is synchronised: the pools start empty again (game serials / indices keep counting)
-		AGX_HIP_CHECK(hipMemset(e->dev.counters + 3, 0, 2 * sizeof(int)));
-		AGX_HIP_CHECK(hipMemset(e->dev.counters + 6, 0, 2 * sizeof(int)));
-	}
-	return AGX_OK;
-}
-
-int agx_engine_records(AgxEngine *e, AgxMoveRecord *h_records, int record_capacity, AgxEdgeView *h_edges, int edge_capacity, int *n_records, int *n_edges)
-{
-	AGX_REQUIRE(e != nullptr && n_records != nullptr && n_edges != nullptr, AGX_ERR_INVALID, "agx_engine_records: null argument");
-	AgxRecordCounts counts;
-	const bool sizes_only = (h_records == nullptr || h_edges == nullptr);
-	const int st = agx_engine_fetch_records(e, sizes_only ? nullptr : h_records, record_capacity, sizes_only ? nullptr : h_edges, edge_capacity, nullptr, 0, nullptr, 0,
-			&counts, 0);
-	if (st != AGX_OK)
-		return st;
-	*n_records = counts.records;
-	*n_edges = counts.edges;
-	return AGX_OK;
-}
-
-int agx_engine_drain_records(AgxEngine *e, AgxMoveRecord *h_records, int record_capacity, AgxEdgeView *h_edges, int edge_capacity, int *n_records, int *n_edges)
-{
-	AGX_REQUIRE(h_records != nullptr && h_edges != nullptr && n_records != nullptr && n_edges != nullptr, AGX_ERR_INVALID,
-			"agx_engine_drain_records: null buffer (query the sizes with agx_engine_records)");
-	AgxRecordCounts counts;
-	const int st = agx_engine_fetch_records(e, h_records, record_capacity, h_edges, edge_capacity, nullptr, 0, nullptr, 0, &counts, 1);
-	if (st != AGX_OK)
-		return st;
-	*n_records = counts.records;
-	*n_edges = counts.edges;
-	return AGX_OK;
-}
-
-int agx_engine_zobrist(AgxEngine *e, uint64_t *h_keys, size_t n_words)
-{
-	AGX_REQUIRE(e != nullptr && h_keys != nullptr, AGX_ERR_INVALID, "agx_engine_zobrist: null argument");
-	AGX_REQUIRE(n_words == e->zobrist.size(), AGX_ERR_INVALID, "agx_engine_zobrist: expected %zu words", e->zobrist.size());
-	std::memcpy(h_keys, e->zobrist.data(), n_words * sizeof(uint64_t));
-	return AGX_OK;
-}
-
-int agx_stream_create(void **out)
-{
-	AGX_REQUIRE(out != nullptr, AGX_ERR_INVALID, "agx_stream_create: null argument");
-	hipStream_t s = nullptr;
-	AGX_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-	*out = s;
-	return AGX_OK;
-}
-/* a stream whose kernels run only on the compute units whose bits are set in `mask` (bit i of word i / 32 = CU i): slices of a pool
- * that own disjoint parts of the chip */
-namespace
-{
-	/* hipStreamDestroy of a CU-masked stream hangs on ROCm 7.2, so such a stream lives until the process exits — and therefore must not be
-	 * created twice: the streams are cached process-wide by (device, mask).  A generator thread that sets its slices up again for every
-	 * training iteration (GeneratorManager::generate, once per iteration in the reference) gets the same streams back instead of leaking a
-	 * hardware queue per slice and iteration. */
-	struct MaskedStream
-	{
-			int device, instance;
-			std::vector<uint32_t> mask;
-			hipStream_t stream;
-	};
-	std::mutex g_masked_streams_mutex;
-	std::vector<MaskedStream> g_masked_streams;
-}
-int agx_stream_create_with_cu_mask(void **out, const uint32_t *mask, int words)
-{
-	return agx_stream_create_with_cu_mask_instance(out, mask, words, 0);
-}
-int agx_stream_create_with_cu_mask_instance(void **out, const uint32_t *mask, int words, int instance)
-{
-	AGX_REQUIRE(out != nullptr && mask != nullptr && words > 0, AGX_ERR_INVALID, "agx_stream_create_with_cu_mask: invalid argument");
-	bool any = false;
-	for (int i = 0; i < words; i++)
-		any = any || mask[i] != 0u;
-	AGX_REQUIRE(any, AGX_ERR_INVALID, "agx_stream_create_with_cu_mask: the mask selects no compute unit");
-	int device = 0;
-	AGX_HIP_CHECK(hipGetDevice(&device));
-	std::vector<uint32_t> key(mask, mask + words);
-	while (key.size() > 1 && key.back() == 0u)
-		key.pop_back(); // (trailing zero words select nothing: the same mask)
-	std::lock_guard<std::mutex> lock(g_masked_streams_mutex);
-	for (const MaskedStream &m : g_masked_streams)
-		if (m.device == device && m.instance == instance && m.mask == key)
-		{
-			*out = m.stream;
-			return AGX_OK;
-		}
-	hipStream_t s = nullptr;
-	AGX_HIP_CHECK(hipExtStreamCreateWithCUMask(&s, static_cast<uint32_t>(words), mask));
-	g_masked_streams.push_back(MaskedStream { device, instance, key, s });
-	*out = s;
-	return AGX_OK;
-}
-int agx_stream_masked_count(void)
-{
-	std::lock_guard<std::mutex> lock(g_masked_streams_mutex);
-	return static_cast<int>(g_masked_streams.size());
-}
-int agx_stream_destroy(void *stream)
-{
-	if (stream == nullptr)
-		return AGX_OK;
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	bool masked = false;
-	{
-		std::lock_guard<std::mutex> lock(g_masked_streams_mutex);
-		for (const MaskedStream &m : g_masked_streams)
-			masked = masked || (m.stream == s);
-	}
-	if (masked)
-	{ // drained (outside the lock), not destroyed: it stays in the cache for the next caller
-		AGX_HIP_CHECK(hipStreamSynchronize(s));
-		return AGX_OK;
-	}
-	AGX_HIP_CHECK(hipStreamDestroy(s));
-	return AGX_OK;
-}
-/* events: ordering between streams without the host (a slice's tower launch on the network partition waits for its search launch on the
- * search partition and the other way round) */
-int agx_event_create(void **out)
-{
-	AGX_REQUIRE(out != nullptr, AGX_ERR_INVALID, "agx_event_create: null argument");
-	hipEvent_t ev = nullptr;
-	AGX_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-	*out = ev;
-	return AGX_OK;
-}
-int agx_event_create_blocking(void **out)
-{ // for agx_event_synchronize: the waiting host thread sleeps (hipEventBlockingSync) instead of spinning
-	AGX_REQUIRE(out != nullptr, AGX_ERR_INVALID, "agx_event_create_blocking: null argument");
-	hipEvent_t ev = nullptr;
-	AGX_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventBlockingSync | hipEventDisableTiming));
-	*out = ev;
-	return AGX_OK;
-}
-int agx_event_synchronize(void *event)
-{ // a SLEEPING wait: hipEventSynchronize spins in user space on this runtime even for a hipEventBlockingSync event (measured: the waiting
-  // thread stays at 100 %), so the event is polled between 100 us naps — the callers wait for work that was queued steps ago
-	AGX_REQUIRE(event != nullptr, AGX_ERR_INVALID, "agx_event_synchronize: null event");
-	while (true)
-	{
-		const hipError_t st = hipEventQuery(static_cast<hipEvent_t>(event));
-		if (st == hipSuccess)
-			return AGX_OK;
-		if (st != hipErrorNotReady)
-			AGX_HIP_CHECK(st);
-		std::this_thread::sleep_for(std::chrono::microseconds(100));
+		hipLaunchKernelGGL(k_positions_init, dim3(slots), dim3(64), 0, s, d, job);
 	}
 }
-int agx_event_record(void *event, void *stream)
-{
-	AGX_REQUIRE(event != nullptr, AGX_ERR_INVALID, "agx_event_record: null event");
-	AGX_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(event), static_cast<hipStream_t>(stream)));
-	return AGX_OK;
-}
-int agx_stream_wait_event(void *stream, void *event)
-{
-	AGX_REQUIRE(event != nullptr, AGX_ERR_INVALID, "agx_stream_wait_event: null event");
-	AGX_HIP_CHECK(hipStreamWaitEvent(static_cast<hipStream_t>(stream), static_cast<hipEvent_t>(event), 0));
-	return AGX_OK;
-}
-int agx_event_destroy(void *event)
-{
-	if (event != nullptr)
-		AGX_HIP_CHECK(hipEventDestroy(static_cast<hipEvent_t>(event)));
-	return AGX_OK;
-}
-int agx_stream_synchronize(void *stream)
-{
-	AGX_HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-	return AGX_OK;
-}
-
-/* ---- test hooks: single stages on caller-supplied positions ---- */
-int agx_engine_kernel_timing(AgxEngine *e, int enable, double *ms_out, long long *launches_out)
-{
-	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_engine_kernel_timing: null engine");
-	AGX_HIP_CHECK(hipDeviceSynchronize());
-	double ms[4] = { 0.0, 0.0, 0.0, 0.0 };
-	long long launches[4] = { 0, 0, 0, 0 };
-	for (size_t i = 0; i < e->event_kernel.size(); i++)
-	{
-		float t = 0.0f;
-		AGX_HIP_CHECK(hipEventElapsedTime(&t, e->events[2 * i], e->events[2 * i + 1]));
-		ms[e->event_kernel[i]] += t;
-		launches[e->event_kernel[i]]++;
-		e->free_events.push_back(e->events[2 * i]);
-		e->free_events.push_back(e->events[2 * i + 1]);
-	}
-	e->events.clear();
-	e->event_kernel.clear();
-	for (int k = 0; k < 4; k++)
-	{
-		if (ms_out != nullptr)
-			ms_out[k] = ms[k];
-		if (launches_out != nullptr)
-			launches_out[k] = launches[k];
-	}
-	e->timing = (enable != 0);
-	return AGX_OK;
-}
-
-int agx_debug_solve(AgxEngine *e, const uint8_t *h_boards, const int *h_signs, int count, uint32_t *h_features, uint16_t *h_moves, uint16_t *h_scores,
-		int *h_counts, uint32_t *h_flags, uint16_t *h_result_scores)
-{
-	AGX_REQUIRE(e != nullptr && h_boards != nullptr && h_signs != nullptr, AGX_ERR_INVALID, "agx_debug_solve: null argument");
-	AGX_REQUIRE(count > 0 && count <= e->dev.n_games, AGX_ERR_INVALID, "agx_debug_solve: count must be in [1, n_games]");
-	const EngineDev &d = e->dev;
-	uint8_t *d_boards = nullptr;
-	int *d_signs = nullptr;
-	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_boards), static_cast<size_t>(count) * d.hw));
-	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_signs), count * sizeof(int)));
-	AGX_HIP_CHECK(hipMemcpy(d_boards, h_boards, static_cast<size_t>(count) * d.hw, hipMemcpyHostToDevice));
-	AGX_HIP_CHECK(hipMemcpy(d_signs, h_signs, count * sizeof(int), hipMemcpyHostToDevice));
-	hipLaunchKernelGGL(k_debug_load_tasks, dim3(count), dim3(64), 0, nullptr, d, d_boards, d_signs, count);
-	EngineDev dd = d;
-	dd.g0 = 0;
-	dd.nn_counter = 16;
-	dd.yield_fraction = 0.0f;
-	hipLaunchKernelGGL(k_reset_counter, dim3(1), dim3(1), 0, nullptr, dd.counters + dd.nn_counter, static_cast<int*>(nullptr));
-	launch_solve(dd, count, nullptr);
-	AGX_HIP_CHECK(hipGetLastError());
-	AGX_HIP_CHECK(hipDeviceSynchronize());
-	std::vector<DTask> tasks(1);
-	for (int g = 0; g < count; g++)
-	{
-		AGX_HIP_CHECK(hipMemcpy(tasks.data(), d.tasks + static_cast<size_t>(g) * d.batch, sizeof(DTask), hipMemcpyDeviceToHost));
-		const DTask &t = tasks[0];
-		h_counts[g] = t.n_edges;
-		h_flags[g] = t.flags;
-		h_result_scores[g] = static_cast<uint16_t>(t.score);
-		for (int i = 0; i < t.n_edges; i++)
-		{
-			h_moves[static_cast<size_t>(g) * d.hw + i] = t.emove[i];
-			h_scores[static_cast<size_t>(g) * d.hw + i] = t.escore[i];
-		}
-		if (h_features != nullptr)
-			AGX_HIP_CHECK(hipMemcpy(h_features + static_cast<size_t>(g) * d.hw, d.nn_features + static_cast<size_t>(g) * d.batch * d.hw, d.hw * sizeof(uint32_t),
-					hipMemcpyDeviceToHost));
-	}
-	{ // solver nodes of every position (GameState::stats[5]) for agx_debug_solve_nodes
-		std::vector<GameState> after(count);
-		AGX_HIP_CHECK(hipMemcpy(after.data(), d.games, static_cast<size_t>(count) * sizeof(GameState), hipMemcpyDeviceToHost));
-		e->debug_solve_nodes.resize(count);
-		for (int g = 0; g < count; g++)
-			e->debug_solve_nodes[g] = after[g].stats[5];
-	}
-	// leave the pool idle again
-	AGX_HIP_CHECK(hipMemcpy(d.games, e->idle_games.data(), e->idle_games.size() * sizeof(GameState), hipMemcpyHostToDevice)); // idle pool, arena descriptors intact
-	(void) hipFree(d_boards);
-	(void) hipFree(d_signs);
-	return AGX_OK;
-}
-
-int agx_debug_solve_nodes(AgxEngine *e, int count, unsigned long long *h_nodes)
-{
-	AGX_REQUIRE(e != nullptr && h_nodes != nullptr, AGX_ERR_INVALID, "agx_debug_solve_nodes: null argument");
-	AGX_REQUIRE(count >= 0 && static_cast<size_t>(count) <= e->debug_solve_nodes.size(), AGX_ERR_INVALID, "agx_debug_solve_nodes: the last agx_debug_solve solved %zu positions",
-			e->debug_solve_nodes.size());
-	for (int g = 0; g < count; g++)
-		h_nodes[g] = e->debug_solve_nodes[g];
-	return AGX_OK;
-}
-
-/*
- * OpeningGenerator::generate (src/selfplay/OpeningGenerator.cpp:21-78), batched: candidates from prepareOpening(config, 1), each
- * given to the threat solver with a 1000-node budget (:61-62) and redrawn (up to 100 times, :55) while the solver proves it; the
- * survivors are evaluated by the network and, in workspace order, accepted when |E - 0.5| < 0.1 + 0.01 * trials (:41-48).
- */
-int agx_engine_generate_openings(AgxEngine *e, AgxNet *net, int count, uint32_t seed, uint16_t *h_openings, int *h_stats)
-{
-	AGX_REQUIRE(e != nullptr && net != nullptr && h_openings != nullptr, AGX_ERR_INVALID, "agx_engine_generate_openings: null argument");
-	AGX_REQUIRE(count > 0, AGX_ERR_INVALID, "agx_engine_generate_openings: count must be positive");
-	AGX_REQUIRE(!e->begun, AGX_ERR_STATE, "agx_engine_generate_openings: the pool is playing (the generator borrows its task slots); call it before agx_engine_begin");
-	const EngineDev &d = e->dev;
-	const int W = std::min(d.n_games, 64); // workspace entries evaluated together (the reference uses max_batch_size of them)
-	struct Entry
-	{
-			uint16_t opening[AGX_OPENING_CAP];
-			bool scheduled = false;
-			float expectation = 0.0f;
-	};
-	std::vector<Entry> workspace(W);
-	std::vector<uint8_t> boards(static_cast<size_t>(W) * d.hw);
-	std::vector<int> signs(W), todo;
-	std::vector<DTask> task(1);
-	std::vector<float> values(static_cast<size_t>(W) * d.batch * 3);
-	uint8_t *d_boards = nullptr;
-	int *d_signs = nullptr;
-	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_boards), boards.size()));
-	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_signs), W * sizeof(int)));
-	EngineDev dd = d;
-	dd.g0 = 0;
-	dd.nn_counter = 16;
-	dd.yield_fraction = 0.0f;
-	dd.use_symmetries = 0;
-	dd.tss_max_nodes = 1000; // solver.setNodeLimit(1000)
-	int completed = 0, trials = 0;
-	long long stats[4] = { 0, 0, 0, 0 }; // candidates drawn, proven by the solver, rejected as unbalanced, network evaluations
-	int status = AGX_OK;
-	while (completed < count && status == AGX_OK)
-	{
-		for (int attempt = 0; attempt < 100; attempt++)
-		{
-			todo.clear();
-			for (int i = 0; i < W; i++)
-				if (!workspace[i].scheduled)
-					todo.push_back(i);
-			if (todo.empty())
-				break;
-			const int m = static_cast<int>(todo.size());
-			for (int j = 0; j < m; j++)
-			{
-				Entry &en = workspace[todo[j]];
-				if ((status = agx_make_opening(d.rules, d.n, seed++, en.opening)) != AGX_OK)
-					break;
-				stats[0]++;
-				uint8_t *b = boards.data() + static_cast<size_t>(j) * d.hw;
-				std::memset(b, 0, d.hw);
-				for (int k = 0; k < en.opening[0]; k++)
-				{
-					const uint16_t mv = en.opening[1 + k];
-					b[((mv >> 2) & 127) * d.n + ((mv >> 9) & 127)] = mv & 3;
-				}
-				signs[j] = (en.opening[0] == 0) ? AGX_CROSS : (3 - (en.opening[en.opening[0]] & 3));
-			}
-			if (status != AGX_OK)
-				break;
-			AGX_HIP_CHECK(hipMemcpy(d_boards, boards.data(), static_cast<size_t>(m) * d.hw, hipMemcpyHostToDevice));
-			AGX_HIP_CHECK(hipMemcpy(d_signs, signs.data(), m * sizeof(int), hipMemcpyHostToDevice));
-			hipLaunchKernelGGL(k_debug_load_tasks, dim3(m), dim3(64), 0, nullptr, dd, d_boards, d_signs, m);
-			hipLaunchKernelGGL(k_reset_counter, dim3(1), dim3(1), 0, nullptr, dd.counters + dd.nn_counter, static_cast<int*>(nullptr));
-			launch_solve(dd, m, nullptr);
-			AGX_HIP_CHECK(hipGetLastError());
-			// the unproven positions are in the pool's slot list exactly as after a search step: evaluate them
-			if ((status = agx_nn_forward_indirect(net, dd.nn_features, dd.nn_list, dd.counters + dd.nn_counter, m * dd.batch, dd.nn_policy, dd.nn_value, nullptr))
-					!= AGX_OK)
-				break;
-			AGX_HIP_CHECK(hipDeviceSynchronize());
-			AGX_HIP_CHECK(hipMemcpy(values.data(), dd.nn_value, static_cast<size_t>(m) * dd.batch * 3 * sizeof(float), hipMemcpyDeviceToHost));
-			for (int j = 0; j < m; j++)
-			{
-				AGX_HIP_CHECK(hipMemcpy(task.data(), dd.tasks + static_cast<size_t>(j) * dd.batch, offsetof(DTask, path_node), hipMemcpyDeviceToHost));
-				Entry &en = workspace[todo[j]];
-				if (task[0].needs_nn)
-				{
-					const float *v = values.data() + static_cast<size_t>(j) * dd.batch * 3;
-					en.expectation = v[0] + 0.5f * v[1];
-					en.scheduled = true;
-					stats[3]++;
-				}
-				else
-					stats[1]++;
-			}
-		}
-		if (status != AGX_OK)
-			break;
-		for (int i = 0; i < W && completed < count; i++)
-		{
-			Entry &en = workspace[i];
-			if (!en.scheduled)
-				continue; // proven 100 times in a row: the reference leaves such an entry for the next call as well
-			const float balance = std::fabs(en.expectation - 0.5f);
-			if (balance < (0.1f + 0.01f * trials))
-			{
-				std::memcpy(h_openings + static_cast<size_t>(completed) * AGX_OPENING_CAP, en.opening, sizeof(en.opening));
-				completed++;
-				trials = 0;
-			}
-			else
-			{
-				trials++;
-				stats[2]++;
-			}
-			en.scheduled = false;
-		}
-		for (Entry &en : workspace)
-			en.scheduled = false; // entries not consumed because enough openings were found
-	}
-	(void) hipMemcpy(d.games, e->idle_games.data(), e->idle_games.size() * sizeof(GameState), hipMemcpyHostToDevice); // leave the pool idle again
-	(void) hipFree(d_boards);
-	(void) hipFree(d_signs);
-	if (h_stats != nullptr)
-		for (int i = 0; i < 4; i++)
-			h_stats[i] = static_cast<int>(stats[i]);
-	return status;
-}
-
-int agx_debug_new_generation(AgxEngine *e)
-{ // AlphaBetaSearch::increaseGeneration (AlphaBetaSearch.cpp:63-66) for the positions agx_debug_solve solves: every game's solver table ages by one
-	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_debug_new_generation: null engine");
-	// (agx_debug_solve leaves the pool idle after every call: the generation lives in the idle template it restores)
-	for (GameState &g : e->idle_games)
-		g.generation = (g.generation + 1) % 64;
-	AGX_HIP_CHECK(hipMemcpy(e->dev.games, e->idle_games.data(), e->idle_games.size() * sizeof(GameState), hipMemcpyHostToDevice));
-	return AGX_OK;
-}
-
-int agx_debug_pattern_state(AgxEngine *e, const uint8_t *h_boards, const int *h_signs, const uint16_t *h_moves, int count, int n_moves, uint8_t *h_ptypes,
-		uint8_t *h_threats, int16_t *h_lists, int lists_stride)
-{
-	AGX_REQUIRE(e != nullptr, AGX_ERR_INVALID, "agx_debug_pattern_state: null engine");
-	AGX_REQUIRE(count > 0 && count <= e->dev.n_games, AGX_ERR_INVALID, "agx_debug_pattern_state: count must be in [1, n_games] (a position uses its game's spill areas)");
-	const EngineDev &d = e->dev;
-	uint8_t *d_boards = nullptr, *d_pt = nullptr, *d_th = nullptr;
-	int *d_signs = nullptr;
-	uint16_t *d_moves = nullptr;
-	int16_t *d_lists = nullptr;
-	const size_t cells = static_cast<size_t>(count) * d.hw;
-	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_boards), cells));
-	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_signs), count * sizeof(int)));
-	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_moves), std::max<size_t>(static_cast<size_t>(count) * n_moves * 2, 16)));
-	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_pt), cells * 8));
-	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_th), cells * 2));
-	AGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_lists), static_cast<size_t>(count) * lists_stride * 2));
-	AGX_HIP_CHECK(hipMemcpy(d_boards, h_boards, cells, hipMemcpyHostToDevice));
-	AGX_HIP_CHECK(hipMemcpy(d_signs, h_signs, count * sizeof(int), hipMemcpyHostToDevice));
-	if (n_moves > 0)
-		AGX_HIP_CHECK(hipMemcpy(d_moves, h_moves, static_cast<size_t>(count) * n_moves * 2, hipMemcpyHostToDevice));
-	hipLaunchKernelGGL(k_debug_pattern_state, dim3(count), dim3(64), 0, nullptr, d, d_boards, d_signs, d_moves, n_moves, d_pt, d_th, d_lists, lists_stride);
-	AGX_HIP_CHECK(hipGetLastError());
-	AGX_HIP_CHECK(hipDeviceSynchronize());
-	AGX_HIP_CHECK(hipMemcpy(h_ptypes, d_pt, cells * 8, hipMemcpyDeviceToHost));
-	AGX_HIP_CHECK(hipMemcpy(h_threats, d_th, cells * 2, hipMemcpyDeviceToHost));
-	AGX_HIP_CHECK(hipMemcpy(h_lists, d_lists, static_cast<size_t>(count) * lists_stride * 2, hipMemcpyDeviceToHost));
-	(void) hipFree(d_boards);
-	(void) hipFree(d_signs);
-	(void) hipFree(d_moves);
-	(void) hipFree(d_pt);
-	(void) hipFree(d_th);
-	(void) hipFree(d_lists);
-	return AGX_OK;
-}
-
-/* host-only: the lookup tables the engine uploads (for CPU-side verification against the reference) */
-int agx_host_tables(int rules, uint8_t *h_pattern, uint8_t *h_half_open_three, uint8_t *h_threat, uint16_t *h_defense)
-{
-	AGX_REQUIRE(rules >= 0 && rules <= AGX_CARO6, AGX_ERR_INVALID, "agx_host_tables: unknown rules %d", rules);
-	HostTables t;
-	build_host_tables(rules, t);
-	if (h_pattern != nullptr)
-		std::memcpy(h_pattern, t.pattern.data(), t.pattern.size());
-	if (h_half_open_three != nullptr)
-		std::memcpy(h_half_open_three, t.half_open_three.data(), t.half_open_three.size());
-	if (h_threat != nullptr)
-		std::memcpy(h_threat, t.threat.data(), t.threat.size());
-	if (h_defense != nullptr)
-		std::memcpy(h_defense, t.defense.data(), t.defense.size() * sizeof(uint16_t));
-	return AGX_OK;
-}
-
-} /* extern "C" */
-
-/* ================================================================================================================ */
-/* agx_position_solver_*: the threat solver on boards (k_solve_positions) */
-struct AgxPositionSolver
-{
-		int rules = 0, n = 0, capacity = 0, waves = 0;
-		int device = -1;
-		std::mutex mutex;
-		EngineDev dev; // only what solve_task reads: tables, limits, the per-wave areas, a task and a game record per wave
-		std::vector<void*> allocations;
-		unsigned long long device_bytes = 0, bytes_per_wave = 0;
-		AgxSolvedPositions workspace; // [capacity] outputs of agx_position_evaluator_evaluate_solved the caller did not ask for
-		// the waves of two launches share the per-wave areas: a call on another stream than the previous one is ordered behind it on the device
-		hipEvent_t done = nullptr;
-		hipStream_t last_stream = nullptr;
-		bool launched = false;
-};
-
-namespace
-{
-	typedef void (*SolvePositionsKernel)(EngineDev, SolvePositionsArgs);
-	SolvePositionsKernel solve_positions_kernel(int rules, int n)
-	{
-#ifdef AGX_QUICK
-		(void) rules;
-		(void) n;
-		return k_solve_positions<AGX_QUICK_RENJU, 15>;
-#else
-		if (rules == AGX_RENJU)
-			return (n == 15) ? k_solve_positions<true, 15> : k_solve_positions<true, 0>;
-		if (n == 15)
-			return k_solve_positions<false, 15>;
-		return (n == 20) ? k_solve_positions<false, 20> : k_solve_positions<false, 0>;
-#endif
-	}
-	template<typename T>
-	int solver_alloc(AgxPositionSolver *ps, T **ptr, size_t count, bool per_wave)
-	{
-		const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-		void *p = nullptr;
-		const hipError_t err = hipMalloc(&p, bytes);
-		if (err != hipSuccess)
-		{
-			(void) hipGetLastError();
-			agx::set_error("agx_position_solver_create: hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(err));
-			return AGX_ERR_HIP;
-		}
-		ps->allocations.push_back(p);
-		ps->device_bytes += bytes;
-		if (per_wave)
-			ps->bytes_per_wave += bytes / static_cast<size_t>(ps->waves);
-		*ptr = static_cast<T*>(p);
-		return AGX_OK;
-	}
-	template<typename T>
-	int solver_upload(AgxPositionSolver *ps, const T **ptr, const std::vector<T> &src)
-	{
-		T *p = nullptr;
-		const int st = solver_alloc(ps, &p, src.size(), false);
-		if (st != AGX_OK)
-			return st;
-		AGX_HIP_CHECK(hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-		*ptr = p;
-		return AGX_OK;
-	}
-}
-
-int agx::position_solver_describe(AgxPositionSolver *ps, int *rules, int *board_size, int *capacity, AgxSolvedPositions *workspace)
-{
-	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "null position solver");
-	*rules = ps->rules;
-	*board_size = ps->n;
-	*capacity = ps->capacity;
-	*workspace = ps->workspace;
-	return AGX_OK;
-}
-int agx::position_solver_mark(AgxPositionSolver *ps, hipStream_t stream)
-{
-	std::lock_guard<std::mutex> lock(ps->mutex);
-	AGX_HIP_CHECK(hipEventRecord(ps->done, stream));
-	ps->launched = true;
-	ps->last_stream = stream;
-	return AGX_OK;
-}
-
-extern "C" {
-
-int agx_position_solver_create(int rules, int board_size, int capacity, int max_positions, uint64_t table_entries, uint64_t zobrist_seed, AgxPositionSolver **out)
-{
-	AGX_REQUIRE(out != nullptr, AGX_ERR_INVALID, "agx_position_solver_create: null argument");
-	*out = nullptr;
-	AGX_REQUIRE(rules >= 0 && rules <= AGX_CARO6, AGX_ERR_INVALID, "agx_position_solver_create: unknown rules %d", rules);
-	AGX_REQUIRE(board_size >= 5 && board_size <= MAXN, AGX_ERR_UNSUPPORTED, "agx_position_solver_create: board size %d not in [5, %d]", board_size, MAXN);
-	AGX_REQUIRE(capacity > 0 && capacity <= (1 << 20), AGX_ERR_INVALID, "agx_position_solver_create: capacity %d", capacity);
-	AGX_REQUIRE(max_positions >= 1 && max_positions <= 1000, AGX_ERR_UNSUPPORTED, "agx_position_solver_create: max_positions must be in [1, 1000]");
-	AGX_REQUIRE(table_entries <= (1ull << 32), AGX_ERR_INVALID, "agx_position_solver_create: %llu table entries per wave (at most 2^32)",
-			static_cast<unsigned long long>(table_entries));
-	AgxPositionSolver *ps = new AgxPositionSolver();
-	ps->rules = rules;
-	ps->n = board_size;
-	ps->capacity = capacity;
-	std::memset(&ps->workspace, 0, sizeof(ps->workspace));
-	EngineDev &d = ps->dev;
-	std::memset(&d, 0, sizeof(d));
-	int status = AGX_OK, cus = 0;
-	if (hipGetDevice(&ps->device) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ps->device) != hipSuccess)
-	{
-		(void) hipGetLastError();
-		agx::set_error("agx_position_solver_create: no HIP device");
-		status = AGX_ERR_HIP;
-	}
-	// one wave per SIMD: k_solve_positions is compiled like k_solve, for the fastest single wave (uncapped registers), and every wave brings
-	// a table and spill areas of its own
-	ps->waves = std::min(capacity, 4 * std::max(1, cus));
-	if (const char *cap = std::getenv("AGX_POSSOLVE_MAX_WAVES"))
-		if (std::atoi(cap) > 0)
-			ps->waves = std::min(ps->waves, std::atoi(cap));
-	d.rules = rules;
-	d.n = board_size;
-	d.hw = board_size * board_size;
-	d.draw_after = d.hw;
-	d.n_games = ps->waves;
-	d.batch = d.batch_limit = 1;
-	d.tss_max_nodes = max_positions;
-	d.tss_max_depth = 100;
-	d.solve_time_ticks = 0ull;
-	d.zobrist_seed = zobrist_seed;
-	const size_t buckets = round_pow2(std::max<size_t>(table_entries, 4)) / 4;
-	d.tt_bucket_mask = buckets - 1;
-	d.act_cap = d.hw * (d.hw + 1) / 2 + 64;
-	d.tt_mod = ps->waves;
-	const size_t W = ps->waves, hw = d.hw, C = capacity;
-	HostTables tables;
-	build_host_tables(rules, tables);
-	std::vector<uint8_t> packed(4096); // cross type | circle type << 4 (dev_solver.hpp: threat_lookup)
-	for (int i = 0; i < 4096; i++)
-		packed[i] = static_cast<uint8_t>((tables.threat[2 * i] & 15u) | ((tables.threat[2 * i + 1] & 15u) << 4));
-#define AGX_TRY(expr) if (status == AGX_OK) status = (expr)
-	AGX_TRY(solver_alloc(ps, &d.tt, W * buckets * 8, true));
-	AGX_TRY(solver_alloc(ps, &d.act, W * d.act_cap, true));
-	AGX_TRY(solver_alloc(ps, &d.list_spill, W * 20 * static_cast<size_t>(MAXHW), true));
-	AGX_TRY(solver_alloc(ps, &d.frame_spill, W * MAX_FRAMES, true));
-	AGX_TRY(solver_alloc(ps, &d.snap_spill, W * (hw + 2) * 64, true)); // one undo-snapshot level per stone on the board, whatever the rules
-	AGX_TRY(solver_alloc(ps, &d.tasks, W, true));
-	AGX_TRY(solver_alloc(ps, &d.games, W, true));
-	AGX_TRY(solver_alloc(ps, &d.nn_features, W * hw, true)); // solve_task encodes the network input of its task on the way
-	AGX_TRY(solver_upload(ps, &d.t_pattern, tables.pattern));
-	AGX_TRY(solver_upload(ps, &d.t_ho3, tables.half_open_three));
-	AGX_TRY(solver_upload(ps, &d.t_threat, tables.threat));
-	AGX_TRY(solver_upload(ps, &d.t_threat_packed, packed));
-	AGX_TRY(solver_upload(ps, &d.t_defense, tables.defense));
-	AGX_TRY(solver_alloc(ps, &ps->workspace.score, C, false));
-	AGX_TRY(solver_alloc(ps, &ps->workspace.n_actions, C, false));
-	AGX_TRY(solver_alloc(ps, &ps->workspace.moves, C * hw, false));
-	AGX_TRY(solver_alloc(ps, &ps->workspace.move_scores, C * hw, false));
-	AGX_TRY(solver_alloc(ps, &ps->workspace.status, C, false));
-#undef AGX_TRY
-	if (status == AGX_OK && (hipMemset(d.games, 0, W * sizeof(GameState)) != hipSuccess || hipMemset(d.tasks, 0, W * sizeof(DTask)) != hipSuccess
-			|| hipEventCreateWithFlags(&ps->done, hipEventDisableTiming) != hipSuccess))
-	{
-		agx::set_error("agx_position_solver_create: clearing the per-wave records failed");
-		status = AGX_ERR_HIP;
-	}
-	if (status != AGX_OK)
-	{ // one way out for every failure: what was allocated is freed, *out stays null
-		const std::string message = agx_last_error();
-		agx_position_solver_destroy(ps);
-		agx::set_error("%s", message.c_str());
-		return status;
-	}
-	*out = ps;
-	return AGX_OK;
-}
-
-int agx_position_solver_destroy(AgxPositionSolver *ps)
-{
-	if (ps == nullptr)
-		return AGX_OK;
-	if (ps->launched)
-		(void) hipEventSynchronize(ps->done);
-	for (void *p : ps->allocations)
-		(void) hipFree(p);
-	if (ps->done != nullptr)
-		(void) hipEventDestroy(ps->done);
-	delete ps;
-	return AGX_OK;
-}
-
-int agx_position_solver_info(const AgxPositionSolver *ps, int *waves, uint64_t *bytes_per_wave, uint64_t *device_bytes)
-{
-	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "agx_position_solver_info: null solver");
-	if (waves != nullptr)
-		*waves = ps->waves;
-	if (bytes_per_wave != nullptr)
-		*bytes_per_wave = ps->bytes_per_wave;
-	if (device_bytes != nullptr)
-		*device_bytes = ps->device_bytes;
-	return AGX_OK;
-}
-
-int agx_position_solver_solve(AgxPositionSolver *ps, int n, const uint8_t *d_boards, const uint8_t *d_signs, const AgxSolvedPositions *out, void *stream_)
-{
-	AGX_REQUIRE(ps != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_position_solver_solve: null argument");
-	AGX_REQUIRE(n >= 0 && n <= ps->capacity, AGX_ERR_INVALID, "agx_position_solver_solve: %d positions, the solver was created for %d", n, ps->capacity);
-	if (n == 0)
-		return AGX_OK;
-	AGX_REQUIRE(d_boards != nullptr && d_signs != nullptr, AGX_ERR_INVALID, "agx_position_solver_solve: null boards or signs");
-	hipStream_t stream = static_cast<hipStream_t>(stream_);
-	std::lock_guard<std::mutex> lock(ps->mutex);
-	int current = -1;
-	AGX_HIP_CHECK(hipGetDevice(&current));
-	AGX_REQUIRE(current == ps->device, AGX_ERR_STATE, "agx_position_solver_solve: the solver lives on device %d, the calling thread's current device is %d", ps->device, current);
-	if (ps->launched && ps->last_stream != stream)
-		AGX_HIP_CHECK(hipStreamWaitEvent(stream, ps->done, 0));
-	SolvePositionsArgs A;
-	A.boards = d_boards;
-	A.signs = d_signs;
-	A.n = n;
-	A.out = *out;
-	hipLaunchKernelGGL(solve_positions_kernel(ps->rules, ps->n), dim3(std::min(n, ps->waves)), dim3(64), 0, stream, ps->dev, A);
-	const hipError_t launched = hipGetLastError();
-	AGX_HIP_CHECK(hipEventRecord(ps->done, stream));
-	ps->launched = true;
-	ps->last_stream = stream;
-	AGX_HIP_CHECK(launched);
-	return AGX_OK;
-}
-
-} /* extern "C" */
-
-/* ================================================================================================================ */
-/* agx_position_searcher_*: the whole search on boards (k_load_positions / k_harvest_positions around the engine's own stages) */
-struct AgxPositionSearcher
-{
-		AgxEngine *engine = nullptr;
-		int slots = 0, device = -1;
-		std::mutex mutex;
-		PositionJob job;      // the job in flight (device addresses); cursor / finished / slot_* are the searcher's own
-		int *state = nullptr;      // device: cursor, finished, slot_position[slots], slot_steps[slots]
-		int *poll_host = nullptr;  // pinned: two finished counts on their way back (search), then slot_position[slots] (slots)
-		hipEvent_t poll_event[2] = { nullptr, nullptr };
-		int job_n = 0;             // positions of the job in flight, 0 = none
-		int job_finished = 0;      // ... of which known to be finished
-		unsigned long long device_bytes = 0;
-		// the calls of one searcher share its pool: a call on another stream than the previous one is ordered behind it on the device
-		hipEvent_t done = nullptr;
-		hipStream_t last_stream = nullptr;
-		bool launched = false;
-};
-
-namespace
-{
-	int searcher_enter(AgxPositionSearcher *ps, hipStream_t stream, const char *what)
-	{ // (under the searcher's mutex) the calling thread's device, and the order behind the previous call's stream
-		int current = -1;
-		AGX_HIP_CHECK(hipGetDevice(&current));
-		AGX_REQUIRE(current == ps->device, AGX_ERR_STATE, "%s: the searcher lives on device %d, the calling thread's current device is %d", what, ps->device, current);
-		if (ps->launched && ps->last_stream != stream)
-			AGX_HIP_CHECK(hipStreamWaitEvent(stream, ps->done, 0));
-		return AGX_OK;
-	}
-	int searcher_leave(AgxPositionSearcher *ps, hipStream_t stream, int status)
-	{
-		const hipError_t launched = hipGetLastError();
-		AGX_HIP_CHECK(hipEventRecord(ps->done, stream));
-		ps->launched = true;
-		ps->last_stream = stream;
-		AGX_HIP_CHECK(launched);
-		return status;
-	}
-	EngineDev searcher_dev(const AgxPositionSearcher *ps)
-	{ // the pool as one group (agx_engine_*_group(e, 0, 1)); the engine's own record keeps what set_max_simulations / set_batch_size changed
-		EngineDev d = ps->engine->dev;
-		d.g0 = 0;
-		d.nn_counter = 16;
-		d.yield_counter = 32;
-		d.grp_first = 0;
-		d.grp_count = d.n_games;
-		return d;
-	}
-	int searcher_default_steps(const AgxPositionSearcher *ps)
-	{ // agx.h: agx_position_searcher_begin
-		const EngineDev &d = ps->engine->dev;
-		const long long steps = (static_cast<long long>(d.max_sims) + 2) * (2 * d.batch + 1) + ARENA_CLASSES;
-		return static_cast<int>(std::min<long long>(steps, 0x7FFFFFF0));
-	}
-	/* (under the mutex) is the job in flight finished?  Asks the device when the host does not know yet: waits for the previous call's stream only */
-	int searcher_job_open(AgxPositionSearcher *ps, bool *open)
-	{
-		*open = false;
-		if (ps->job_n == 0 || ps->job_finished >= ps->job_n)
-			return AGX_OK;
-		if (ps->launched)
-			AGX_HIP_CHECK(hipEventSynchronize(ps->done));
-		int finished = 0;
-		AGX_HIP_CHECK(hipMemcpy(&finished, ps->job.finished, sizeof(int), hipMemcpyDeviceToHost));
-		ps->job_finished = finished;
-		*open = finished < ps->job_n;
-		return AGX_OK;
-	}
-	int searcher_begin_locked(AgxPositionSearcher *ps, int n, const uint8_t *d_boards, const uint8_t *d_signs, const int32_t *d_serials,
-			const AgxPositionSearchOutputs *out, const AgxPositionSampleSink *sink, int max_pv, int max_steps, hipStream_t stream)
-	{
-		bool open = false;
-		const int st = searcher_job_open(ps, &open);
-		if (st != AGX_OK)
-			return st;
-		AGX_REQUIRE(!open, AGX_ERR_STATE, "agx_position_searcher_begin: the previous job has finished %d of its %d positions", ps->job_finished, ps->job_n);
-		const int entered = searcher_enter(ps, stream, "agx_position_searcher_begin");
-		if (entered != AGX_OK)
-			return entered;
-		ps->job.boards = d_boards;
-		ps->job.signs = d_signs;
-		ps->job.serials = d_serials;
-		ps->job.n = n;
-		ps->job.max_pv = max_pv;
-		ps->job.max_steps = (max_steps > 0) ? max_steps : searcher_default_steps(ps);
-		ps->job.out = *out;
-		std::memset(&ps->job.sink, 0, sizeof(ps->job.sink));
-		if (sink != nullptr && sink->d_bytes != nullptr && sink->d_sizes != nullptr)
-			ps->job.sink = *sink;
-		ps->job_n = n;
-		ps->job_finished = 0;
-		const EngineDev d = searcher_dev(ps);
-		hipLaunchKernelGGL(k_positions_reset, dim3(1), dim3(1), 0, stream, ps->job);
-		hipLaunchKernelGGL(k_load_positions, dim3(ps->slots), dim3(256), 0, stream, d, ps->job);
-		return searcher_leave(ps, stream, AGX_OK);
-	}
-	int searcher_begin_checks(AgxPositionSearcher *ps, int n, const uint8_t *d_boards, const uint8_t *d_signs, const AgxPositionSearchOutputs *out, int max_pv, const char *what)
-	{
-		AGX_REQUIRE(ps != nullptr && out != nullptr, AGX_ERR_INVALID, "%s: null argument", what);
-		AGX_REQUIRE(n >= 0, AGX_ERR_INVALID, "%s: %d positions", what, n);
-		AGX_REQUIRE(max_pv >= 0 && max_pv <= MAXHW, AGX_ERR_INVALID, "%s: max_pv %d outside [0, %d]", what, max_pv, MAXHW);
-		AGX_REQUIRE(n == 0 || (d_boards != nullptr && d_signs != nullptr), AGX_ERR_INVALID, "%s: null boards or signs", what);
-		return AGX_OK;
-	}
-	int searcher_sink_checks(const AgxPositionSearcher *ps, const AgxPositionSampleSink *sink, const char *what)
-	{ // (after searcher_begin_checks) a sample never outgrows its stride: 16 bytes and at most one entry per cell
-		if (sink == nullptr || sink->d_bytes == nullptr || sink->d_sizes == nullptr)
-			return AGX_OK;
-		const int needed = agx::v201::HEADER_BYTES + agx::v201::ENTRY_BYTES * ps->engine->dev.hw;
-		AGX_REQUIRE(sink->stride >= needed && sink->stride % 4 == 0, AGX_ERR_INVALID, "%s: a sample stride of %d bytes (at least %d and a multiple of 4 expected)", what,
-				sink->stride, needed);
-		return AGX_OK;
-	}
-	int searcher_harvest_locked(AgxPositionSearcher *ps, hipStream_t stream)
-	{ // harvest -> arena service -> load: ordered by the launch order on one stream, as the stages behind k_advance are
-		const EngineDev d = searcher_dev(ps);
-		hipLaunchKernelGGL(k_harvest_positions, dim3(ps->slots), dim3(64), 0, stream, d, ps->job);
-		hipLaunchKernelGGL(k_arena_service, dim3(1), dim3(1024), 0, stream, d, ps->slots, 0);
-		hipLaunchKernelGGL(k_arena_copy, dim3(ps->slots * CLEAR_PARTS), dim3(256), 0, stream, d, CLEAR_PARTS); // (its last part per game commits)
-		hipLaunchKernelGGL(k_load_positions, dim3(ps->slots), dim3(256), 0, stream, d, ps->job);
-		return AGX_OK;
-	}
-}
-
-int agx::position_searcher_describe(AgxPositionSearcher *ps, int *rules, int *board_size, int *slots)
-{
-	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "position searcher: null searcher");
-	*rules = ps->engine->dev.rules;
-	*board_size = ps->engine->dev.n;
-	*slots = ps->slots;
-	return AGX_OK;
-}
-
-extern "C" {
-
-int agx_position_searcher_create(const AgxEngineConfig *cfg, AgxPositionSearcher **out)
-{
-	AGX_REQUIRE(cfg != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_position_searcher_create: null argument");
-	*out = nullptr;
-	AGX_REQUIRE(!cfg->match_mode, AGX_ERR_UNSUPPORTED, "agx_position_searcher_create: match_mode pools play matches, they search no positions");
-	AGX_REQUIRE(cfg->search_threads <= 1 && cfg->search_buffers <= 1, AGX_ERR_UNSUPPORTED,
-			"agx_position_searcher_create: search_threads > 1 / search_buffers > 1 make the pool one tree; the searcher needs a tree per slot");
-	AgxEngineConfig own = *cfg;
-	own.record_format = 0; // nothing is played: no move records, no samples, no finished games
-	own.record_capacity = 1;
-	own.record_edge_capacity = 1;
-	own.record_sample_capacity = 4;
-	own.game_end_capacity = 1;
-	AgxEngine *engine = nullptr;
-	const int created = agx_engine_create(&own, &engine);
-	if (created != AGX_OK)
-		return created;
-	AgxPositionSearcher *ps = new AgxPositionSearcher();
-	ps->engine = engine;
-	ps->slots = cfg->n_games;
-	std::memset(&ps->job, 0, sizeof(ps->job));
-	const size_t words = 2 + 2 * static_cast<size_t>(ps->slots);
-	int status = AGX_OK;
-	if (hipGetDevice(&ps->device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&ps->state), words * sizeof(int)) != hipSuccess
-			|| hipHostMalloc(reinterpret_cast<void**>(&ps->poll_host), (2 + static_cast<size_t>(ps->slots)) * sizeof(int)) != hipSuccess
-			|| hipEventCreateWithFlags(&ps->done, hipEventDisableTiming) != hipSuccess
-			|| hipEventCreateWithFlags(&ps->poll_event[0], hipEventDisableTiming) != hipSuccess
-			|| hipEventCreateWithFlags(&ps->poll_event[1], hipEventDisableTiming) != hipSuccess)
-	{
-		(void) hipGetLastError();
-		agx::set_error("agx_position_searcher_create: allocating the slot records failed");
-		status = AGX_ERR_HIP;
-	}
-	if (status == AGX_OK)
-	{
-		ps->job.cursor = ps->state;
-		ps->job.finished = ps->state + 1;
-		ps->job.slot_position = ps->state + 2;
-		ps->job.slot_steps = ps->state + 2 + ps->slots;
-		ps->device_bytes = engine->device_bytes + words * sizeof(int);
-		hipLaunchKernelGGL(k_positions_init, dim3(ps->slots), dim3(64), 0, nullptr, engine->dev, ps->job);
-		if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)
-		{
-			(void) hipGetLastError();
-			agx::set_error("agx_position_searcher_create: the launch that idles the slots failed");
-			status = AGX_ERR_HIP;
-		}
-		engine->begun = true; // (the staged calls are the engine's own; its slots take positions where a pool takes openings)
-	}
-	if (status != AGX_OK)
-	{
-		const std::string message = agx_last_error();
-		agx_position_searcher_destroy(ps);
-		agx::set_error("%s", message.c_str());
-		return status;
-	}
-	*out = ps;
-	return AGX_OK;
-}
-
-int agx_position_searcher_destroy(AgxPositionSearcher *ps)
-{
-	if (ps == nullptr)
-		return AGX_OK;
-	if (ps->launched)
-		(void) hipEventSynchronize(ps->done);
-	if (ps->state != nullptr)
-		(void) hipFree(ps->state);
-	if (ps->poll_host != nullptr)
-		(void) hipHostFree(ps->poll_host);
-	for (hipEvent_t ev : { ps->done, ps->poll_event[0], ps->poll_event[1] })
-		if (ev != nullptr)
-			(void) hipEventDestroy(ev);
-	(void) agx_engine_destroy(ps->engine);
-	delete ps;
-	return AGX_OK;
-}
-
-int agx_position_searcher_info(const AgxPositionSearcher *ps, int *slots, uint64_t *device_bytes)
-{
-	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "agx_position_searcher_info: null searcher");
-	if (slots != nullptr)
-		*slots = ps->slots;
-	if (device_bytes != nullptr)
-		*device_bytes = ps->device_bytes;
-	return AGX_OK;
-}
-
-int agx_position_searcher_engine(AgxPositionSearcher *ps, AgxEngine **out)
-{
-	AGX_REQUIRE(ps != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_position_searcher_engine: null argument");
-	*out = ps->engine;
-	return AGX_OK;
-}
-
-int agx_position_searcher_begin(AgxPositionSearcher *ps, int n, const uint8_t *d_boards, const uint8_t *d_signs, const int32_t *d_serials,
-		const AgxPositionSearchOutputs *out, int max_pv, int max_steps, void *stream)
-{
-	return agx_position_searcher_begin_ex(ps, n, d_boards, d_signs, d_serials, out, nullptr, max_pv, max_steps, stream);
-}
-
-int agx_position_searcher_begin_ex(AgxPositionSearcher *ps, int n, const uint8_t *d_boards, const uint8_t *d_signs, const int32_t *d_serials,
-		const AgxPositionSearchOutputs *out, const AgxPositionSampleSink *sink, int max_pv, int max_steps, void *stream)
-{
-	int st = searcher_begin_checks(ps, n, d_boards, d_signs, out, max_pv, "agx_position_searcher_begin");
-	if (st == AGX_OK)
-		st = searcher_sink_checks(ps, sink, "agx_position_searcher_begin");
-	if (st != AGX_OK || n == 0)
-		return st;
-	std::lock_guard<std::mutex> lock(ps->mutex);
-	return searcher_begin_locked(ps, n, d_boards, d_signs, d_serials, out, sink, max_pv, max_steps, static_cast<hipStream_t>(stream));
-}
-
-int agx_position_searcher_select_solve(AgxPositionSearcher *ps, void *stream)
-{
-	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "agx_position_searcher_select_solve: null searcher");
-	std::lock_guard<std::mutex> lock(ps->mutex);
-	const int st = searcher_enter(ps, static_cast<hipStream_t>(stream), "agx_position_searcher_select_solve");
-	if (st != AGX_OK)
-		return st;
-	return searcher_leave(ps, static_cast<hipStream_t>(stream), agx_engine_select_solve_group(ps->engine, 0, 1, stream));
-}
-
-int agx_position_searcher_buffers(AgxPositionSearcher *ps, AgxEngineBuffers *out)
-{
-	AGX_REQUIRE(ps != nullptr && out != nullptr, AGX_ERR_INVALID, "agx_position_searcher_buffers: null argument");
-	return agx_engine_buffers(ps->engine, out);
-}
-
-int agx_position_searcher_evaluate(AgxPositionSearcher *ps, AgxNet *net, void *stream)
-{
-	AGX_REQUIRE(ps != nullptr && net != nullptr, AGX_ERR_INVALID, "agx_position_searcher_evaluate: null argument");
-	std::lock_guard<std::mutex> lock(ps->mutex);
-	const int st = searcher_enter(ps, static_cast<hipStream_t>(stream), "agx_position_searcher_evaluate");
-	if (st != AGX_OK)
-		return st;
-	return searcher_leave(ps, static_cast<hipStream_t>(stream), agx_engine_evaluate_group(ps->engine, net, 0, 1, stream));
-}
-
-int agx_position_searcher_expand(AgxPositionSearcher *ps, void *stream)
-{
-	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "agx_position_searcher_expand: null searcher");
-	std::lock_guard<std::mutex> lock(ps->mutex);
-	const int st = searcher_enter(ps, static_cast<hipStream_t>(stream), "agx_position_searcher_expand");
-	if (st != AGX_OK)
-		return st;
-	return searcher_leave(ps, static_cast<hipStream_t>(stream), expand_stage(ps->engine, 0, 1, stream, false)); // (the harvest stage services the arenas)
-}
-
-int agx_position_searcher_harvest(AgxPositionSearcher *ps, void *stream)
-{
-	AGX_REQUIRE(ps != nullptr, AGX_ERR_INVALID, "agx_position_searcher_harvest: null searcher");
-	std::lock_guard<std::mutex> lock(ps->mutex);
-	const int st = searcher_enter(ps, static_cast<hipStream_t>(stream), "agx_position_searcher_harvest");
-	if (st != AGX_OK)
-		return st;
-	return searcher_leave(ps, static_cast<hipStream_t>(stream), searcher_harvest_locked(ps, static_cast<hipStream_t>(stream)));
-}
-
-int agx_position_searcher_slots(AgxPositionSearcher *ps, void *stream, int *h_position_of_slot)
-{
-	AGX_REQUIRE(ps != nullptr && h_position_of_slot != nullptr, AGX_ERR_INVALID, "agx_position_searcher_slots: null argument");
-	std::lock_guard<std::mutex> lock(ps->mutex);
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	const int st = searcher_enter(ps, s, "agx_position_searcher_slots");
-	if (st != AGX_OK)
-		return st;
-	AGX_HIP_CHECK(hipMemcpyAsync(ps->poll_host + 2, ps->job.slot_position, ps->slots * sizeof(int), hipMemcpyDeviceToHost, s));
-	AGX_HIP_CHECK(hipStreamSynchronize(s));
-	std::memcpy(h_position_of_slot, ps->poll_host + 2, ps->slots * sizeof(int));
-	return AGX_OK;
-}
-
-int agx_position_searcher_finished(AgxPositionSearcher *ps, void *stream, int *count)
-{
-	AGX_REQUIRE(ps != nullptr && count != nullptr, AGX_ERR_INVALID, "agx_position_searcher_finished: null argument");
-	std::lock_guard<std::mutex> lock(ps->mutex);
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	const int st = searcher_enter(ps, s, "agx_position_searcher_finished");
-	if (st != AGX_OK)
-		return st;
-	if (ps->job_n == 0)
-	{
-		*count = 0;
-		return AGX_OK;
-	}
-	AGX_HIP_CHECK(hipMemcpyAsync(ps->poll_host, ps->job.finished, sizeof(int), hipMemcpyDeviceToHost, s));
-	AGX_HIP_CHECK(hipStreamSynchronize(s));
-	ps->job_finished = ps->poll_host[0];
-	*count = ps->job_finished;
-	return AGX_OK;
-}
-
-int agx_position_searcher_search(AgxPositionSearcher *ps, AgxNet *net, int n, const uint8_t *d_boards, const uint8_t *d_signs, const int32_t *d_serials,
-		const AgxPositionSearchOutputs *out, int max_pv, int max_steps, void *stream_)
-{
-	return agx_position_searcher_search_ex(ps, net, n, d_boards, d_signs, d_serials, out, nullptr, max_pv, max_steps, stream_);
-}
-
-int agx_position_searcher_search_ex(AgxPositionSearcher *ps, AgxNet *net, int n, const uint8_t *d_boards, const uint8_t *d_signs, const int32_t *d_serials,
-		const AgxPositionSearchOutputs *out, const AgxPositionSampleSink *sink, int max_pv, int max_steps, void *stream_)
-{
-	int checked = searcher_begin_checks(ps, n, d_boards, d_signs, out, max_pv, "agx_position_searcher_search");
-	if (checked == AGX_OK)
-		checked = searcher_sink_checks(ps, sink, "agx_position_searcher_search");
-	if (checked != AGX_OK)
-		return checked;
-	AGX_REQUIRE(net != nullptr, AGX_ERR_INVALID, "agx_position_searcher_search: null network");
-	if (n == 0)
-		return AGX_OK;
-	hipStream_t stream = static_cast<hipStream_t>(stream_);
-	std::lock_guard<std::mutex> lock(ps->mutex);
-	int st = searcher_begin_locked(ps, n, d_boards, d_signs, d_serials, out, sink, max_pv, max_steps, stream);
-	if (st != AGX_OK)
-		return st;
-	// every position finishes within max_steps steps of its load, a slot loads a new one in the step that finishes the old one: the slots work
-	// through the list in at most ceil(n / slots) rounds of max_steps steps
-	const long long rounds = (static_cast<long long>(n) + ps->slots - 1) / ps->slots;
-	const long long step_bound = rounds * ps->job.max_steps + 1;
-	constexpr int POLL_EVERY = 4; // steps between two reads of the finished counter; the read of the previous poll is awaited, so POLL_EVERY steps stay queued
-	int polls = 0;
-	bool all_finished = false;
-	for (long long step = 0; !all_finished && step < step_bound + 2 * POLL_EVERY; step++)
-	{
-		st = agx_engine_select_solve_group(ps->engine, 0, 1, stream_);
-		if (st == AGX_OK)
-			st = agx_engine_evaluate_group(ps->engine, net, 0, 1, stream_);
-		if (st == AGX_OK)
-			st = expand_stage(ps->engine, 0, 1, stream_, false);
-		if (st == AGX_OK)
-			st = searcher_harvest_locked(ps, stream);
-		if (st != AGX_OK)
-			break;
-		if ((step + 1) % POLL_EVERY != 0)
-			continue;
-		const int slot = polls & 1;
-		if (hipMemcpyAsync(ps->poll_host + slot, ps->job.finished, sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess
-				|| hipEventRecord(ps->poll_event[slot], stream) != hipSuccess)
-		{
-			agx::set_error("agx_position_searcher_search: queuing a read of the finished counter failed: %s", hipGetErrorString(hipGetLastError()));
-			st = AGX_ERR_HIP;
-			break;
-		}
-		polls++;
-		if (polls >= 2)
-		{ // the poll before this one: its steps were queued POLL_EVERY steps ago
-			st = agx_event_synchronize(ps->poll_event[slot ^ 1]);
-			if (st != AGX_OK)
-				break;
-			ps->job_finished = ps->poll_host[slot ^ 1];
-			all_finished = ps->job_finished >= n;
-		}
-	}
-	(void) searcher_leave(ps, stream, AGX_OK);
-	const hipError_t drained = hipStreamSynchronize(stream);
-	if (st != AGX_OK)
-		return st;
-	AGX_HIP_CHECK(drained);
-	int finished = 0;
-	AGX_HIP_CHECK(hipMemcpy(&finished, ps->job.finished, sizeof(int), hipMemcpyDeviceToHost));
-	ps->job_finished = finished;
-	AGX_REQUIRE(finished >= n, AGX_ERR_STATE, "agx_position_searcher_search: %d of %d positions finished within the step bound", finished, n);
-	return AGX_OK;
-}
-
-} /* extern "C" */
+#undef AGX_FOR_SHAPE

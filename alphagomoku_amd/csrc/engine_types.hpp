@@ -13,6 +13,9 @@
 #define AGX_ENGINE_TYPES_HPP_
 
 #include <cstdint>
+#include <hip/hip_vector_types.h>
+
+#include "../../include/agx.h"
 
 namespace agx
 {
@@ -21,6 +24,8 @@ namespace agx
 	constexpr int BWORDS = 13;      // 2 bits per cell, 32 cells per 64-bit word (NodeCache.hpp:56)
 	constexpr int PATH_CAP = 256;
 	constexpr int SPEC_PARK_POOL = 128;   // park buffers of a pool (a launch parks a handful of solves; none free = the solve simply runs on)
+	// the fraction of a launch's games after which a running speculative solve is parked (engine.hip "Parking"; EngineDev::park_fraction)
+	constexpr float SPEC_PARK_FRACTION = 0.90f; // (C5 on one box: 0.80 484 k, 0.86 511 k, 0.90 520 k, 0.94 469 k, 0.97 406 k simulations/s; without parking 408 k)
 	constexpr int SPEC_PARK_WORDS = 2048 + 8; // 64-bit words per park buffer: the largest solver state (16 064 bytes at 20x20) + the solve's loop variables
 	constexpr int MAX_FRAMES = 104; // alpha-beta recursion depth is bounded by the iterative-deepening limit (100 plies) + root
 	constexpr int OPENING_CAP = 32;
@@ -310,6 +315,48 @@ namespace agx
 			// overrides the plain fields above in its by-value copy of E with player[g >= n_games / 2] (dev::use_player_search); every other
 			// launch — self-play, tournament, position search, a match pool stepped group by group — reads the plain fields as the host wrote them
 			PlayerSearchDev player[2];
+	};
+
+	/* ---- the small records a launch takes by value next to EngineDev: filled by the host layer, read by the kernels of engine.hip ---- */
+	constexpr int ADV_THREADS = 1024; // threads per game of k_advance (engine.hip)
+	constexpr int CLEAR_PARTS = 16; // workgroups per game in k_clear_tables / k_arena_copy
+
+	/* agx_engine_match_track_pairs: what a match pool keeps about its PAIR RESULTS — the points the first player took from one opening
+	 * played twice with the colours swapped (2 per win, 1 per draw: 0..4), which is what a sequential test consumes one at a time
+	 * (the reference's get_points / convert_match_results in front of GSPRT).  head[0..4] histogram of the points, [5] results seen (logged
+	 * or not), [6] flags (1 log full, 2 an opening was skipped, 4 inconsistent scores), [7] log launches, [8] cursor = entries written;
+	 * shadow[pair] = (games_done, won, drawn, lost) as of the pair's last logged opening. */
+	struct PairLogDev
+	{
+			long long *head = nullptr;
+			int4 *shadow = nullptr;
+			AgxPairResult *entries = nullptr;
+			int capacity = 0;
+	};
+	constexpr int PAIR_LOG_HEAD = 16; // long longs in front of the shadows (9 used; keeps the int4 shadows 16-byte aligned)
+
+	/* agx_position_searcher_*: the job in flight (k_positions_init / _reset, k_load_positions, k_harvest_positions) */
+	struct PositionJob
+	{
+			const uint8_t *boards;  // [n][hw] 0 empty, 1 cross, 2 circle
+			const uint8_t *signs;   // [n] 1 cross, 2 circle to move
+			const int32_t *serials; // [n] noise / symmetry serial (GameState::opening_id), null = 0
+			int n, max_pv, max_steps;
+			AgxPositionSearchOutputs out; // each may be null
+			AgxPositionSampleSink sink;   // format-201 samples (position_write_sample); d_bytes or d_sizes null = none
+			int *cursor;        // next position of the list
+			int *finished;      // positions whose outputs are written
+			int *slot_position; // [n_games] the position a slot searches, -1 = free
+			int *slot_steps;    // [n_games] steps the slot has spent on it
+	};
+
+	/* agx_position_solver_solve: one batch of boards (k_solve_positions) */
+	struct SolvePositionsArgs
+	{
+			const uint8_t *boards; // [n][hw] 0 empty, 1 cross, 2 circle
+			const uint8_t *signs;  // [n] 1 cross, 2 circle
+			int n;
+			AgxSolvedPositions out; // each may be null
 	};
 }
 

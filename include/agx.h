@@ -959,7 +959,7 @@ int agx_position_evaluator_evaluate(AgxPositionEvaluator* pe, AgxNet* net, int n
 		int flags, int top_k, const AgxPositionOutputs* out, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
- * Positions solved on the device: boards -> proven scores and the solver's action lists (k_solve_positions, csrc/engine.hip).
+ * Positions solved on the device: boards -> proven scores and the solver's action lists (k_solve_positions in csrc/engine.hip; the host side is csrc/position_solver.cpp).
  * The threat solver of the search (AlphaBetaSearch) for callers that hold boards: filtering provable samples out of a training set, puzzle
  * sets, opening checks, a move suggestion that respects forced defences.  Every position is solved as a fresh AlphaBetaSearch with an empty
  * table and node limit max_positions would solve it, so a position's result is a function of the position and of the arguments of
@@ -1025,7 +1025,7 @@ int agx_position_evaluator_evaluate_solved(AgxPositionEvaluator* pe, AgxPosition
 
 /* ----------------------------------------------------------------------------------------------
  * Positions searched on the device: boards -> the root of a full search (PUCT, threat solver and network together, max_simulations
- * playouts per position; k_load_positions / k_harvest_positions, csrc/engine.hip).  Re-searching old samples with a newer network, puzzle
+ * playouts per position; k_load_positions / k_harvest_positions in csrc/engine.hip; the host side is csrc/position_searcher.cpp).  Re-searching old samples with a newer network, puzzle
  * suites, opening checks, a move for a mid-game position at full search strength.
  *
  * Position i = (board[i], sign_to_move[i], serial[i], default 0) is searched exactly as a freshly created self-play GameGenerator would
